@@ -5,6 +5,7 @@ A "step" is one pass of the hot path (classify -> compact -> per-site rate ML ->
 all-gather of PI tables when N > 1) over one batch of synthetic loci already resident in HBM.
 
   python bench.py                       one GPU, workload C3 (100 loci x 50 000 columns x 64 taxa): the headline
+  python bench.py --full                the same, plus the measurements and checks that need work of their own (below)
   python bench.py --workload C4         one GPU, the WHOLE 8-GPU config C4 (50 000 loci x 1 000 x 64; 3.2 GB: it fits)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W
@@ -14,10 +15,17 @@ all-gather of PI tables when N > 1) over one batch of synthetic loci already res
       config alone and requires the gathered table to be bit-identical to its own.
 
 Prints ONE JSON line on rank 0 (contract in the round prompt) with the extra objects `roofline` (dominant
-kernel = site_rate_kernel; algorithmic bytes = (ntaxa + 24) per column), `fp64` (the bound
-that actually binds this path) and `cpu_baseline` (the CPU oracle timed on the box's host cores on a
-bounded sample of the same workload, one core and all usable cores; a reported baseline, not the target),
-whose `parity_sample` is the GPU-vs-oracle gate SURVEY 8d attaches to every measurement: the run fails on a mismatch.
+kernel = site_rate_kernel; algorithmic bytes = (ntaxa + 24) per column) and `fp64` (the bound
+that actually binds this path), both from the HIP events of the timed steps themselves.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds everything that needs work of its
+own: the device-copy HBM roof (`roofline.hbm_copy_measured_gbs`), the stage-1 sample (`stage1`), `cpu_baseline` (the
+CPU oracle timed on the host's cores on a bounded sample of the same workload, one core and all usable cores; a
+reported baseline, not the target) whose `parity_sample` is the GPU-vs-oracle gate SURVEY 8d attaches to every
+measurement (the run fails on a mismatch), and for N > 1 rank 0's single-GPU run of the whole config.
+
+`--dump-outputs DIR` writes what the last timed step returned (per-column outputs and PI table, a fixed seeded sample
+where they are large) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -38,6 +46,13 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FP64_VALU_PEAK_TFLOPS = 78.6  # MI355X FP64 vector peak
+
+# --dump-outputs stays under 64 MB: at most DUMP_COLUMNS columns of the per-column outputs (40 B per column with their
+# index) and DUMP_TABLE_BYTES of PI table rows; larger outputs are sampled, the same entries on every run (DUMP_SEED)
+DUMP_SEED = 20261016
+DUMP_COLUMNS = 1 << 20
+DUMP_TABLE_BYTES = 16 << 20
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def flops_per_eval(oc):
@@ -65,6 +80,34 @@ def usable_cpus():
     return max(1, n)
 
 
+def dump_outputs(path, cols, tables):
+    """--dump-outputs: the per-column outputs `cols` (name -> [ncols] array) and the [L, W] PI table `tables` of the last
+    timed step, torch tensors or numpy arrays, as path/<name>.npy.  Float64 stays float64, flags and counts become
+    float32 (exact); beyond DUMP_COLUMNS columns or DUMP_TABLE_BYTES of table, a sample fixed by DUMP_SEED, whose
+    indices are written as column_index / locus_index (float64, exact)."""
+    def sample(n, k):
+        if n <= k:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+    def take(a, idx):
+        if isinstance(a, np.ndarray):
+            return a[idx]
+        import torch
+        return a[torch.from_numpy(idx).to(a.device)].cpu().numpy()
+
+    ci = sample(len(next(iter(cols.values()))), DUMP_COLUMNS)
+    li = sample(tables.shape[0], max(1, DUMP_TABLE_BYTES // (8 * tables.shape[1])))
+    out = {k: take(v, ci) for k, v in cols.items()}
+    out.update(tables=take(tables, li), column_index=ci, locus_index=li)
+    out = {k: v.astype(np.float64 if v.dtype.itemsize == 8 else np.float32) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 # ---- CPU oracle legs (bench.py's cpu_baseline is one of the three places allowed to call oracle/) ----------------
 
 def _oracle_job(job):
@@ -90,9 +133,14 @@ def main():
     ap.add_argument("--workload", default=None, choices=["C2", "C3", "C4", "C5", "R1"],
                     help="default: C3 on one GPU (the headline), C4 dealt over the ranks when --gpus > 1")
     ap.add_argument("--loci", type=int, default=None, help="override the number of loci of the config (experiments)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration per leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what needs work of its own: HBM copy roof, stage-1 sample, CPU baseline with its parity "
+                         "gate, and for N > 1 the single-GPU check of the gathered table")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32/float64, sampled when large)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU-baseline duration per leg (0 = skip)")
     ap.add_argument("--stage1-loci", type=int, default=16,
-                    help="also time HyPhy's stage 1 (model-averaged exchangeabilities) on the first N loci (0 = skip)")
+                    help="--full: also time HyPhy's stage 1 (model-averaged exchangeabilities) on the first N loci (0 = skip)")
     ap.add_argument("--gamma-categories", type=int, default=1,
                     help="K > 1: opt-in discrete-gamma rate mixture in the site-rate stage (alpha 0.5); not the headline config")
     ap.add_argument("--integ-mode", type=int, default=0, help="0 = QUADPACK emulation (reference parity), 1 = closed form")
@@ -100,8 +148,10 @@ def main():
                     help="N > 1 ranks all on cuda:0 with a gloo process group (tables staged through the host for the "
                          "collective): rehearses the sharded code path on a one-GPU box; not a measurement")
     ap.add_argument("--no-single-gpu-check", action="store_true",
-                    help="N > 1: skip rank 0's run of the whole config (the bit-identity check of the gathered table)")
+                    help="N > 1 with --full: skip rank 0's run of the whole config (the bit-identity check of the gathered table)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.workload == "R1":
         return real_data_workload(args)
@@ -115,7 +165,8 @@ def main():
     # touches the GPU (a fork of a process that holds a HIP context inherits its KFD state), and sit idle until the
     # GPU part is over.
     cpu_pool, cpu_workers = None, 0
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    single_gpu_check = args.full and world > 1 and not args.no_single_gpu_check
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         import multiprocessing
         from oracle import oracle as orc
         orc.build()
@@ -158,7 +209,7 @@ def main():
     if world > 1:
         idx = torch.from_numpy(mine).to(dev)
         d_states = data["states"].view(ntaxa, nloci_full, ncols)[:, idx, :].reshape(ntaxa, nloci * ncols).contiguous()
-        if rank != 0 or args.no_single_gpu_check:
+        if rank != 0 or not single_gpu_check:
             data["states"] = None   # only rank 0 needs the whole batch again (single-GPU check)
     else:
         d_states = data["states"]
@@ -232,9 +283,11 @@ def main():
     achieved = alg_bytes / (site_avg_ms * 1e-3) / 1e9 if site_avg_ms > 0 else 0.0
 
     table = result["table"]
+    if args.dump_outputs and rank == 0:   # N > 1: rank 0's share of the per-column outputs, the gathered table
+        dump_outputs(args.dump_outputs, {k: B[k] for k in ("rate", "subst", "lnl", "flag", "nres")}, table)
     table_sha = hashlib.sha256(table.cpu().numpy().tobytes()).hexdigest() if rank == 0 else None
     single_check = None
-    if world > 1 and rank == 0 and not args.no_single_gpu_check:
+    if single_gpu_check and rank == 0:
         # the whole config on this one GPU: the gathered table of the sharded run must carry the same bits
         full_plan = make_plan(np.arange(nloci_full))
         FB = buffers(full_plan, nloci_full)
@@ -249,7 +302,7 @@ def main():
 
     # what the HBM roof is on this very device: a device-to-device copy of 1 GiB (read + write counted)
     hbm_copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         src = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -321,9 +374,9 @@ def main():
         out["rehearsal"] = "all %d ranks on cuda:0, gloo collective through the host: NOT a measurement" % world
 
     parity_failure = None
-    if rank == 0 and world == 1 and args.stage1_loci > 0:
+    if args.full and rank == 0 and world == 1 and args.stage1_loci > 0:
         out["stage1"] = stage1_sample(data, pin, min(args.stage1_loci, nloci), ncols, ntaxa, times, intervals)
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         out["cpu_baseline"], parity_failure = cpu_baseline(cpu_pool, cpu_workers, data, pin, nloci, ncols, ntaxa, times,
                                                            intervals, args, B, plan)
     if cpu_pool is not None:
@@ -398,6 +451,8 @@ def real_data_workload(args):
             raise SystemExit("PARITY FAILURE: de-duplication changed `%s`" % k)
     n = L * S
     a = res["auto"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: a["out"][k] for k in ("rate", "subst", "lnl", "flag", "nres")}, a["out"]["tables"])
     alg = n * (len(names) + 24)
     print(json.dumps({
         "metric": "alignment columns/sec (site-rate+PI)", "value": n / (a["ms"] * 1e-3), "unit": "columns/s", "n_gpus": 1,

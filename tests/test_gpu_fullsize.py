@@ -10,6 +10,7 @@ a sampled comparison with the oracle.  The oracle cannot process 5 x 10^7 column
   * three random 400-column slices agree with the CPU oracle to the usual tolerances.
 All property checks run on the device (nothing but the oracle samples crosses PCIe), so the whole file takes minutes.
 """
+import hashlib
 import json
 import os
 import subprocess
@@ -189,9 +190,28 @@ def test_bench_two_rank_rehearsal_matches_single_gpu_table():
     single-GPU run of the whole config) rehearsed with two ranks sharing this box's one GPU (gloo collective through
     the host; RCCL itself is covered by the one-rank launches above).  The run fails unless the gathered table is
     bit-identical to the single-GPU table; the hash must also equal a plain one-process run's."""
-    common = ["--workload", "C4", "--loci", "3001", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0", "--stage1-loci", "0"]
+    common = ["--workload", "C4", "--loci", "3001", "--steps", "1", "--warmup", "1", "--full", "--cpu-seconds", "0",
+              "--stage1-loci", "0"]
     two = _bench(["--gpus", "2", "--rehearse-on-one-gpu"] + common, nproc=2)
     one = _bench(["--gpus", "1"] + common)
     assert two["n_gpus"] == 2 and two["scaling"] == "strong" and two["gathered_equals_single_gpu"] is True
     assert two["config"]["loci_per_gpu"] == 1501 and two["config"]["total_columns"] == 3001 * 1000
     assert two["table_sha256"] == one["table_sha256"]
+
+
+def test_bench_dump_outputs_are_the_timed_steps_outputs(tmp_path):
+    """bench.py --dump-outputs on a plain run: the files hold the outputs of the timed path (the dumped PI table hashes
+    to the line's table_sha256, the flags to its counts), whole at this size, float64 / exact float32."""
+    from tapir_amd import synth
+    out = _bench(["--gpus", "1", "--workload", "C2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert "cpu_baseline" not in out and "stage1" not in out and out["roofline"]["hbm_copy_measured_gbs"] is None
+    d = {f.stem: np.load(f) for f in tmp_path.iterdir()}
+    nloci, ncols = synth.WORKLOADS["C2"][:2]
+    assert np.array_equal(d["column_index"], np.arange(nloci * ncols)) and np.array_equal(d["locus_index"], np.arange(nloci))
+    for k in ("rate", "subst", "lnl", "tables"):
+        assert d[k].dtype == np.float64, k
+    assert d["flag"].dtype == np.float32 and d["nres"].dtype == np.float32
+    assert hashlib.sha256(d["tables"].tobytes()).hexdigest() == out["table_sha256"]
+    counts = np.bincount(d["flag"].astype(np.int64), minlength=5)
+    assert counts.tolist() == [out["flags"][k] for k in ("ok", "flat", "saturated", "zero", "maxit")]
+    assert np.isfinite(d["lnl"]).all() and (d["nres"] <= 16).all()

@@ -836,3 +836,35 @@ def test_fused_tree_program_expands_to_the_plain_one(tmp_path):
                                   if plain[i][0] == TIP_SET and plain[i + 1][0] == TIP_MUL and plain[i][2] == plain[i + 1][2]) > 0
             if ntaxa == 64:
                 assert ncherry == 21 and len(fused) == 105
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 stays float64, flags and counts become exact float32, outputs beyond the budget
+    are sampled at the same sorted indices on every call, and the files stay under 64 MB in all."""
+    import importlib
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    bench = importlib.import_module("bench")
+    n, L, W = 3 * bench.DUMP_COLUMNS, 40000, 112                # more columns and table rows than the budget holds
+    rng = np.random.default_rng(3)
+    cols = dict(rate=rng.random(n), flag=rng.integers(0, 5, n).astype(np.uint8), nres=rng.integers(0, 257, n).astype(np.int32))
+    tables = rng.random((L, W))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        bench.dump_outputs(str(d), cols, tables)
+        dumps.append({f.stem: np.load(f) for f in d.iterdir()})
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    a, b = dumps
+    assert sorted(a) == ["column_index", "flag", "locus_index", "nres", "rate", "tables"]
+    for k in a:
+        assert a[k].dtype == (np.float32 if k in ("flag", "nres") else np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    ci, li = a["column_index"].astype(np.int64), a["locus_index"].astype(np.int64)
+    assert len(ci) == bench.DUMP_COLUMNS and np.all(np.diff(ci) > 0) and ci[-1] < n
+    assert 0 < len(li) < L and np.all(np.diff(li) > 0) and a["tables"].shape == (len(li), W)
+    assert np.array_equal(a["rate"], cols["rate"][ci]) and np.array_equal(a["tables"], tables[li])
+    assert np.array_equal(a["flag"], cols["flag"][ci]) and np.array_equal(a["nres"], cols["nres"][ci])
+    # small outputs are written whole
+    d = tmp_path / "small"
+    bench.dump_outputs(str(d), {k: v[:1000] for k, v in cols.items()}, tables[:7])
+    assert np.array_equal(np.load(d / "column_index.npy"), np.arange(1000)) and np.array_equal(np.load(d / "tables.npy"), tables[:7])

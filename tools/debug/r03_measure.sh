@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r03_final
 mkdir -p $OUT
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "default bench failed"; tail -3 $OUT/bench_default.err; }
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "default bench failed"; tail -3 $OUT/bench_default.err; }
 python bench.py --workload C2 --steps 20 --warmup 5 --cpu-seconds 0 --stage1-loci 0 > $OUT/c2.json 2>/dev/null
 python bench.py --workload C5 --steps 3 --warmup 1 --cpu-seconds 0 --stage1-loci 0 > $OUT/c5_full_1gpu.json 2>/dev/null
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --workload C4 --steps 5 --warmup 2 --cpu-seconds 0 --stage1-loci 0 2>/dev/null | grep "^{" > $OUT/c4_full_1rank_torchrun.json
