@@ -36,8 +36,12 @@ __global__ void split_sum_kernel(const double* part, double* out, int64_t ncand,
     out[i] = s;
 }
 
-// State masks of the block's columns: either staged in LDS (all loads of a column block in flight at once, then
-// LDS-latency reads in the sweeps) or, for trees too large for that, read from global memory op by op.
+// State masks of the block's columns: read from global memory op by op, or (locus_grad_kernel, where it pays) staged in
+// LDS first: all loads of a column block in flight at once, then LDS-latency reads in the sweeps.
+__device__ inline unsigned lik_global_mask(const LikParams& P, int taxon, int64_t c) {
+    const unsigned m = P.states[(int64_t)taxon * P.ncols_total + c] & 15u;
+    return m ? m : 15u;
+}
 __device__ inline void lik_stage_states(const LikParams& P, uint8_t* sts, int64_t c, int block) {
     for (int t = 0; t < P.ntaxa; ++t) {
         unsigned m = P.states[(int64_t)t * P.ncols_total + c] & 15u;
@@ -46,8 +50,7 @@ __device__ inline void lik_stage_states(const LikParams& P, uint8_t* sts, int64_
 }
 __device__ inline unsigned lik_tip_mask(const LikParams& P, const uint8_t* sts, int taxon, int64_t c, int block) {
     if (P.stage_states) return sts[taxon * block + threadIdx.x];
-    const unsigned m = P.states[(int64_t)taxon * P.ncols_total + c] & 15u;
-    return m ? m : 15u;
+    return lik_global_mask(P, taxon, c);
 }
 
 // locus_loglik_kernel: value only.  Works in the eigenbasis of Q = U Lambda U^-1 (reversible, so U^-1 = U^T diag(pi)):
@@ -59,7 +62,6 @@ __global__ __launch_bounds__(kLikBlock) void locus_loglik_kernel(LikParams P) {
     extern __shared__ double lds[];
     double* ET = lds;                                   // [nnodes][4] exp(lam_k t_b)
     double* stack = ET + (size_t)P.nnodes * 4;          // [depth][4][kLikBlock]
-    uint8_t* sts = (uint8_t*)(stack + (size_t)P.stack_depth * 4 * kLikBlock);   // [ntaxa][kLikBlock] when staged
     __shared__ double eig[4 + 16 + 16];                 // lam[4], U[16], Ui[16]
     __shared__ double tipY[16 * 4];
     __shared__ double red[kLikBlock / 64];
@@ -102,13 +104,12 @@ __global__ __launch_bounds__(kLikBlock) void locus_loglik_kernel(LikParams P) {
         const int64_t c = active ? col : lo;
         double acc[4] = {1.0, 1.0, 1.0, 1.0};
         int scale = 0, sp = 0;
-        if (P.stage_states) lik_stage_states(P, sts, c, kLikBlock);
         int4 nxt = P.lops[0];
         for (int ip = 0; ip < P.nops; ++ip) {
             const int4 op = nxt;
             if (ip + 1 < P.nops) nxt = P.lops[ip + 1];
             if (op.x <= OP_TIP_MUL) {
-                const unsigned m = lik_tip_mask(P, sts, op.y, c, kLikBlock);
+                const unsigned m = lik_global_mask(P, op.y, c);
                 const double* et = ET + (size_t)op.z * 4;
                 double z[4];
 #pragma unroll

@@ -20,6 +20,7 @@ struct LikParams {
     int32_t nops;
     int32_t ntaxa;
     int32_t stage_states;          // 1: the block's state masks are staged in LDS [ntaxa][block] before each sweep
+                                   // (locus_grad_kernel only)
     int32_t nnodes;
     int32_t stack_depth;
     const int32_t* cand_locus;     // [ncand]

@@ -319,8 +319,8 @@ __device__ __forceinline__ uint32_t pick_word(const uint32_t (&pk)[NW > 0 ? NW :
 // NW = kStreamWords: more than 64 tips -- the packed words would take 16+ registers and push the kernel past 256
 //         VGPRs (one wave per SIMD).  Only word 0 stays in a register; word w + 1 is requested from the packed array
 //         (L2-resident: 4 bytes per 8 tips per evaluation) when word w is started, i.e. eight ops before it is needed;
-// NW = 0: states are fetched from the byte array one op ahead (the eval_columns diagnostic, which thereby
-//         cross-checks the packed paths, and TPHIP_FORCE_BYTE_PATH).
+// NW = 0: states are fetched from the byte array one op ahead (eval_columns_kernel only: the diagnostic thereby
+//         cross-checks the packed paths).
 // SPILL: the parked partials beyond the first P.lds_depth live in a global scratch row of this wave (L2-resident)
 //        instead of LDS.  On a deep tree (256 taxa: 4 parked partials = 24 KB of LDS per wave) the LDS stack, not the
 //        registers, caps the CU at 6 waves; the deepest slot is used by ~1 push in 9, so parking it in global memory

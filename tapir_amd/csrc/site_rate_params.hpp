@@ -100,7 +100,7 @@ struct EvalParams {
 };
 
 // ---- launchers defined in site_rate_launch.hip ------------------------------------------------------------------
-// variant: 0 = byte path (NW = 0), 2 / 8 = packed words in registers, kStreamWords = streamed words (> 64 tips),
+// variant: 2 / 8 = packed words in registers, kStreamWords = streamed words (> 64 tips),
 // kStreamWordsSpill = the same with the deepest parked partials in global scratch (S.spill, S.lds_depth)
 hipError_t launch_site_rate_kernel(int variant, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S);
 hipError_t site_rate_kernel_occupancy(int variant, size_t lds_bytes, int* blocks_per_cu);

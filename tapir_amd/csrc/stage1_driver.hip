@@ -247,7 +247,7 @@ extern "C" int tphip_stage1_fit_dev(tphip_plan* p, const uint8_t* d_states, cons
         X.o_exch = A.take<double>(P * 6); X.pi = A.take<double>(P * 4); X.hist = A.take<unsigned long long>(P * 16);
         CandArrays C = take_cands(A, cap);
         // general model
-        G.P = L; G.D = D; G.nb = nb; G.nn = nn; G.bspace_metric = getenv("TPHIP_S1_LOGMETRIC") ? 0 : 1; G.node_coord = X.node_coord; G.branches = X.branches; G.dk = X.dk;
+        G.P = L; G.D = D; G.nb = nb; G.nn = nn; G.node_coord = X.node_coord; G.branches = X.branches; G.dk = X.dk;
         G.node_w = X.node_w; G.partner = X.partner;
         G.x = A.take<double>(P * D); G.g = A.take<double>(P * D); G.hd = A.take<double>(P * D); G.d = A.take<double>(P * D);
         G.xt = A.take<double>(P * D); G.S = A.take<double>((size_t)kHistory * P * D); G.Y = A.take<double>((size_t)kHistory * P * D);
@@ -358,7 +358,7 @@ extern "C" int tphip_stage1_fit_dev(tphip_plan* p, const uint8_t* d_states, cons
     // hard to beat (21.2 iterations against 22.0); but where the input lengths are off -- each branch by a factor exp(N(0, 2)):
     // 36 iterations from the grid start, and 472 of 500 loci end hundreds of log-units lower with a few branches parked at
     // saturating lengths, where the gradient vanishes -- the counts keep every start inside the region the data support
-    // (24.7 iterations, tools/debug/s1_start_perturbed.py).  TPHIP_S1_START = grid | shrunk (default) | pars | both.
+    // (24.7 iterations, tools/debug/s1_start_perturbed.py).  TPHIP_S1_START=grid (a test hook) keeps the grid start alone.
     {
         bool postorder = nn <= kParsMaxNodes && desc->parent[nn - 1] < 0;
         for (int n = 0; n + 1 < nn && postorder; ++n) postorder = desc->parent[n] > n && desc->parent[n] < nn;
@@ -370,16 +370,11 @@ extern "C" int tphip_stage1_fit_dev(tphip_plan* p, const uint8_t* d_states, cons
             hipLaunchKernelGGL(branch_parsimony_kernel, dim3((unsigned)L, ny), dim3(128), sizeof(double) * (nn + 1), st, d_states, p->ncols,
                                p->d_offsets.p, p->d_col_weight, nn, X.parent, X.leaf, X.pchanges);
             KCHECK();
-            const double alpha_env = getenv("TPHIP_S1_PARS_ALPHA") ? atof(getenv("TPHIP_S1_PARS_ALPHA")) : 0.5;
-            for (int pass = 0; pass < 2; ++pass) {   // the counts shrunk towards the grid start; the counts alone (experiments)
-                const bool on = pass == 0 ? !(env && !strcmp(env, "pars")) : (env && (!strcmp(env, "pars") || !strcmp(env, "both")));
-                if (!on) continue;
-                hipLaunchKernelGGL(grm_pars_emit_kernel, dim3((unsigned)L), dim3(64), sizeof(double) * D, st, G, X.pchanges, pass == 0 ? alpha_env : -1.0);
-                KCHECK();
-                RC(dr.value(G.C, G.vecs, (int64_t)L));
-                hipLaunchKernelGGL(grm_pars_pick_kernel, dim3((unsigned)L), dim3(64), 0, st, G, X.counters + C_PARS, 0.0);
-                KCHECK();
-            }
+            hipLaunchKernelGGL(grm_pars_emit_kernel, dim3((unsigned)L), dim3(64), sizeof(double) * D, st, G, X.pchanges);
+            KCHECK();
+            RC(dr.value(G.C, G.vecs, (int64_t)L));
+            hipLaunchKernelGGL(grm_pars_pick_kernel, dim3((unsigned)L), dim3(64), 0, st, G, X.counters + C_PARS, 0.0);
+            KCHECK();
         }
     }
     // optimiser state

@@ -85,7 +85,7 @@ __device__ inline double backtrack(double t, double ft, double f0, double gd) {
 // ---------------------------------------------------------------------------------------------------------------------
 struct GrmState {
     int32_t P, D, nb, nn;
-    int32_t bspace_metric;       // 1: initial metric of a branch coordinate from the Newton step of b itself (grm_direction_kernel)
+    int32_t unused;              // (free slot: the offsets of the fields below, and so the kernels' code, stay as they were)
     // Branch coordinates.  On a reversible model the likelihood depends on the two branches below a bifurcating root only
     // through their SUM (P(b1) P(b2) = P(b1 + b2) across the root): left as two coordinates that is an exactly flat, in
     // log-coordinates curved, direction, which made quasi-Newton steps overshoot for hundreds of iterations on some loci.  The
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64) void grm_direction_kernel(GrmState G) {
     for (int j = lane; j < D; j += 64) {
         double h = hd[j];
         any_h |= isfinite(h);
-        if (G.bspace_metric && j >= 5 && isfinite(h)) {
+        if (j >= 5 && isfinite(h)) {
             // The curvature in log b is a poor model of a short branch: there lnL is close to LINEAR in b, so in log b the
             // second derivative h = b^2 f'' + b f' nearly cancels against the first (g = b f') and a Newton step -g / h is
             // tens of log-units (seen: g = -0.09, h = 9e-4), clipped, and the line search then shortens EVERY coordinate's
@@ -498,13 +498,12 @@ __global__ __launch_bounds__(128) void branch_parsimony_kernel(const uint8_t* st
     for (int n = threadIdx.x; n <= nn; n += blockDim.x)
         if (acc[n] != 0.0) atomicAdd(&changes[(size_t)l * (nn + 1) + n], acc[n]);
 }
-// the parsimony point of every problem: rates 1, b = -3/4 log(1 - 4/3 p) with p = changes per column on the branch (at least
-// kParsFloor changes, at most 0.6 per column) -> G.xt and value candidate p.  block = one wave = one problem
-constexpr double kParsFloor = 0.3;
-// alpha >= 0: the counts shrunk towards the grid start b0 (kept in G.d by grm_grid_pick_kernel) as a Gamma prior of alpha
+// the parsimony point of every problem: rates 1, b_pars = -3/4 log(1 - 4/3 p) with p = changes per column on the branch (at
+// most 0.6), shrunk towards the grid start b0 (kept in G.d by grm_grid_pick_kernel) as a Gamma prior of alpha = kParsAlpha
 // pseudo-changes: b = (b_pars W + alpha) / (W + alpha / b0) -- branches with many changes follow the data, branches with
-// hardly any follow the input tree's shape
-__global__ __launch_bounds__(64) void grm_pars_emit_kernel(GrmState G, const double* changes, double alpha) {
+// hardly any follow the input tree's shape -> G.xt and value candidate p.  block = one wave = one problem
+constexpr double kParsAlpha = 0.5;
+__global__ __launch_bounds__(64) void grm_pars_emit_kernel(GrmState G, const double* changes) {
     extern __shared__ double xs[];   // [D]
     const int p = blockIdx.x, lane = threadIdx.x;
     const double* ch = changes + (size_t)p * (G.nn + 1);
@@ -515,12 +514,9 @@ __global__ __launch_bounds__(64) void grm_pars_emit_kernel(GrmState G, const dou
         if (j >= 5) {
             const int n = G.branches[j - 5], n2 = G.partner[j - 5];
             const double c = ch[n] + (n2 >= 0 ? ch[n2] : 0.0);
-            const double pc = fmin(fmax(c, alpha >= 0.0 ? 0.0 : kParsFloor) / W, 0.6);
-            double b = -0.75 * log1p(-pc * (4.0 / 3.0));
-            if (alpha >= 0.0) {
-                const double b0 = exp(G.d[(size_t)p * G.D + j]);
-                b = (b * W + alpha) / (W + alpha / b0);
-            }
+            const double pc = fmin(fmax(c, 0.0) / W, 0.6);
+            const double b0 = exp(G.d[(size_t)p * G.D + j]);
+            const double b = (-0.75 * log1p(-pc * (4.0 / 3.0)) * W + kParsAlpha) / (W + kParsAlpha / b0);
             v = fmax(fmin(log(b), kLogBlenMax), kLogBlenMin);
         }
         xt[j] = v;

@@ -317,7 +317,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             std::vector<int4> rops;
             int32_t rdepth = 0;
             const std::string gerr = build_grad2_program(d->nnodes, d->parent, d->leaf_taxon, tape_slot, tip_pos, &rops, &rdepth);
-            if (gerr.empty() && rdepth <= kGrad2MaxRDepth && !getenv("TPHIP_GRAD_EIGENBASIS")) {
+            if (gerr.empty() && rdepth <= kGrad2MaxRDepth) {
                 e = p->d_grad2_fops.upload(fops);
                 if (e == hipSuccess) e = p->d_grad2_rops.upload(rops);
                 p->grad2_nrops = (int32_t)(rops.size() / 2);
@@ -384,12 +384,9 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
                 }
             }
         }
-        // locus likelihood (value) kernel: staging the state masks in LDS costs it more than it saves (measured 13.6 ms
-        // vs 10.0 ms per 1616 candidates x 20000 columns x 64 taxa); opt-in for experiments
+        // locus likelihood (value) kernel: no staging of the state masks in LDS, which cost it more than it saved (measured
+        // 13.6 ms vs 10.0 ms per 1616 candidates x 20000 columns x 64 taxa)
         p->lik_lds = ((size_t)p->nnodes * 4 + (size_t)p->prog.stack_depth * 4 * kLikBlock) * sizeof(double);
-        const size_t lik_stage_bytes = (size_t)p->ntaxa * kLikBlock;
-        p->lik_stage = (getenv("TPHIP_LIK_STAGE") && lik_stage_bytes <= 48 * 1024 && p->lik_lds + lik_stage_bytes <= 150 * 1024) ? 1 : 0;
-        if (p->lik_stage) p->lik_lds += lik_stage_bytes;
         p->lik_ok = p->lik_lds <= 150 * 1024;
         if (p->lik_ok && p->lik_lds > 64 * 1024)
             p->lik_ok = locus_loglik_kernel_allow_lds(150 * 1024) == hipSuccess;
@@ -415,7 +412,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             p->grad_slots >>= 1;
         p->grad_lds = (size_t)p->nnodes * (kGradEF + 2 * kGradWaves * p->grad_slots) * sizeof(double);
         const size_t grad_stage_bytes = (size_t)p->ntaxa * kGradBlock;
-        p->grad_stage = (!getenv("TPHIP_LIK_NO_STAGE") && grad_stage_bytes <= 48 * 1024 && p->grad_lds + grad_stage_bytes <= 150 * 1024) ? 1 : 0;
+        p->grad_stage = (grad_stage_bytes <= 48 * 1024 && p->grad_lds + grad_stage_bytes <= 150 * 1024) ? 1 : 0;
         if (p->grad_stage) p->grad_lds += grad_stage_bytes;
         p->grad_ok = p->grad_lds <= 150 * 1024;
         if (p->grad_ok && p->grad_lds > 64 * 1024)
@@ -427,7 +424,6 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             // blocks per CU (390 MB of tape) ran slower than 3 (91 vs 85 ms); fewer than 3 loses more to latency
             const size_t tape_per_block = (size_t)std::max(1, p->prog.ntape + p->prog.stack_depth) * 4 * kGradBlock * sizeof(double);
             if (tape_per_block * (size_t)p->num_cus * (size_t)bpc > ((size_t)300 << 20)) bpc = std::min(bpc, 3);
-            if (const char* env = getenv("TPHIP_GRAD_BLOCKS_PER_CU")) bpc = std::max(1, atoi(env));
             p->grad_blocks_per_cu = bpc;
         }
         // transition-matrix gradient kernel: LDS = tip table + tipY + parked adjoints + per-branch accumulators + state codes
@@ -439,12 +435,9 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             if (p->grad2_ok) {
                 int bpc = 1;
                 if (locus_grad2_kernel_occupancy(p->prog.stack_depth, p->grad2_lds, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-                if (const char* env = getenv("TPHIP_GRAD2_BLOCKS_PER_CU")) bpc = std::max(1, atoi(env));
                 p->grad2_blocks_per_cu = bpc;
             }
         }
-        if (const char* env = getenv("TPHIP_LIK_NSPLIT")) p->lik_nsplit_forced = std::max(1, atoi(env));
-        if (const char* fb = getenv("TPHIP_FORCE_BYTE_PATH")) p->force_byte_path = (fb[0] == '1');
         // Small batches (an equal share would be under ~1000 columns) leave the persistent grid: the mixed-loci mode below,
         // or one workgroup per locus-aligned slice (cutting a small locus in two doubles its prologue and drain: measured on C2).
         p->site_persistent = (ncols / p->site_waves >= 1000) ? 1 : 0;
@@ -454,9 +447,9 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             p->site_waves = per_cu * prop.multiProcessorCount;
         }
         // Small batches of trees up to 64 taxa: equal shares of the work list, a wave carrying columns of several loci at
-        // once (site_rate_kernel<NW, false, true>); the slice mode remains for the streamed-words and byte paths.
-        p->site_mixed = (!p->site_persistent && p->nwords <= 8 && !p->force_byte_path && ncols < ((int64_t)1 << kMixedColBits)) ? 1 : 0;
-        if (const char* em = getenv("TPHIP_SITE_MIXED")) p->site_mixed = (em[0] == '1') && p->nwords <= 8 && !p->force_byte_path && ncols < ((int64_t)1 << kMixedColBits);
+        // once (site_rate_kernel<NW, false, true>); the slice mode remains for the streamed words.
+        p->site_mixed = (!p->site_persistent && p->nwords <= 8 && ncols < ((int64_t)1 << kMixedColBits)) ? 1 : 0;
+        if (const char* em = getenv("TPHIP_SITE_MIXED")) p->site_mixed = (em[0] == '1') && p->nwords <= 8 && ncols < ((int64_t)1 << kMixedColBits);
         if (p->site_mixed) {
             int per3 = 0;
             const size_t lds3 = (kMixedLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
@@ -509,7 +502,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     // workspace layout
     size_t off = 0;
     p->ws_work_cols = off; off = align_up(off + sizeof(int32_t) * (size_t)ncols, 256);
-    if (!p->site_persistent && !getenv("TPHIP_SITE_NO_REORDER")) {   // small batches: slow-columns-first copy of the work list
+    if (!p->site_persistent) {   // small batches: slow-columns-first copy of the work list
         p->ws_work_cols2 = off; off = align_up(off + sizeof(int32_t) * (size_t)ncols, 256);
     }
     p->ws_work_count = off; off = align_up(off + sizeof(int32_t) * (size_t)d->nloci, 256);
@@ -702,24 +695,20 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
     // profiling brackets exactly the dominant kernel, so the figure matches rocprofv3's per-kernel average
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 0], st));
     if (p->n_site_chunks > 0) {
-        const bool mixed = p->site_mixed && !p->force_byte_path;
+        const bool mixed = p->site_mixed;
         const dim3 grid((unsigned)(mixed ? p->site_waves : p->site_persistent ? p->site_waves * p->site_grid_mult : p->n_site_chunks));
-        // packed tip states: in registers up to 64 tips, streamed one word ahead beyond (site_rate_kernel.hpp)
-        const bool byte_path = p->force_byte_path;   // test/tuning knob, resolved at plan creation
-        if (!byte_path) {  // the packed path reads the stream with fused cherries (tree_program.hpp)
-            S.ops = p->d_fused_ops.p;
-            S.nops = (int32_t)p->prog.fused_ops.size();
-        }
-        // variants: byte path; packed words in registers (<= 16 / <= 64 tips); streamed words (more than 64 tips)
+        // the packed tip states are read with the fused-cherry stream (tree_program.hpp)
+        S.ops = p->d_fused_ops.p;
+        S.nops = (int32_t)p->prog.fused_ops.size();
+        // variants: packed words in registers (<= 16 / <= 64 tips); streamed one word ahead (more than 64 tips)
         const size_t lds_full = (kSiteLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
-        const int variant = byte_path ? 0 : p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : (spill ? kStreamWordsSpill : kStreamWords);
-        if (byte_path) { S.lds_depth = p->prog.stack_depth; S.spill = nullptr; }
+        const int variant = p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : (spill ? kStreamWordsSpill : kStreamWords);
         if (mixed) {   // equal shares: first_round = grid
             const size_t lds_mixed = (kMixedLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
             S.first_fraction = 1.0;
             HIP_TRY(launch_site_rate_kernel(kMixedVariant + variant, grid, lds_mixed, st, S));
         } else
-        HIP_TRY(launch_site_rate_kernel(variant, grid, (byte_path || !spill) ? lds_full : lds, st, S));
+        HIP_TRY(launch_site_rate_kernel(variant, grid, spill ? lds : lds_full, st, S));
     }
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 1], st));
     if (dedup) dedup_scatter_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
@@ -864,7 +853,6 @@ int tphip_quad_townsend_dev(int32_t device, const double* d_rates, int64_t n, do
 // Slices per candidate for the locus likelihood / gradient kernels: enough work items to fill the device even when
 // only a few candidates are in flight (the general model's one point per locus), never more than a locus has blocks.
 static int lik_nsplit(const tphip_plan* p, int64_t ncand, int block) {
-    if (p->lik_nsplit_forced > 0) return p->lik_nsplit_forced;
     const int64_t target = (int64_t)p->num_cus * 8;
     int64_t ns = (target + ncand - 1) / std::max<int64_t>(ncand, 1);
     const int64_t max_blocks = std::max<int64_t>(1, (p->max_locus_cols + block - 1) / block);
@@ -872,11 +860,12 @@ static int lik_nsplit(const tphip_plan* p, int64_t ncand, int block) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(ns, 4096));
 }
 
-static int grow_part(tphip_plan* p, size_t need) {
-    if (need <= p->part_bytes) return TPHIP_OK;
-    if (p->d_part) { HIP_TRY(hipFree(p->d_part)); p->d_part = nullptr; p->part_bytes = 0; }
-    HIP_TRY(hipMalloc((void**)&p->d_part, need));
-    p->part_bytes = need;
+// device buffer grown on demand (its contents are not kept)
+static int grow(void** ptr, size_t& have, size_t need) {
+    if (need <= have && *ptr) return TPHIP_OK;
+    if (*ptr) { HIP_TRY(hipFree(*ptr)); *ptr = nullptr; have = 0; }
+    HIP_TRY(hipMalloc(ptr, need ? need : 1));
+    have = need;
     return TPHIP_OK;
 }
 
@@ -902,19 +891,15 @@ int tphip_locus_loglik_dev(tphip_plan* p, const uint8_t* d_states, int64_t ncand
         const int C = p->value_cols;
         const int nsplit = lik_nsplit(p, ncand, kLikBlock * C);
         if (nsplit > 1) {
-            int rc = grow_part(p, (size_t)ncand * nsplit * sizeof(double));
+            int rc = grow((void**)&p->d_part, p->part_bytes, (size_t)ncand * nsplit * sizeof(double));
             if (rc) return rc;
         }
         const size_t per_cand = ((size_t)p->nnodes * 16 + 36) * sizeof(double);
         int64_t chunk = std::max<int64_t>(1, (int64_t)(kValueWorkspaceBytes / per_cand));
         chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, ((int64_t)1 << 30) / nsplit));   // grid.x limit
         chunk = std::min<int64_t>(chunk, ncand);
-        const size_t need = (size_t)chunk * per_cand;
-        if (need > p->value_ws_bytes) {
-            if (p->d_value_ws) { HIP_TRY(hipFree(p->d_value_ws)); p->d_value_ws = nullptr; p->value_ws_bytes = 0; }
-            HIP_TRY(hipMalloc((void**)&p->d_value_ws, need));
-            p->value_ws_bytes = need;
-        }
+        int rc = grow((void**)&p->d_value_ws, p->value_ws_bytes, (size_t)chunk * per_cand);
+        if (rc) return rc;
         double* d_eig = p->d_value_ws;
         double* d_pmat = p->d_value_ws + (size_t)chunk * 36;
         ValueParams V;
@@ -941,11 +926,10 @@ int tphip_locus_loglik_dev(tphip_plan* p, const uint8_t* d_states, int64_t ncand
     }
     if (!p->lik_ok) return fail(TPHIP_ERR_INVALID, "tree too large for the locus-likelihood kernel's LDS tables");
     const size_t lds = p->lik_lds;
-    L.stage_states = p->lik_stage;
     const int nsplit = lik_nsplit(p, ncand, kLikBlock);
     L.nsplit = nsplit;
     if (nsplit > 1) {
-        int rc = grow_part(p, (size_t)ncand * nsplit * sizeof(double));
+        int rc = grow((void**)&p->d_part, p->part_bytes, (size_t)ncand * nsplit * sizeof(double));
         if (rc) return rc;
         L.out = p->d_part;
     }
@@ -983,28 +967,21 @@ int tphip_locus_gradient_dev(tphip_plan* p, const uint8_t* d_states, int64_t nca
         const size_t per_cand = (36 + nn * (16 + kGrad2EF)) * sizeof(double);
         int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)4 << 30) / per_cand));
         chunk = std::min<int64_t>(chunk, ncand);
-        const size_t need_ws = (size_t)chunk * per_cand;
-        if (need_ws > p->grad2_ws_bytes) {
-            if (p->d_grad2_ws) { HIP_TRY(hipFree(p->d_grad2_ws)); p->d_grad2_ws = nullptr; p->grad2_ws_bytes = 0; }
-            HIP_TRY(hipMalloc((void**)&p->d_grad2_ws, need_ws));
-            p->grad2_ws_bytes = need_ws;
-        }
+        int rc = grow((void**)&p->d_grad2_ws, p->grad2_ws_bytes, (size_t)chunk * per_cand);
+        if (rc) return rc;
         double* d_eig = p->d_grad2_ws;
         double* d_pmat = d_eig + (size_t)chunk * 36;
         double* d_ef = d_pmat + (size_t)chunk * nn * 16;
         const size_t items_all = (size_t)ncand * nsplit;
         if (nsplit > 1) {
-            int rc = grow_part(p, items_all * (8 + (d_dlogt ? nn : 0) + (d_d2logt ? nn : 0)) * sizeof(double));
+            rc = grow((void**)&p->d_part, p->part_bytes, items_all * (8 + (d_dlogt ? nn : 0) + (d_d2logt ? nn : 0)) * sizeof(double));
             if (rc) return rc;
         }
         const int64_t grid_max = (int64_t)p->num_cus * p->grad2_blocks_per_cu;
         const size_t need_tape = (size_t)std::min<int64_t>((int64_t)std::min<int64_t>(chunk, ncand) * nsplit, grid_max) *
                                  (size_t)std::max(1, p->grad2_ntape) * 4 * kGrad2Block * sizeof(double);
-        if (need_tape > p->tape_bytes) {
-            if (p->d_tape) { HIP_TRY(hipFree(p->d_tape)); p->d_tape = nullptr; p->tape_bytes = 0; }
-            HIP_TRY(hipMalloc((void**)&p->d_tape, need_tape));
-            p->tape_bytes = need_tape;
-        }
+        rc = grow((void**)&p->d_tape, p->tape_bytes, need_tape);
+        if (rc) return rc;
         if (!p->d_grad2_params) HIP_TRY(hipMalloc((void**)&p->d_grad2_params, sizeof(Grad2Params) * 64));
         double* o_lnl = nsplit > 1 ? p->d_part : d_lnl;
         double* o_sum = nsplit > 1 ? p->d_part + items_all : d_sum_dlogt;
@@ -1062,7 +1039,7 @@ int tphip_locus_gradient_dev(tphip_plan* p, const uint8_t* d_states, int64_t nca
     L.nsplit = nsplit;
     const size_t nn = (size_t)p->nnodes, items = (size_t)ncand * nsplit;
     if (nsplit > 1) {   // partials: lnl[items], sum[items], dexch[items][6], dlogt[items][nn]
-        int rc = grow_part(p, items * (8 + (d_dlogt ? nn : 0) + (d_d2logt ? nn : 0)) * sizeof(double));
+        int rc = grow((void**)&p->d_part, p->part_bytes, items * (8 + (d_dlogt ? nn : 0) + (d_d2logt ? nn : 0)) * sizeof(double));
         if (rc) return rc;
         L.out = p->d_part;
         G.out_sum_dlogt = p->d_part + items;
@@ -1072,21 +1049,14 @@ int tphip_locus_gradient_dev(tphip_plan* p, const uint8_t* d_states, int64_t nca
     }
     const int64_t grid = std::min<int64_t>((int64_t)items, (int64_t)p->num_cus * blocks_per_cu);
     const size_t need = (size_t)grid * (size_t)std::max(1, p->prog.ntape + p->prog.stack_depth) * 4 * kGradBlock * sizeof(double);
-    if (need > p->tape_bytes) {
-        if (p->d_tape) { HIP_TRY(hipFree(p->d_tape)); p->d_tape = nullptr; p->tape_bytes = 0; }
-        HIP_TRY(hipMalloc((void**)&p->d_tape, need));
-        p->tape_bytes = need;
-    }
+    int rc = grow((void**)&p->d_tape, p->tape_bytes, need);
+    if (rc) return rc;
     G.tape = p->d_tape;
     // eigen-systems of the candidates by one thread each (locus_value_launch.hip) instead of thread 0 of every work item
     G.cand_eig = nullptr;
     {
-        const size_t need_eig = (size_t)ncand * 36 * sizeof(double);
-        if (need_eig > p->grad_eig_bytes) {
-            if (p->d_grad_eig) { HIP_TRY(hipFree(p->d_grad_eig)); p->d_grad_eig = nullptr; p->grad_eig_bytes = 0; }
-            HIP_TRY(hipMalloc((void**)&p->d_grad_eig, need_eig));
-            p->grad_eig_bytes = need_eig;
-        }
+        rc = grow((void**)&p->d_grad_eig, p->grad_eig_bytes, (size_t)ncand * 36 * sizeof(double));
+        if (rc) return rc;
         HIP_TRY(launch_lik_eigen_kernel((hipStream_t)stream, p->d_models.p, d_cand_locus, d_cand_exch, ncand, p->d_grad_eig));
         G.cand_eig = p->d_grad_eig;
     }
@@ -1134,14 +1104,6 @@ struct HostBuffers {
     hipStream_t copy_stream = nullptr, run_stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_site = nullptr;
 };
-
-int grow(void** ptr, size_t& have, size_t need) {
-    if (need <= have && *ptr) return TPHIP_OK;
-    if (*ptr) { HIP_TRY(hipFree(*ptr)); *ptr = nullptr; have = 0; }
-    HIP_TRY(hipMalloc(ptr, need ? need : 1));
-    have = need;
-    return TPHIP_OK;
-}
 
 bool is_pinned(const void* q) {   // host memory the DMA engines can reach directly
     hipPointerAttribute_t a;

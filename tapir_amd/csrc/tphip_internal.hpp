@@ -96,11 +96,10 @@ struct tphip_plan {
     DevBuf<LocusModel> d_models;
     DevBuf<int64_t> d_offsets, d_locus_pichunk_offsets;
     DevBuf<int32_t> d_tip_taxon, d_op_node;
-    // launch configuration of the locus likelihood / gradient kernels, fixed at plan creation (tuning knobs are read
-    // from the environment once, there): LDS bytes, whether the gradient kernel stages its state masks, resident
-    // gradient blocks per CU, forced slice count (0 = automatic)
+    // launch configuration of the locus likelihood / gradient kernels, fixed at plan creation: LDS bytes, whether the
+    // gradient kernel stages its state masks, resident gradient blocks per CU
     size_t lik_lds = 0, grad_lds = 0;
-    int32_t lik_stage = 0, grad_stage = 0, grad_blocks_per_cu = 1, lik_nsplit_forced = 0, grad_slots = 4;
+    int32_t grad_stage = 0, grad_blocks_per_cu = 1, grad_slots = 4;
     bool lik_ok = false, grad_ok = false;
     int32_t ncat = 0;
     DevBuf<double> d_cat;     // [2 * ncat] category rates, then log weights
@@ -154,7 +153,6 @@ struct tphip_plan {
     int32_t site_lds_depth = 0;   // parked partials kept in LDS by site_rate_kernel (< stack depth: SPILL variant)
     size_t ws_spill = 0;
     double site_first_fraction = 0.0;   // share of the work the first round of shares takes (0 = equal shares)
-    bool force_byte_path = false;       // TPHIP_FORCE_BYTE_PATH=1 at plan creation: run the NW = 0 kernel on any tree (tests)
     // profiling
     bool profile = false;
     std::vector<hipEvent_t> ev;  // 4 events per slot: site start/stop, pi start/stop

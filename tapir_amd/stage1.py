@@ -690,7 +690,7 @@ def model_averaged_exchangeabilities(plan, states, pi, parent, blen, engine_fit=
     optimiser over the same likelihood kernels instead: the round-1/2 implementation, kept as a second opinion for
     tests and A/B timing (tools/stage1_timing.py host)."""
     if engine_fit is None:
-        engine_fit = hasattr(plan, "stage1_fit") and not kw and os.environ.get("TPHIP_STAGE1_HOST") is None
+        engine_fit = hasattr(plan, "stage1_fit") and not kw
     if engine_fit:
         out = plan.stage1_fit(states)
         st = out.pop("stats")

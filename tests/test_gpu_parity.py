@@ -546,14 +546,13 @@ def test_all_gap_and_ragged_loci(oracle):
     plan.close()
 
 
-@pytest.mark.parametrize("persistent,byte_path,mixed", [("0", "0", "0"), ("0", "0", "1"), ("1", "0", "0"), ("0", "1", "0"), ("1", "1", "0")])
-def test_site_rate_kernel_variants(oracle, monkeypatch, persistent, byte_path, mixed):
+@pytest.mark.parametrize("persistent,mixed", [("0", "0"), ("0", "1"), ("1", "0")])
+def test_site_rate_kernel_variants(oracle, monkeypatch, persistent, mixed):
     """Every scheduling mode (persistent equal shares / locus-aligned slices / waves carrying several loci) and both
-    tip-state paths (register-resident packed words / one-op-ahead byte loads) against the oracle on the same bytes."""
+    tip-state paths (packed words in registers: 20 taxa / streamed words: 130 taxa) against the oracle on the same bytes."""
     engine = _engine()
     from tapir_amd import synth
     monkeypatch.setenv("TPHIP_SITE_PERSISTENT", persistent)
-    monkeypatch.setenv("TPHIP_FORCE_BYTE_PATH", byte_path)
     monkeypatch.setenv("TPHIP_SITE_MIXED", mixed)
     for ntaxa, nloci, ncols, seed in [(20, 9, 777, 31), (130, 3, 300, 32)]:
         d = synth.simulate(nloci, ncols, ntaxa, seed)
@@ -1316,7 +1315,7 @@ def test_locus_kernels_on_a_400_taxon_tree(oracle):
 
 
 def test_site_rates_on_300_and_500_taxon_trees(oracle):
-    """Beyond 256 tips the site-rate kernel leaves its register-resident packed states for the byte path (NW = 0) and
+    """Trees far beyond 64 tips: the site-rate kernel streams its packed tip states (38 and 63 words per column) and
     partials need rescaling more than once per column; both against the oracle."""
     engine = _engine()
     from tapir_amd import synth
