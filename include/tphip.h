@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define TPHIP_VERSION 110 /* 0.1.1: tphip_plan_desc.struct_size, TPHIP_START_AUTO, tphip_stage1_fit, tphip_plan_set_models */
+#define TPHIP_VERSION 110 /* 0.1.1: tphip_plan_desc.struct_size, TPHIP_START_AUTO, tphip_stage1_fit, tphip_plan_set_models;
+                              tphip_plan_desc.model (TPHIP_MODEL_F81), a trailing field that struct_size makes safe to add */
 
 enum {
     TPHIP_OK = 0,
@@ -73,6 +74,13 @@ enum {
 
 /* tphip_plan_desc.pattern_dedup */
 enum { TPHIP_DEDUP_AUTO = 0, TPHIP_DEDUP_OFF = 1, TPHIP_DEDUP_ON = 2 };
+
+/* tphip_plan_desc.model: the per-site substitution model */
+enum {
+    TPHIP_MODEL_GTR = 0, /* default: the locus' GTR model, pi and exch per locus (HyPhy's, bf:978-1001)                      */
+    TPHIP_MODEL_F81 = 1  /* all six exchangeabilities 1 (exch must be NULL), pi per locus: Q = Pi - I, P(t) = e^-t I +
+                            (1 - e^-t) Pi in closed form (a cheaper site-rate kernel).  Jukes-Cantor = F81 with pi = 1/4 each */
+};
 
 int tphip_version(void);
 const char *tphip_last_error(void);
@@ -134,6 +142,11 @@ typedef struct tphip_plan_desc {
      * alignments with random gaps hardly repeat a column), in batches of at least 2^20 columns (smaller ones are
      * latency-bound: nothing to gain); ON / OFF force it.  The outputs are bit-identical either way. */
     int32_t pattern_dedup;     /* TPHIP_DEDUP_*                                                        */
+    /* The substitution model of the per-site loop.  TPHIP_MODEL_GTR (0, the zero default of callers built against an older
+     * header) is the locus' GTR model.  TPHIP_MODEL_F81: exch must be NULL (the library uses 1s), pi is required; rate is
+     * kappa * s with kappa = 1 - sum pi_i^2.  tphip_plan_set_models then takes pi only, tphip_stage1_fit[_dev] is refused
+     * (a fixed model has nothing to fit) and tphip_plan_get_models returns the eigen-system of Pi - I (lam = -1, -1, -1). */
+    int32_t model;             /* TPHIP_MODEL_*                                                        */
 } tphip_plan_desc;
 
 int tphip_plan_create(const tphip_plan_desc *desc, tphip_plan **out);

@@ -5,7 +5,7 @@ Same positionals, same required/optional flags and defaults, same output directo
 (Tree_<factor>_<depth>.newick, <alignment>.rates JSON per locus, phylogenetic-informativeness.sqlite).
 `--hyphy` and `--template` are accepted for compatibility and ignored (there is no subprocess);
 `--multiprocessing` parallelises the host side only (NEXUS parsing, .rates files).  New, opt-in flags only: --device, --exchangeabilities / --subs-model,
---integral-mode, --full-precision-rates, --gamma-categories / --gamma-alpha.
+--integral-mode, --full-precision-rates, --gamma-categories / --gamma-alpha, --site-model.
 
 Several GPUs: launch it with `python -m torch.distributed.run --nproc-per-node G bin/tapir_compute.py ...` (one process
 per GPU).  The files are dealt round-robin over the ranks (what `Pool.map(worker, params)` did over cores,
@@ -15,7 +15,7 @@ without GPUs) and rank 0 writes the sqlite file in the original file order.
 
 Stage 1 of the HyPhy script (203-model fit + model averaging of the GTR exchangeabilities,
 models_and_rates.bf:405-897) runs on the GPU too (tapir_amd/stage1.py) unless the exchangeabilities are given
-with --exchangeabilities / --subs-model.
+with --exchangeabilities / --subs-model, or a fixed model is chosen with --site-model jc / f81.
 """
 import argparse
 import os
@@ -79,7 +79,18 @@ def get_args(argv=None):
                           "ones the optimum uphill of HyPhy's start; costs about one likelihood evaluation per site")
     new.add_argument('--full-precision-rates', action='store_true',
                      help="do not round site rates to 4 decimals before PI (the reference rounds through its JSON file)")
-    return parser.parse_args(argv)
+    new.add_argument('--site-model', choices=['locus', 'jc', 'f81'], default='locus',
+                     help="locus = the locus' GTR model (stage-1 estimates, or --exchangeabilities / --subs-model); "
+                          "jc = Jukes-Cantor (equal base frequencies, exchangeabilities 1; PhyDesign's other model); "
+                          "f81 = exchangeabilities 1 with the locus' empirical base frequencies.  jc and f81 skip stage 1 "
+                          "and run a closed-form site-rate kernel")
+    args = parser.parse_args(argv)
+    if args.site_model != 'locus':
+        for flag, given in (('--exchangeabilities', args.exchangeabilities is not None), ('--subs-model', bool(args.subs_model)),
+                            ('--site-rates', args.site_rates)):
+            if given:
+                parser.error("--site-model {0} fixes the model: it cannot be combined with {1}".format(args.site_model, flag))
+    return args
 
 
 def _six_floats(string):
@@ -255,7 +266,8 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
                                                cat_rates=cat_rates, cat_weights=cat_weights,
                                                start_rule=1 if args.reference_start else 0,
                                                during_write=store if world == 1 else None,
-                                               table_sink=_TableSink() if world == 1 else None)
+                                               table_sink=_TableSink() if world == 1 else None,
+                                               site_model=args.site_model)
             tables = out["final_tables"]
             stored = bool(out.get("during_write_done"))
             sqlite_seconds = LAST_TIMINGS.get("sqlite")

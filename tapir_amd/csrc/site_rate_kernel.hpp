@@ -29,6 +29,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 #include "tphip.h"
 #include "fast_exp.hpp"
 #include "gtr_model.hpp"
@@ -233,6 +234,140 @@ __device__ __forceinline__ void branch_apply(const ModelRegs& R, const double* _
     }
 }
 
+// ---- F81 / Jukes-Cantor (TPHIP_MODEL_F81): exchangeabilities of 1 ----------------------------------------------------
+// Under HyPhy's parametrisation (gtr_model.hpp) r = 1 gives Q = Pi - I (Pi_ij = pi_j), whose transition matrix has a closed
+// form: P(tau) = e I + (1 - e) Pi with e = exp(-tau), tau = t s.  A message through a branch is (P L)_i = e L_i + (1 - e) pi.L:
+// one exponential and no eigenvector products.  With x = -tau the u-derivatives of e are e' = x e and e'' = x (1 + x) e.
+// A tip's message needs its 0/1 indicator vector (a model-independent [16][4] table in LDS) and pi.tip (a [16] table per
+// locus, pointed to by wdot).  Everything else -- rescaling, the LDS stack, the optimiser -- is shared with the GTR kernel.
+struct F81Regs {
+    double pi[4];
+    double c4;             // as in ModelRegs
+    const double* wdot;    // LDS: pi . tip(mask) of the lane's locus, [16]
+};
+
+// Non-persistent / persistent modes: pi and kappa go through the model slots of mtab (as load_model), mtab[0..15] holds wdot.
+__device__ __forceinline__ F81Regs load_model_f81(const LocusModel* __restrict__ M, double* mtab, int lane) {
+    if (lane >= 27 && lane < 32) mtab[lane] = reinterpret_cast<const double*>(M)[lane];  // pi[4] kappa
+    __syncthreads();
+    F81Regs R;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) R.pi[i] = mtab[27 + i];
+    R.wdot = mtab;
+    R.c4 = 4.1666666666666664e-02;
+    asm volatile("" : "+v"(R.c4));
+    return R;
+}
+
+__device__ __forceinline__ void load_model_lane(const LocusModel* __restrict__ M, F81Regs& R) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) R.pi[i] = M->pi[i];
+}
+
+// itab[mask][i] = 1 if base i is in the mask (model-independent); wdot[mask] = sum_{j in mask} pi_j
+__device__ __forceinline__ void build_tip_table_f81(const LocusModel* __restrict__ M, double* itab, double* wdot, int lane) {
+    const int mask = lane >> 2, k = lane & 3;
+    itab[lane] = ((mask >> k) & 1) ? 1.0 : 0.0;
+    if (lane < 16) {
+        double w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w += ((lane >> j) & 1) ? M->pi[j] : 0.0;
+        wdot[lane] = w;
+    }
+}
+
+// acc = fma(a, acc, c) in place
+__device__ __forceinline__ void fma_self(double& acc, double a, double c) {
+    asm("v_fma_f64 %0, %1, %0, %2" : "+v"(acc) : "v"(a), "v"(c));
+}
+
+// e, e' and e'' of a branch of length ts
+__device__ __forceinline__ void f81_decay(const F81Regs& R, const double* __restrict__ etab, double ts, double& e, double& e1,
+                                          double& e2) {
+    const double x = -ts;
+    e = kUseExpTable ? exp_nonpos_tab(x, etab, R.c4) : exp_nonpos(x);
+    e1 = x * e;
+    e2 = fma(x, e1, e1);
+}
+
+// a tip's message: m_i = e ind_i + (1 - e) w, w = pi.tip (w[4]); d/du: e' (ind_i - w), d2/du2: e'' (ind_i - w)
+__device__ __forceinline__ void tip_message(const F81Regs& R, const double* __restrict__ etab, const double* w, double ts, Partial& m) {
+    double e, e1, e2;
+    f81_decay(R, etab, ts, e, e1, e2);
+    const double c0 = fma(-e, w[4], w[4]), c1 = -e1 * w[4], c2 = -e2 * w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        m.v[i] = fma(w[i], e, c0);
+        m.d1[i] = fma(w[i], e1, c1);
+        m.d2[i] = fma(w[i], e2, c2);
+    }
+}
+
+__device__ __forceinline__ void f81_tip_over(const double* w, double e, double e1, double e2, Partial& acc) {
+    const double c0 = fma(-e, w[4], w[4]), c1 = -e1 * w[4], c2 = -e2 * w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        fma_over(acc.v[i], w[i], e, c0);
+        fma_over(acc.d1[i], w[i], e1, c1);
+        fma_over(acc.d2[i], w[i], e2, c2);
+    }
+}
+
+__device__ __forceinline__ void tip_message_over(const F81Regs& R, const double* __restrict__ etab, const double* w, double ts,
+                                                 Partial& acc) {
+    double e, e1, e2;
+    f81_decay(R, etab, ts, e, e1, e2);
+    f81_tip_over(w, e, e1, e2, acc);
+}
+
+__device__ __forceinline__ void cherry_over(const F81Regs& R, const double* __restrict__ etab, const double* w1, const double* w2,
+                                            double ts, Partial& acc) {
+    double e, e1, e2;
+    f81_decay(R, etab, ts, e, e1, e2);
+    f81_tip_over(w1, e, e1, e2, acc);
+    Partial m;
+    const double c0 = fma(-e, w2[4], w2[4]), c1 = -e1 * w2[4], c2 = -e2 * w2[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        m.v[i] = fma(w2[i], e, c0);
+        m.d1[i] = fma(w2[i], e1, c1);
+        m.d2[i] = fma(w2[i], e2, c2);
+    }
+    partial_mul(acc, m);
+}
+
+// p <- e p + (1 - e) (pi.p) with derivatives (product rule, z_k = pi . p^(k)):
+//   v_i  = e v_i + (1 - e) z0
+//   d1_i = e d1_i + e' v_i + (1 - e) z1 - e' z0
+//   d2_i = e d2_i + 2 e' d1_i + e'' v_i + (1 - e) z2 - 2 e' z1 - e'' z0
+// in place, highest derivative first (each reads the lower components' old values)
+__device__ __forceinline__ void branch_apply(const F81Regs& R, const double* __restrict__ etab, double ts, Partial& p) {
+    const double z0 = fma(R.pi[3], p.v[3], fma(R.pi[2], p.v[2], fma(R.pi[1], p.v[1], R.pi[0] * p.v[0])));
+    const double z1 = fma(R.pi[3], p.d1[3], fma(R.pi[2], p.d1[2], fma(R.pi[1], p.d1[1], R.pi[0] * p.d1[0])));
+    const double z2 = fma(R.pi[3], p.d2[3], fma(R.pi[2], p.d2[2], fma(R.pi[1], p.d2[1], R.pi[0] * p.d2[0])));
+    double e, e1, e2;
+    f81_decay(R, etab, ts, e, e1, e2);
+    const double ome = 1.0 - e, twice = e1 + e1;
+    const double c0 = ome * z0;
+    const double c1 = fma(ome, z1, -e1 * z0);
+    const double c2 = fma(ome, z2, fma(-twice, z1, -e2 * z0));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        fma_self(p.d2[i], e, c2);
+        fma_into(p.d2[i], twice, p.d1[i]);
+        fma_into(p.d2[i], e2, p.v[i]);
+        fma_self(p.d1[i], e, c1);
+        fma_into(p.d1[i], e1, p.v[i]);
+        fma_self(p.v[i], e, c0);
+    }
+}
+
+// The tip operand of the F81 message functions: the indicator vector and pi.tip.
+__device__ __forceinline__ void tip_operand(const F81Regs& R, const double* __restrict__ itab, unsigned mask, double (&wv)[5]) {
+    const double* w = itab + mask * 4;
+    wv[0] = w[0]; wv[1] = w[1]; wv[2] = w[2]; wv[3] = w[3]; wv[4] = R.wdot[mask];
+}
+
 // Rescaling for deep trees / hundreds of taxa: when the largest component of the running partial is below 2^-256
 // the partial (value and both derivatives) is multiplied by 2^-e and e is added to `scale` -- exact, and everything
 // downstream is linear in it.  The test runs before every TIP_MUL and BRANCH; it is 4 integer instructions and a
@@ -325,11 +460,13 @@ __device__ __forceinline__ uint32_t pick_word(const uint32_t (&pk)[NW > 0 ? NW :
 //        instead of LDS.  On a deep tree (256 taxa: 4 parked partials = 24 KB of LDS per wave) the LDS stack, not the
 //        registers, caps the CU at 6 waves; the deepest slot is used by ~1 push in 9, so parking it in global memory
 //        costs little and lets 8 waves (2 per SIMD) stay resident.
-template <int NW, bool SPILL = false>
-__device__ __forceinline__ void evaluate_column(const SiteParams& P, const ModelRegs& R, const double* __restrict__ wtab,
+// Regs: ModelRegs (GTR, wtab = the locus' U^-1 tip table) or F81Regs (wtab = the indicator table; pi.tip through R.wdot).
+template <int NW, bool SPILL = false, class Regs = ModelRegs>
+__device__ __forceinline__ void evaluate_column(const SiteParams& P, const Regs& R, const double* __restrict__ wtab,
                                                 const double* __restrict__ etab, double* __restrict__ stack, int64_t col,
                                                 const uint32_t (&pk)[NW > 0 ? NW : 1], double s, double& f,
                                                 double& g, double& h) {
+    constexpr bool kF81 = std::is_same<Regs, F81Regs>::value;
     Partial acc;
     int scale = 0;
     int sp = 0;
@@ -443,29 +580,50 @@ __device__ __forceinline__ void evaluate_column(const SiteParams& P, const Model
                 mask = st & 15u;
                 mask = mask ? mask : 15u;
             }
-            const double* w = wtab + mask * 4;
-            if (code == OP_TIP_SET) {
-                // A subtree starts here (program start, or right after a PUSH: tree_program.hpp emits no other
-                // TIP_SET): the tip's message IS the new accumulator -- no product with an identity, no rescaling.
-                if (op.code & OP_PUSH_BEFORE) park();
-                const double wv[4] = {w[0], w[1], w[2], w[3]};
-                tip_message_over(R, etab, wv, op.t * s, acc);
+            if constexpr (kF81) {
+                double wv[5];
+                tip_operand(R, wtab, mask, wv);
+                if (code == OP_TIP_SET) {
+                    if (op.code & OP_PUSH_BEFORE) park();
+                    tip_message_over(R, etab, wv, op.t * s, acc);
+                } else {
+                    Partial m;
+                    rescale_if_needed(acc, scale);
+                    tip_message(R, etab, wv, op.t * s, m);
+                    partial_mul(acc, m);
+                }
             } else {
-                Partial m;
-                rescale_if_needed(acc, scale);
-                const double wv[4] = {w[0], w[1], w[2], w[3]};
-                tip_message(R, etab, wv, op.t * s, m);
-                partial_mul(acc, m);
+                const double* w = wtab + mask * 4;
+                if (code == OP_TIP_SET) {
+                    // A subtree starts here (program start, or right after a PUSH: tree_program.hpp emits no other
+                    // TIP_SET): the tip's message IS the new accumulator -- no product with an identity, no rescaling.
+                    if (op.code & OP_PUSH_BEFORE) park();
+                    const double wv[4] = {w[0], w[1], w[2], w[3]};
+                    tip_message_over(R, etab, wv, op.t * s, acc);
+                } else {
+                    Partial m;
+                    rescale_if_needed(acc, scale);
+                    const double wv[4] = {w[0], w[1], w[2], w[3]};
+                    tip_message(R, etab, wv, op.t * s, m);
+                    partial_mul(acc, m);
+                }
             }
         } else if (NW != 0 && code == OP_CHERRY) {   // fused stream (packed paths only)
             if (op.code & OP_PUSH_BEFORE) park();
             const unsigned mask1 = next_mask();
             const unsigned mask2 = next_mask();
-            const double* w1 = wtab + mask1 * 4;
-            const double* w2 = wtab + mask2 * 4;
-            const double wa[4] = {w1[0], w1[1], w1[2], w1[3]};
-            const double wb[4] = {w2[0], w2[1], w2[2], w2[3]};
-            cherry_over(R, etab, wa, wb, op.t * s, acc);
+            if constexpr (kF81) {
+                double wa[5], wb[5];
+                tip_operand(R, wtab, mask1, wa);
+                tip_operand(R, wtab, mask2, wb);
+                cherry_over(R, etab, wa, wb, op.t * s, acc);
+            } else {
+                const double* w1 = wtab + mask1 * 4;
+                const double* w2 = wtab + mask2 * 4;
+                const double wa[4] = {w1[0], w1[1], w1[2], w1[3]};
+                const double wb[4] = {w2[0], w2[1], w2[2], w2[3]};
+                cherry_over(R, etab, wa, wb, op.t * s, acc);
+            }
         } else if (code == OP_POP_MUL) {
             pop_mul();
         } else {  // OP_PUSH
@@ -495,8 +653,8 @@ __device__ __forceinline__ void evaluate_column(const SiteParams& P, const Model
 // L(s) = sum_k w_k L(s rho_k) -- the "+G" of GTR+G as an opt-in extension the reference's script does not have
 // (SURVEY F2).  With f_k, g_k, h_k the category's log-likelihood and u-derivatives and p_k its posterior weight:
 // f = logsumexp(log w_k + f_k), g = sum p_k g_k, h = sum p_k (h_k + g_k^2) - g^2 (running maximum, one pass).
-template <int NW, bool SPILL = false>
-__device__ __forceinline__ void evaluate_site(const SiteParams& P, const ModelRegs& R, const double* __restrict__ wtab,
+template <int NW, bool SPILL = false, class Regs = ModelRegs>
+__device__ __forceinline__ void evaluate_site(const SiteParams& P, const Regs& R, const double* __restrict__ wtab,
                                               const double* __restrict__ etab, double* __restrict__ stack, int64_t col,
                                               const uint32_t (&pk)[NW > 0 ? NW : 1], double s, double& f, double& g,
                                               double& h) {
@@ -504,7 +662,7 @@ __device__ __forceinline__ void evaluate_site(const SiteParams& P, const ModelRe
     double top = -INFINITY, z = 0.0, a = 0.0, b = 0.0;
     for (int k = 0; k < K; ++k) {
         double fk, gk, hk;
-        evaluate_column<NW, SPILL>(P, R, wtab, etab, stack, col, pk, P.ncat > 1 ? s * P.cat[k] : s, fk, gk, hk);
+        evaluate_column<NW, SPILL, Regs>(P, R, wtab, etab, stack, col, pk, P.ncat > 1 ? s * P.cat[k] : s, fk, gk, hk);
         if (P.ncat <= 1) { f = fk; g = gk; h = hk; return; }
         fk += P.cat[K + k];
         if (fk > top) {
@@ -587,8 +745,13 @@ __global__ __launch_bounds__(1024) void scan_counts_kernel(const int32_t* __rest
 // slowest locus (27 rounds of evaluations against 18 on average on C2) with one wave per SIMD and a drain per locus; here
 // shares are equal column counts whatever the loci, lanes are refilled across locus boundaries and a wave drains once.
 // Results are bit-identical: a column's arithmetic does not depend on the lane or wave that carries it.
-template <int NW, bool SPILL = false, bool MIXED = false>
+//
+// MODEL = TPHIP_MODEL_F81: the closed-form messages above.  LDS: wtab is the indicator table [16][4]; pi.tip of the locus sits in
+// mtab[0..15] (the model slots 27..31 keep pi and kappa), MIXED: at wtab + 64 + 16 k for the group's k-th locus.
+template <int NW, bool SPILL = false, bool MIXED = false, int MODEL = TPHIP_MODEL_GTR>
 __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_kernel(SiteParams P) {
+    constexpr bool F81 = MODEL == TPHIP_MODEL_F81;
+    using Regs = typename std::conditional<F81, F81Regs, ModelRegs>::type;
     extern __shared__ double lds[];
     double* wtab = lds;          // [16 masks][4]          MIXED: [kMixedLoci][16][4]
     double* mtab = lds + 64;     // [32] the locus' model  MIXED: unused, the segment table sits behind etab
@@ -695,7 +858,7 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
     int64_t gpos = g0;
     int64_t locus = lo_l;
     while (gpos < g1) {
-        ModelRegs R;
+        Regs R;
         const double* wt = wtab;     // the lane's tip table
         double kappa = 0.0;
         int begin, end;
@@ -710,8 +873,13 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
             gpos = seg_end_g;
             __syncthreads();  // the previous segment's readers of wtab / mtab are done
             const LocusModel* __restrict__ M = P.models + locus;
-            build_tip_table(M, wtab, lane);
-            R = load_model(M, mtab, lane);
+            if constexpr (F81) {
+                build_tip_table_f81(M, wtab, mtab, lane);
+                R = load_model_f81(M, mtab, lane);
+            } else {
+                build_tip_table(M, wtab, lane);
+                R = load_model(M, mtab, lane);
+            }
             kappa = mtab[31];
             work = ((!P.persistent && P.work_cols2) ? (const int32_t*)P.work_cols2 : P.work_cols) + P.locus_offsets[locus];
             ++locus;
@@ -728,7 +896,8 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
                         seg_end[K] = (int)(se - gb);
                         seg_locus[K] = (int)locus;
                     }
-                    build_tip_table(P.models + locus, wtab + 64 * K, lane);
+                    if constexpr (F81) build_tip_table_f81(P.models + locus, wtab, wtab + 64 + 16 * K, lane);
+                    else build_tip_table(P.models + locus, wtab + 64 * K, lane);
                     ++K;
                     gpos = se;
                 }
@@ -807,7 +976,8 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
             if constexpr (MIXED) {
                 myk = c0 >> 28;
                 load_model_lane(P.models + seg_locus[myk], R);
-                wt = wtab + 64 * myk;
+                if constexpr (F81) R.wdot = wtab + 64 + 16 * myk;
+                else wt = wtab + 64 * myk;
             }
         }
         // the next 64 candidates of the work list, one per lane, requested an evaluation before a refill needs them: the
@@ -827,7 +997,7 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
         int it = 0;
         while (true) {
             double f, g, h;
-            evaluate_site<NW, SPILL>(P, R, wt, etab, stack, col, pk, exp(u), f, g, h);
+            evaluate_site<NW, SPILL, Regs>(P, R, wt, etab, stack, col, pk, exp(u), f, g, h);
 #ifdef TPHIP_SITE_TRACE_ROUNDS
             ++rounds;
 #endif
@@ -982,7 +1152,8 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
                         if (nk != myk) {   // the lane moves on to another locus: its model and tip table
                             myk = nk;
                             load_model_lane(P.models + seg_locus[nk], R);
-                            wt = wtab + 64 * nk;
+                            if constexpr (F81) R.wdot = wtab + 64 + 16 * nk;
+                            else wt = wtab + 64 * nk;
                         }
                     }
 #pragma unroll
@@ -1019,7 +1190,8 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
 // Diagnostic: evaluate f = log L, g = df/du, h = d2f/du2 at a caller-chosen u for EVERY column (no
 // classification, no optimiser).  Tests use it to check the derivative propagation by finite differences.
 // Uses the same chunk tables with chunk_cols columns per workgroup, 64 at a time.
-__global__ __launch_bounds__(kSiteBlock) void eval_columns_kernel(EvalParams E) {
+template <int MODEL>
+__device__ __forceinline__ void eval_columns_body(const EvalParams& E) {
     extern __shared__ double lds[];
     double* wtab = lds;
     double* mtab = lds + 64;
@@ -1031,8 +1203,15 @@ __global__ __launch_bounds__(kSiteBlock) void eval_columns_kernel(EvalParams E) 
     const int locus = P.chunk_locus[chunk];
     const LocusModel* __restrict__ M = P.models + locus;
     const int lane = threadIdx.x;
-    build_tip_table(M, wtab, lane);
-    const ModelRegs R = load_model(M, mtab, lane);
+    using Regs = typename std::conditional<MODEL == TPHIP_MODEL_F81, F81Regs, ModelRegs>::type;
+    Regs R;
+    if constexpr (MODEL == TPHIP_MODEL_F81) {
+        build_tip_table_f81(M, wtab, mtab, lane);
+        R = load_model_f81(M, mtab, lane);
+    } else {
+        build_tip_table(M, wtab, lane);
+        R = load_model(M, mtab, lane);
+    }
     const int64_t lo = P.locus_offsets[locus], hi = P.locus_offsets[locus + 1];
     const int64_t S = hi - lo;
     int64_t ns = (S + P.chunk_cols / 2) / P.chunk_cols;  // = workgroups launched for this locus
@@ -1046,9 +1225,14 @@ __global__ __launch_bounds__(kSiteBlock) void eval_columns_kernel(EvalParams E) 
         const int64_t col = active ? want : first;
         double f, g, h;
         const uint32_t none[1] = {0};
-        evaluate_site<0>(P, R, wtab, etab, stack, col, none, exp(E.u[col]), f, g, h);
+        evaluate_site<0, false, Regs>(P, R, wtab, etab, stack, col, none, exp(E.u[col]), f, g, h);
         if (active) { E.f[col] = f; E.g[col] = g; E.h[col] = h; }
     }
 }
+
+// The GTR and the F81 diagnostic: overloads on the parameter type, so that both keep the kernel's name.
+struct EvalParamsF81 : EvalParams {};
+__global__ __launch_bounds__(kSiteBlock) void eval_columns_kernel(EvalParams E) { eval_columns_body<TPHIP_MODEL_GTR>(E); }
+__global__ __launch_bounds__(kSiteBlock) void eval_columns_kernel(EvalParamsF81 E) { eval_columns_body<TPHIP_MODEL_F81>(E); }
 
 }  // namespace tphip

@@ -14,32 +14,52 @@
 
 namespace tphip {
 
-hipError_t launch_site_rate_kernel(int variant, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S) {
+// MODEL is a template parameter of every variant: F81 plans run the closed-form instantiations (distinct kernel names).
+template <int MODEL>
+static hipError_t launch_site_rate_model(int variant, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S) {
     const dim3 block(kSiteBlock);
-    if (variant == 2) site_rate_kernel<2><<<grid, block, lds_bytes, st>>>(S);
-    else if (variant == 8) site_rate_kernel<8><<<grid, block, lds_bytes, st>>>(S);
-    else if (variant == kMixedVariant + 2) site_rate_kernel<2, false, true><<<grid, block, lds_bytes, st>>>(S);
-    else if (variant == kMixedVariant + 8) site_rate_kernel<8, false, true><<<grid, block, lds_bytes, st>>>(S);
-    else if (variant == kStreamWords) site_rate_kernel<kStreamWords><<<grid, block, lds_bytes, st>>>(S);
-    else if (variant == kStreamWordsSpill) site_rate_kernel<kStreamWords, true><<<grid, block, lds_bytes, st>>>(S);
+    if (variant == 2) site_rate_kernel<2, false, false, MODEL><<<grid, block, lds_bytes, st>>>(S);
+    else if (variant == 8) site_rate_kernel<8, false, false, MODEL><<<grid, block, lds_bytes, st>>>(S);
+    else if (variant == kMixedVariant + 2) site_rate_kernel<2, false, true, MODEL><<<grid, block, lds_bytes, st>>>(S);
+    else if (variant == kMixedVariant + 8) site_rate_kernel<8, false, true, MODEL><<<grid, block, lds_bytes, st>>>(S);
+    else if (variant == kStreamWords) site_rate_kernel<kStreamWords, false, false, MODEL><<<grid, block, lds_bytes, st>>>(S);
+    else if (variant == kStreamWordsSpill) site_rate_kernel<kStreamWords, true, false, MODEL><<<grid, block, lds_bytes, st>>>(S);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
-hipError_t site_rate_kernel_occupancy(int variant, size_t lds_bytes, int* blocks_per_cu) {
-    if (variant == 2) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<2>, kSiteBlock, lds_bytes);
-    if (variant == 8) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<8>, kSiteBlock, lds_bytes);
-    if (variant == kMixedVariant + 2) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<2, false, true>, kSiteBlock, lds_bytes);
-    if (variant == kMixedVariant + 8) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<8, false, true>, kSiteBlock, lds_bytes);
+template <int MODEL>
+static hipError_t site_rate_occupancy_model(int variant, size_t lds_bytes, int* blocks_per_cu) {
+    if (variant == 2) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<2, false, false, MODEL>, kSiteBlock, lds_bytes);
+    if (variant == 8) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<8, false, false, MODEL>, kSiteBlock, lds_bytes);
+    if (variant == kMixedVariant + 2) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<2, false, true, MODEL>, kSiteBlock, lds_bytes);
+    if (variant == kMixedVariant + 8) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<8, false, true, MODEL>, kSiteBlock, lds_bytes);
     if (variant == kStreamWords)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<kStreamWords>, kSiteBlock, lds_bytes);
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<kStreamWords, false, false, MODEL>, kSiteBlock, lds_bytes);
     if (variant == kStreamWordsSpill)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<kStreamWords, true>, kSiteBlock, lds_bytes);
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, site_rate_kernel<kStreamWords, true, false, MODEL>, kSiteBlock, lds_bytes);
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_eval_columns_kernel(dim3 grid, size_t lds_bytes, hipStream_t st, const EvalParams& E) {
-    eval_columns_kernel<<<grid, dim3(kSiteBlock), lds_bytes, st>>>(E);
+hipError_t launch_site_rate_kernel(int variant, int model, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S) {
+    if (model == TPHIP_MODEL_F81) return launch_site_rate_model<TPHIP_MODEL_F81>(variant, grid, lds_bytes, st, S);
+    if (model == TPHIP_MODEL_GTR) return launch_site_rate_model<TPHIP_MODEL_GTR>(variant, grid, lds_bytes, st, S);
+    return hipErrorInvalidValue;
+}
+
+hipError_t site_rate_kernel_occupancy(int variant, int model, size_t lds_bytes, int* blocks_per_cu) {
+    if (model == TPHIP_MODEL_F81) return site_rate_occupancy_model<TPHIP_MODEL_F81>(variant, lds_bytes, blocks_per_cu);
+    if (model == TPHIP_MODEL_GTR) return site_rate_occupancy_model<TPHIP_MODEL_GTR>(variant, lds_bytes, blocks_per_cu);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_eval_columns_kernel(int model, dim3 grid, size_t lds_bytes, hipStream_t st, const EvalParams& E) {
+    if (model == TPHIP_MODEL_F81) {
+        EvalParamsF81 F;
+        static_cast<EvalParams&>(F) = E;
+        eval_columns_kernel<<<grid, dim3(kSiteBlock), lds_bytes, st>>>(F);
+    } else if (model == TPHIP_MODEL_GTR) eval_columns_kernel<<<grid, dim3(kSiteBlock), lds_bytes, st>>>(E);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -101,10 +101,11 @@ struct EvalParams {
 
 // ---- launchers defined in site_rate_launch.hip ------------------------------------------------------------------
 // variant: 2 / 8 = packed words in registers, kStreamWords = streamed words (> 64 tips),
-// kStreamWordsSpill = the same with the deepest parked partials in global scratch (S.spill, S.lds_depth)
-hipError_t launch_site_rate_kernel(int variant, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S);
-hipError_t site_rate_kernel_occupancy(int variant, size_t lds_bytes, int* blocks_per_cu);
-hipError_t launch_eval_columns_kernel(dim3 grid, size_t lds_bytes, hipStream_t st, const EvalParams& E);
+// kStreamWordsSpill = the same with the deepest parked partials in global scratch (S.spill, S.lds_depth);
+// model: TPHIP_MODEL_GTR (eigen-system messages) or TPHIP_MODEL_F81 (closed-form messages)
+hipError_t launch_site_rate_kernel(int variant, int model, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S);
+hipError_t site_rate_kernel_occupancy(int variant, int model, size_t lds_bytes, int* blocks_per_cu);
+hipError_t launch_eval_columns_kernel(int model, dim3 grid, size_t lds_bytes, hipStream_t st, const EvalParams& E);
 hipError_t launch_scan_counts_kernel(hipStream_t st, const int32_t* count, int64_t nloci, int32_t chunk_cols, int64_t* prefix,
                                      int64_t* slice_prefix);
 

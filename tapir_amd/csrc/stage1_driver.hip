@@ -157,6 +157,8 @@ extern "C" int tphip_stage1_fit_dev(tphip_plan* p, const uint8_t* d_states, cons
                                     double* pi_out, double* weights_out, double* lnl_out, double* model_exch_out, double* grm_blen_out,
                                     int32_t* grm_iters_out, int32_t* sub_iters_out, int64_t* stats_out, void* stream) {
     if (!p || !d_states || !exch_out) return fail(TPHIP_ERR_INVALID, "null argument");
+    if (p->model != TPHIP_MODEL_GTR)
+        return fail(TPHIP_ERR_INVALID, "tphip_stage1_fit: the plan's model is TPHIP_MODEL_F81 (fixed exchangeabilities, nothing to fit)");
     tphip_stage1_opts opt;
     memset(&opt, 0, sizeof(opt));
     if (opts_in) {
@@ -571,6 +573,8 @@ extern "C" int tphip_stage1_fit(tphip_plan* p, const uint8_t* states, void** d_s
                                 double* exch_out, double* pi_out, double* weights_out, double* lnl_out, double* model_exch_out,
                                 double* grm_blen_out, int32_t* grm_iters_out, int32_t* sub_iters_out, int64_t* stats_out) {
     if (!p || !states) return fail(TPHIP_ERR_INVALID, "null argument");
+    if (p->model != TPHIP_MODEL_GTR)
+        return fail(TPHIP_ERR_INVALID, "tphip_stage1_fit: the plan's model is TPHIP_MODEL_F81 (fixed exchangeabilities, nothing to fit)");
     HIP_TRY(hipSetDevice(p->device));
     tphip_stage1_opts opt;
     memset(&opt, 0, sizeof(opt));

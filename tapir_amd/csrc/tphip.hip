@@ -87,7 +87,8 @@ static tphip_saved_desc* save_desc(const tphip_plan_desc* d) {
     s->leaf.assign(d->leaf_taxon, d->leaf_taxon + d->nnodes);
     s->offsets.assign(d->locus_offsets, d->locus_offsets + d->nloci + 1);
     s->pi.assign(d->pi, d->pi + 4 * d->nloci);
-    s->exch.assign(d->exch, d->exch + 6 * d->nloci);
+    if (d->model == TPHIP_MODEL_F81) s->exch.assign(6 * (size_t)d->nloci, 1.0);   // what the library uses; d.exch stays NULL
+    else s->exch.assign(d->exch, d->exch + 6 * d->nloci);
     if (d->n_t) s->times.assign(d->times, d->times + d->n_t);
     if (d->n_i) s->intervals.assign(d->intervals, d->intervals + 2 * (size_t)d->n_i);
     if (d->ncat > 0 && d->cat_rate && d->cat_weight) {
@@ -96,7 +97,8 @@ static tphip_saved_desc* save_desc(const tphip_plan_desc* d) {
     }
     // the saved descriptor points at its own copies (the caller's arrays may be gone after tphip_plan_create returns)
     s->d.parent = s->parent.data(); s->d.branch_len = s->blen.data(); s->d.leaf_taxon = s->leaf.data();
-    s->d.locus_offsets = s->offsets.data(); s->d.pi = s->pi.data(); s->d.exch = s->exch.data();
+    s->d.locus_offsets = s->offsets.data(); s->d.pi = s->pi.data();
+    s->d.exch = d->model == TPHIP_MODEL_F81 ? nullptr : s->exch.data();
     s->d.times = s->times.empty() ? nullptr : s->times.data();
     s->d.intervals = s->intervals.empty() ? nullptr : s->intervals.data();
     s->d.cat_rate = s->cat_rate.empty() ? nullptr : s->cat_rate.data();
@@ -112,6 +114,28 @@ static void free_parts(tphip_plan* p) {
     p->parts.clear();
     delete p->saved;
     p->saved = nullptr;
+}
+
+// F81 models (TPHIP_MODEL_F81) on the host, exact: Q = Pi - I has the eigenvalue 0 (right vector 1, left vector pi) and -1
+// three times, whose right eigenvectors are the vectors orthogonal to pi -- here e_k - pi_k 1 (k = 1..3), with the rows
+// e_k - e_0 of the inverse.  Needs no floor (nothing divides by pi); pi normalised to sum 1, kappa = 1 - sum pi_i^2 (=
+// 2 sum_{i<j} pi_i pi_j, what gtr_setup_kernel computes for exchangeabilities of 1).  The site-rate kernels read pi and
+// kappa only; classify_kernel's start rule reads -Q_xx = 1 - pi_x from the eigen-form.
+static void f81_models(const double* pi_in, int64_t L, std::vector<LocusModel>* out) {
+    out->assign((size_t)L, LocusModel{});
+    for (int64_t l = 0; l < L; ++l) {
+        LocusModel& m = (*out)[(size_t)l];
+        double pi[4], sum = 0.0, sq = 0.0;
+        for (int i = 0; i < 4; ++i) sum += pi_in[4 * l + i];
+        for (int i = 0; i < 4; ++i) { pi[i] = pi_in[4 * l + i] / sum; sq += pi[i] * pi[i]; }
+        for (int k = 1; k < 4; ++k) {
+            m.lam[k - 1] = -1.0;
+            for (int i = 0; i < 4; ++i) m.U[i * 3 + k - 1] = (i == k ? 1.0 : 0.0) - pi[k];
+            for (int j = 0; j < 4; ++j) m.Ui[(k - 1) * 4 + j] = (j == k ? 1.0 : 0.0) - (j == 0 ? 1.0 : 0.0);
+        }
+        for (int i = 0; i < 4; ++i) m.pi[i] = pi[i];
+        m.kappa = 1.0 - sq;
+    }
 }
 
 // The plans of the locus groups of a host-pointer run (created on first use): boundaries at the loci nearest to equal
@@ -137,7 +161,8 @@ static int make_parts(tphip_plan* p) {
         for (int64_t& o : off) o -= S.offsets[l0];
         tphip_plan_desc d = S.d;
         d.parent = S.parent.data(); d.branch_len = S.blen.data(); d.leaf_taxon = S.leaf.data();
-        d.nloci = l1 - l0; d.locus_offsets = off.data(); d.pi = S.pi.data() + 4 * l0; d.exch = S.exch.data() + 6 * l0;
+        d.nloci = l1 - l0; d.locus_offsets = off.data(); d.pi = S.pi.data() + 4 * l0;
+        d.exch = S.d.model == TPHIP_MODEL_F81 ? nullptr : S.exch.data() + 6 * l0;
         d.times = S.times.empty() ? nullptr : S.times.data();
         d.intervals = S.intervals.empty() ? nullptr : S.intervals.data();
         d.cat_rate = S.cat_rate.empty() ? nullptr : S.cat_rate.data();
@@ -173,7 +198,11 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     if (d->device < 0 || d->device >= ndev) return fail(TPHIP_ERR_INVALID, "device ordinal out of range");
     if (d->ntaxa < 2) return fail(TPHIP_ERR_INVALID, "ntaxa must be >= 2");
     if (!d->parent || !d->branch_len || !d->leaf_taxon) return fail(TPHIP_ERR_INVALID, "null tree arrays");
-    if (d->nloci < 1 || !d->locus_offsets || !d->pi || !d->exch) return fail(TPHIP_ERR_INVALID, "null or empty locus arrays");
+    if (d->model != TPHIP_MODEL_GTR && d->model != TPHIP_MODEL_F81) return fail(TPHIP_ERR_INVALID, "unknown model");
+    if (d->model == TPHIP_MODEL_F81 && d->exch)
+        return fail(TPHIP_ERR_INVALID, "exch must be NULL with TPHIP_MODEL_F81 (its exchangeabilities are all 1)");
+    if (d->nloci < 1 || !d->locus_offsets || !d->pi || (d->model == TPHIP_MODEL_GTR && !d->exch))
+        return fail(TPHIP_ERR_INVALID, "null or empty locus arrays");
     if (d->T < 0 || d->n_t < 0 || d->n_i < 0) return fail(TPHIP_ERR_INVALID, "negative schedule size");
     if ((d->n_t && !d->times) || (d->n_i && !d->intervals)) return fail(TPHIP_ERR_INVALID, "null times/intervals");
     if (!(d->correction > 0.0)) return fail(TPHIP_ERR_INVALID, "correction must be > 0");
@@ -199,7 +228,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             npos += d->pi[l * 4 + k] > 0.0;
         }
         if (npos < 2) return fail(TPHIP_ERR_INVALID, "locus " + std::to_string(l) + " has fewer than two bases with a positive frequency");
-        for (int k = 0; k < 6; ++k)
+        for (int k = 0; k < 6 && d->exch; ++k)
             if (!(d->exch[l * 6 + k] >= 0.0)) return fail(TPHIP_ERR_INVALID, "exchangeabilities must be >= 0");
     }
     const int64_t ncols = d->locus_offsets[d->nloci];
@@ -228,6 +257,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
                         ? ((d->ntaxa >= kFirstStepMinTaxa || d->ncat > 1) ? TPHIP_START_PARSIMONY : TPHIP_START_REFERENCE)
                         : d->start_rule;
     p->dedup_mode = d->pattern_dedup;
+    p->model = d->model;
     p->ncat = cat.empty() ? 0 : d->ncat;
     std::string terr = build_tree_program(d->ntaxa, d->nnodes, d->parent, d->branch_len, d->leaf_taxon, &p->prog);
     if (!terr.empty()) { delete p; return fail(TPHIP_ERR_INVALID, "tree: " + terr); }
@@ -268,7 +298,10 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     hipError_t e = hipSetDevice(d->device);
     std::vector<int32_t> times(d->times, d->times + d->n_t), iv(d->intervals, d->intervals + 2 * (size_t)d->n_i);
     DevBuf<double> d_pi, d_exch;
-    std::vector<double> hpi(d->pi, d->pi + 4 * (size_t)d->nloci), hex(d->exch, d->exch + 6 * (size_t)d->nloci);
+    std::vector<double> hpi(d->pi, d->pi + 4 * (size_t)d->nloci), hex(6 * (size_t)d->nloci, 1.0);
+    if (d->exch) hex.assign(d->exch, d->exch + 6 * (size_t)d->nloci);
+    std::vector<LocusModel> f81;
+    if (d->model == TPHIP_MODEL_F81) f81_models(d->pi, d->nloci, &f81);
     // A base that never occurs in a (short) locus has empirical frequency 0 (HarvestFrequencies, bf:968); HyPhy takes
     // that as it is: the state is unreachable and no tip carries it, so the likelihood is that of the three-state
     // model.  The eigen-form used here needs D^-1/2, so the zero is floored at kPiFloor before the renormalisation in
@@ -341,9 +374,11 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     if (e == hipSuccess) e = p->d_models.alloc((size_t)d->nloci);
     if (e == hipSuccess) e = p->d_evals.alloc(8);   // [0] evaluations; [1..5] diagnostics of a TPHIP_SITE_TRACE_ROUNDS build
     if (e == hipSuccess) e = hipMemset(p->d_evals.p, 0, 8 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = d_pi.upload(hpi);
-    if (e == hipSuccess) e = d_exch.upload(hex);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && d->model == TPHIP_MODEL_F81)
+        e = hipMemcpy(p->d_models.p, f81.data(), sizeof(LocusModel) * f81.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && d->model == TPHIP_MODEL_GTR) e = d_pi.upload(hpi);
+    if (e == hipSuccess && d->model == TPHIP_MODEL_GTR) e = d_exch.upload(hex);
+    if (e == hipSuccess && d->model == TPHIP_MODEL_GTR) {
         const int bs = 128;
         gtr_setup_kernel<<<dim3((unsigned)((d->nloci + bs - 1) / bs)), dim3(bs)>>>(d_pi.p, d_exch.p, d->nloci, p->d_models.p);
         e = hipGetLastError();
@@ -360,7 +395,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
         hipDeviceProp_t prop;
         int per_cu = 0;
         if (hipGetDeviceProperties(&prop, d->device) != hipSuccess) { tphip_plan_destroy(p); return fail(TPHIP_ERR_HIP, "hipGetDeviceProperties failed"); }
-        const hipError_t oe = site_rate_kernel_occupancy(p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : kStreamWords, lds_bytes, &per_cu);
+        const hipError_t oe = site_rate_kernel_occupancy(p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : kStreamWords, p->model, lds_bytes, &per_cu);
         if (oe != hipSuccess || per_cu < 1) per_cu = 1;
         p->site_waves = per_cu * prop.multiProcessorCount;
         p->num_cus = prop.multiProcessorCount;
@@ -377,7 +412,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
                 const int depth = std::max(1, std::min(keep, p->prog.stack_depth - 1));
                 const size_t lds2 = (kSiteLdsHeader + (size_t)depth * 12 * kSiteBlock) * sizeof(double);
                 int per2 = 0;
-                if (site_rate_kernel_occupancy(kStreamWordsSpill, lds2, &per2) == hipSuccess && per2 > per_cu &&
+                if (site_rate_kernel_occupancy(kStreamWordsSpill, p->model, lds2, &per2) == hipSuccess && per2 > per_cu &&
                     ncols / ((int64_t)per2 * prop.multiProcessorCount) >= 1000) {   // persistent mode will be chosen below
                     p->site_lds_depth = depth;
                     p->site_waves = per2 * prop.multiProcessorCount;
@@ -455,7 +490,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             const size_t lds3 = (kMixedLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
             const int64_t simds = 4 * (int64_t)prop.multiProcessorCount;
             const double est_rounds = (double)ncols * (p->start_rule == TPHIP_START_REFERENCE ? 2.2 : 1.4) / (double)(kSiteBlock * simds);
-            if (lds3 > 160 * 1024 || site_rate_kernel_occupancy(kMixedVariant + (p->nwords <= 2 ? 2 : 8), lds3, &per3) != hipSuccess || per3 < 1) p->site_mixed = 0;
+            if (lds3 > 160 * 1024 || site_rate_kernel_occupancy(kMixedVariant + (p->nwords <= 2 ? 2 : 8), p->model, lds3, &per3) != hipSuccess || per3 < 1) p->site_mixed = 0;
             // a batch that wants two waves per SIMD on a tree whose tables leave room for six per CU (64 taxa: 23.3 KB of LDS
             // per wave) stays with the slices: 1900 loci x 1000 x 64, 3.36 ms in slices, 4.10 with 1024 mixed waves
             else if (est_rounds >= 28.0 && per3 < 8 && !getenv("TPHIP_SITE_MIXED")) p->site_mixed = 0;
@@ -706,9 +741,9 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
         if (mixed) {   // equal shares: first_round = grid
             const size_t lds_mixed = (kMixedLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
             S.first_fraction = 1.0;
-            HIP_TRY(launch_site_rate_kernel(kMixedVariant + variant, grid, lds_mixed, st, S));
+            HIP_TRY(launch_site_rate_kernel(kMixedVariant + variant, p->model, grid, lds_mixed, st, S));
         } else
-        HIP_TRY(launch_site_rate_kernel(variant, grid, spill ? lds : lds_full, st, S));
+        HIP_TRY(launch_site_rate_kernel(variant, p->model, grid, spill ? lds : lds_full, st, S));
     }
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 1], st));
     if (dedup) dedup_scatter_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
@@ -1333,7 +1368,7 @@ int tphip_eval_columns_dev(tphip_plan* p, const uint8_t* d_s, const double* d_u,
     E.S.flag = nullptr; E.S.eval_counter = nullptr; E.S.spill = nullptr; E.S.lds_depth = p->prog.stack_depth;
     E.u = d_u; E.f = d_f; E.g = d_g; E.h = d_h;
     const size_t lds = (kSiteLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
-    if (p->n_site_chunks > 0) HIP_TRY(launch_eval_columns_kernel(dim3((unsigned)p->n_site_chunks), lds, (hipStream_t)stream, E));
+    if (p->n_site_chunks > 0) HIP_TRY(launch_eval_columns_kernel(p->model, dim3((unsigned)p->n_site_chunks), lds, (hipStream_t)stream, E));
     return TPHIP_OK;
 }
 
@@ -1393,6 +1428,8 @@ int tphip_plan_set_models(tphip_plan* p, const double* pi, const double* exch) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
     if (!p->saved) return fail(TPHIP_ERR_INVALID, "plan has no saved descriptor");
     const size_t L = (size_t)p->nloci;
+    if (p->model == TPHIP_MODEL_F81 && exch)
+        return fail(TPHIP_ERR_INVALID, "exch must be NULL on a TPHIP_MODEL_F81 plan (its exchangeabilities are all 1)");
     if (pi) {
         for (size_t l = 0; l < L; ++l) {
             int npos = 0;
@@ -1411,8 +1448,16 @@ int tphip_plan_set_models(tphip_plan* p, const double* pi, const double* exch) {
         p->saved->exch.assign(exch, exch + 6 * L);
     }
     p->saved->d.pi = p->saved->pi.data();
-    p->saved->d.exch = p->saved->exch.data();
     HIP_TRY(hipSetDevice(p->device));
+    if (p->model == TPHIP_MODEL_F81) {
+        std::vector<LocusModel> f81;
+        f81_models(p->saved->pi.data(), p->nloci, &f81);
+        HIP_TRY(hipMemcpy(p->d_models.p, f81.data(), sizeof(LocusModel) * L, hipMemcpyHostToDevice));
+        for (tphip_plan* q : p->parts) (void)tphip_plan_destroy(q);
+        p->parts.clear();
+        return TPHIP_OK;
+    }
+    p->saved->d.exch = p->saved->exch.data();
     std::vector<double> hpi(p->saved->pi);
     for (size_t l = 0; l < L; ++l) {   // same floor as at plan creation
         double sum = 0;

@@ -143,6 +143,7 @@ struct tphip_plan {
     size_t ws_work_cols2 = 0, ws_work_cols = 0, ws_work_count = 0, ws_work_prefix = 0, ws_slice_prefix = 0, ws_partial = 0, ws_packed = 0, ws_total = 0;
     size_t ws_hash = 0, ws_dup_of = 0, ws_tab_key = 0, ws_tab_val = 0, ws_dedup_on = 0;   // site-pattern de-duplication
     int32_t dedup_mode = 0;   // DEDUP_AUTO (pattern_kernels.hpp)
+    int32_t model = 0;        // TPHIP_MODEL_GTR / TPHIP_MODEL_F81 (tphip_plan_desc.model): the site-rate kernels' messages
     int32_t num_cus = 256;
     int32_t site_waves = 0;  // persistent grid of site_rate_kernel = resident waves on the device
     int32_t site_persistent = 1;

@@ -18,6 +18,8 @@ FLAG_OK, FLAG_FLAT, FLAG_SATURATED, FLAG_ZERO, FLAG_MAXIT = 0, 1, 2, 3, 4
 START_AUTO, START_REFERENCE, START_PARSIMONY = 0, 1, 2
 DEDUP_AUTO, DEDUP_OFF, DEDUP_ON = 0, 1, 2
 INTEG_QUADPACK, INTEG_CLOSED = 0, 1
+MODEL_GTR, MODEL_F81 = 0, 1
+MODELS = {"gtr": MODEL_GTR, "f81": MODEL_F81}
 
 _vp = ctypes.c_void_p
 _i32, _i64, _f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -33,7 +35,7 @@ class PlanDesc(ctypes.Structure):
                 ("T", _i32), ("times", _vp), ("n_t", _i32), ("intervals", _vp), ("n_i", _i32),
                 ("integ_mode", _i32), ("correction", _f64), ("threshold", _i32), ("round_decimals", _i32),
                 ("ncat", _i32), ("cat_rate", _vp), ("cat_weight", _vp), ("start_rule", _i32),
-                ("pattern_dedup", _i32)]
+                ("pattern_dedup", _i32), ("model", _i32)]
 
 
 class Stage1Opts(ctypes.Structure):
@@ -200,17 +202,22 @@ class Plan:
     parent / branch_len / leaf_taxon: post-order tree arrays (branch lengths already / correction).
     locus_offsets: [L+1] column ranges; pi [L,4]; exch [L,6] in AC,AG,AT,CG,CT,GT order.
     times / intervals: the --times and --intervals of bin/tapir_compute.py:27-33.
+    model: "gtr" (the locus' GTR model) or "f81" (exchangeabilities of 1, closed-form site-rate kernel; exch must be
+    None -- Jukes-Cantor is "f81" with pi = 1/4 each).
     """
 
     def __init__(self, ntaxa, parent, branch_len, leaf_taxon, locus_offsets, pi, exch, T, times, intervals,
                  correction=1.0, threshold=3, round_decimals=4, integ_mode=INTEG_QUADPACK, device=0, cat_rates=None,
-                 cat_weights=None, start_rule=START_AUTO, pattern_dedup=DEDUP_AUTO):
+                 cat_weights=None, start_rule=START_AUTO, pattern_dedup=DEDUP_AUTO, model="gtr"):
+        if model not in MODELS:
+            raise TphipError("model must be one of %s" % sorted(MODELS))
         lib = load()
         self._lib = lib
         self._h = _vp()
         self._keep = dict(parent=_np(parent, np.int32), blen=_np(branch_len, np.float64),
                           leaf=_np(leaf_taxon, np.int32), off=_np(locus_offsets, np.int64),
-                          pi=_np(pi, np.float64).reshape(-1), exch=_np(exch, np.float64).reshape(-1),
+                          pi=_np(pi, np.float64).reshape(-1),
+                          exch=None if exch is None else _np(exch, np.float64).reshape(-1),
                           times=_np(times, np.int32).reshape(-1), iv=_np(intervals, np.int32).reshape(-1))
         k = self._keep
         ncat = 0 if cat_rates is None else len(cat_rates)
@@ -220,22 +227,23 @@ class Plan:
             if k["cw"].size != ncat:
                 raise TphipError("cat_weights must match cat_rates")
         self.nloci = len(k["off"]) - 1
-        if k["pi"].size != 4 * self.nloci or k["exch"].size != 6 * self.nloci:
+        if k["pi"].size != 4 * self.nloci or (k["exch"] is not None and k["exch"].size != 6 * self.nloci):
             raise TphipError("pi must be [L,4] and exch [L,6] for L = len(locus_offsets) - 1")
         if k["iv"].size % 2:
             raise TphipError("intervals must be (start, stop) pairs")
         d = PlanDesc(struct_size=ctypes.sizeof(PlanDesc), device=device, ntaxa=ntaxa, nnodes=len(k["parent"]), parent=k["parent"].ctypes.data,
                      branch_len=k["blen"].ctypes.data, leaf_taxon=k["leaf"].ctypes.data, nloci=self.nloci,
-                     locus_offsets=k["off"].ctypes.data, pi=k["pi"].ctypes.data, exch=k["exch"].ctypes.data, T=int(T),
+                     locus_offsets=k["off"].ctypes.data, pi=k["pi"].ctypes.data, exch=_ptr(k["exch"]), T=int(T),
                      times=k["times"].ctypes.data, n_t=k["times"].size, intervals=k["iv"].ctypes.data,
                      n_i=k["iv"].size // 2, integ_mode=integ_mode, correction=float(correction),
                      threshold=int(threshold), round_decimals=int(round_decimals),
                      ncat=ncat if ncat > 1 else 0, cat_rate=k["cr"].ctypes.data if ncat > 1 else None,
                      cat_weight=k["cw"].ctypes.data if ncat > 1 else None, start_rule=int(start_rule),
-                     pattern_dedup=int(pattern_dedup))
+                     pattern_dedup=int(pattern_dedup), model=MODELS[model])
         _check(lib.tphip_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
         self.device = device
         self.ntaxa = ntaxa
+        self.model = model
         self.T, self.n_t, self.n_i = int(T), k["times"].size, k["iv"].size // 2
         self.ncols = lib.tphip_plan_ncols(self._h)
         self.width = lib.tphip_plan_table_width(self._h)
@@ -433,7 +441,8 @@ class Plan:
         return out
 
     def set_models(self, pi=None, exch=None):
-        """Replace the per-locus base frequencies [L, 4] and / or exchangeabilities [L, 6] of the plan (tphip_plan_set_models)."""
+        """Replace the per-locus base frequencies [L, 4] and / or exchangeabilities [L, 6] of the plan (tphip_plan_set_models;
+        an F81 plan takes pi only)."""
         a = None if pi is None else _np(pi, np.float64).reshape(-1)
         b = None if exch is None else _np(exch, np.float64).reshape(-1)
         if (a is not None and a.size != 4 * self.nloci) or (b is not None and b.size != 6 * self.nloci):

@@ -367,8 +367,17 @@ def _block_sizes():
     return STAGE1_BLOCK_LOCI, STREAM_BLOCK_LOCI
 
 
+def _fixed_model_pi(eng, site_model, states, offsets, device):
+    """[L, 4] base frequencies of a fixed site model: 1/4 each (jc) or the loci's empirical ones (f81, HarvestFrequencies)."""
+    L = len(offsets) - 1
+    if site_model == "jc":
+        return np.full((L, 4), 0.25)
+    return nexus.base_frequencies_from_histogram(eng.state_histogram(np.ascontiguousarray(states), offsets, device=device))
+
+
 def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                  pi, output_dir, device, integ_mode, round_decimals, extra, pool, progress, table_sink, timings, lap):
+                  pi, output_dir, device, integ_mode, round_decimals, extra, pool, progress, table_sink, timings, lap,
+                  site_model="locus"):
     """The whole pipeline block by block, host and device working at the same time.
 
     Block k of the loci: stage 1 (one tphip_stage1_fit call on the block's column range of the pinned batch array), its
@@ -376,7 +385,8 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
     and while the GPU does that for block k + 1, the pool's workers format block k's `.rates` files from a shared array and
     a second thread of this process inserts block k's PI rows into sqlite (`table_sink`).  At C4 scale the GPU needs ~8 s for
     the 50 000 loci and the host ~8 s for their 12 GB of text and 5.4 M rows: one after the other that is the sum, here close
-    to the larger.  Results are those of the unstreamed run (loci are independent; every array is filled at the same places)."""
+    to the larger.  Results are those of the unstreamed run (loci are independent; every array is filled at the same places).
+    A fixed site model (site_model jc / f81) has no stage 1: each block's plan carries the model from the start."""
     import tempfile
     import time
     L = len(alignments)
@@ -417,15 +427,24 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
             l1 = min(L, l0 + step)
             a, b = int(offsets[l0]), int(offsets[l1])
             cols = states[:, a:b]
-            blk_pi = np.full((l1 - l0, 4), 0.25) if pi is None else pi[l0:l1]
-            plan = eng.Plan(ntaxa, parent, blen, leaf, offsets[l0:l1 + 1] - a, blk_pi, np.ones((l1 - l0, 6)), T, times, intervals,
-                            correction=correction, threshold=threshold, round_decimals=round_decimals, integ_mode=integ_mode,
-                            device=device, **extra)
+            if site_model != "locus":
+                blk_pi = _fixed_model_pi(eng, site_model, cols, offsets[l0:l1 + 1] - a, device)
+                lap("base_frequencies")
+                plan = eng.Plan(ntaxa, parent, blen, leaf, offsets[l0:l1 + 1] - a, blk_pi, None, T, times, intervals,
+                                correction=correction, threshold=threshold, round_decimals=round_decimals, integ_mode=integ_mode,
+                                device=device, model="f81", **extra)
+                exch_all[l0:l1], pi_all[l0:l1] = 1.0, blk_pi
+            else:
+                blk_pi = np.full((l1 - l0, 4), 0.25) if pi is None else pi[l0:l1]
+                plan = eng.Plan(ntaxa, parent, blen, leaf, offsets[l0:l1 + 1] - a, blk_pi, np.ones((l1 - l0, 6)), T, times, intervals,
+                                correction=correction, threshold=threshold, round_decimals=round_decimals, integ_mode=integ_mode,
+                                device=device, **extra)
             try:
-                res = plan.stage1_fit(cols, details=False, compress_patterns=True, empirical_pi=pi is None)
-                lap("stage1_model_averaging")
-                exch_all[l0:l1], pi_all[l0:l1] = res["exch"], res["pi"]
-                plan.set_models(exch=res["exch"])
+                if site_model == "locus":
+                    res = plan.stage1_fit(cols, details=False, compress_patterns=True, empirical_pi=pi is None)
+                    lap("stage1_model_averaging")
+                    exch_all[l0:l1], pi_all[l0:l1] = res["exch"], res["pi"]
+                    plan.set_models(exch=res["exch"])
                 plan.run_fused_into(cols, out, col0=a, locus0=l0)
                 lap("site_rates_and_pi_incl_pcie")
             finally:
@@ -473,7 +492,7 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
 def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
                    exch, pi=None, subsets=None, output_dir=None, device=0, integ_mode=0, round_decimals=4,
                    engine_mod=None, progress=None, pool=None, cat_rates=None, cat_weights=None, start_rule=0,
-                   during_write=None, table_sink=None):
+                   during_write=None, table_sink=None, site_model="locus"):
     """Site rates + PI for a list of NEXUS alignments.  Returns a list of worker()-shaped tuples
     (alignment, rates, mean_rate, None, pi_net, pi_times, pi_epochs) in the order of `alignments`.
 
@@ -484,7 +503,15 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
 
     exch: [6] or [L,6] exchangeabilities AC,AG,AT,CG,CT,GT, or None = HyPhy's stage 1 (model-averaged estimates per
     locus, tapir_amd/stage1.py); pi: None (empirical, HarvestFrequencies) or [L,4].
+    site_model: "locus" (the GTR model above), or a fixed model without stage 1 that runs the engine's F81 kernel:
+    "jc" (Jukes-Cantor: pi = 1/4, exchangeabilities 1) or "f81" (the loci's empirical pi, exchangeabilities 1); exch and pi
+    must then be None.
     pool: a HostPool created before the process touched the GPU (parallel parsing and .rates writing), or None."""
+    if site_model not in ("locus", "jc", "f81"):
+        raise PipelineError("unknown site model %r" % (site_model,))
+    fixed = site_model != "locus"
+    if fixed and (exch is not None or pi is not None):
+        raise PipelineError("site model %s fixes the exchangeabilities and base frequencies" % site_model)
     eng = engine_mod
     if eng is None:
         from . import engine as eng
@@ -506,14 +533,24 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
     if start_rule:   # every column starts at siteRate = 1 as in HyPhy (bf:1050) instead of at its parsimony rate
         extra["start_rule"] = int(start_rule)
     need_subset = any(os.path.basename(a) in subsets for a in alignments)
-    if (exch is None and pool is not None and hasattr(pool, "write_rates_async") and output_dir is not None and not need_subset and
+    if ((exch is None or fixed) and pool is not None and hasattr(pool, "write_rates_async") and output_dir is not None and not need_subset and
             L > _block_sizes()[1] and hasattr(eng, "Plan") and hasattr(eng.Plan, "run_fused_into") and
             _shared_dir(32 * max(int(offsets[-1]), 1)) is not None and os.environ.get("TPHIP_NO_STREAM") is None):
         if pi is not None:
             pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
         return _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction,
                              threshold, pi, output_dir, device, integ_mode, round_decimals, extra, pool, progress, table_sink,
-                             timings, lap)
+                             timings, lap, site_model=site_model)
+    if fixed:
+        pi = _fixed_model_pi(eng, site_model, states, offsets, device)
+        lap("base_frequencies")
+        out = _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
+                        round_decimals, integ_mode, device, extra, pi, None, need_subset, pinned, model="f81")
+        lap("site_rates_and_pi_incl_pcie")
+        exch = np.ones((L, 6))
+        return _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction,
+                       threshold, round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool,
+                       progress, during_write, timings, lap)
     if pi is None and exch is not None:
         hist = eng.state_histogram(states, offsets, device=device)
         pi = nexus.base_frequencies_from_histogram(hist)
@@ -526,17 +563,33 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
     exch = np.asarray(exch, dtype=np.float64)
     if exch.ndim == 1:
         exch = np.tile(exch, (L, 1))
+    out = _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
+                    round_decimals, integ_mode, device, extra, pi, exch, need_subset, pinned)
+    lap("site_rates_and_pi_incl_pcie")
+    return _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
+                   round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool, progress, during_write,
+                   timings, lap)
+
+
+def _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold, round_decimals,
+              integ_mode, device, extra, pi, exch, need_subset, pinned, **model):
+    """One plan over the whole batch: per-site rates, and the PI tables unless a subset needs its own."""
     plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, times, intervals,
                     correction=correction, threshold=threshold, round_decimals=round_decimals,
-                    integ_mode=integ_mode, device=device, **extra)
+                    integ_mode=integ_mode, device=device, **extra, **model)
     try:
         if need_subset:
-            out = plan.site_rates(states)
-        else:
-            out = plan.run_fused(states, pinned=True) if pinned else plan.run_fused(states)
+            return plan.site_rates(states)
+        return plan.run_fused(states, pinned=True) if pinned else plan.run_fused(states)
     finally:
         plan.close()
-    lap("site_rates_and_pi_incl_pcie")
+
+
+def _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
+            round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool, progress, during_write,
+            timings, lap):
+    """Rounding, culling, the `.rates` files and the worker()-shaped tuples of run_alignments."""
+    L = len(alignments)
     # what tapir would have after parse_site_rates + cull (bin/tapir_compute.py:100-102)
     rate4 = compute.round_like_hyphy(out["rate"], round_decimals) if round_decimals >= 0 else out["rate"]
     corrected = rate4 / correction

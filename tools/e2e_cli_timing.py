@@ -2,6 +2,7 @@
 # breakdown the pipeline records.
 # usage: python tools/e2e_cli_timing.py LOCI COLS TAXA [--model-averaging] [cli flags ...]
 #   --model-averaging: let the CLI estimate the exchangeabilities (HyPhy stage 1) instead of fixing them
+#   --site-model jc|f81: the fixed Jukes-Cantor / F81 model (no stage 1, no --exchangeabilities)
 # The alignments are generated (on the GPU when there is one) and written by a CHILD process, so that this process has
 # not touched the GPU when cli.main() forks its --multiprocessing pool.
 import os, sys, time, tempfile, shutil, subprocess
@@ -43,14 +44,15 @@ try:
     out = os.path.join(tmp, "out")
     os.mkdir(out)
     extra = [a for a in sys.argv[4:] if a != "--model-averaging"]
-    fixed = [] if "--model-averaging" in sys.argv[4:] else ["--exchangeabilities", "1,1.2,0.8,0.9,1.5,1"]
+    # --site-model jc / f81 fixes the model itself (and refuses --exchangeabilities)
+    fixed = [] if "--model-averaging" in sys.argv[4:] or "--site-model" in extra else ["--exchangeabilities", "1,1.2,0.8,0.9,1.5,1"]
     t0 = time.time()
     cli.main([os.path.join(tmp, "aln"), os.path.join(tmp, "tree.newick"), "--output", out, "--times", "10,30,50,90",
               "--intervals", "5-15,25-35,45-55,85-95"] + extra + fixed)
     dt = time.time() - t0
     nbytes = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(out) for f in fs)
     print("CLI end to end (%s): %.2f s for %d loci x %d columns x %d taxa = %.3g columns/s; %.2f GB written under %s"
-          % (" ".join(extra + (["fixed exchangeabilities"] if fixed else ["model averaging"])), dt, nloci, ncols, ntaxa,
+          % (" ".join(extra + (["fixed exchangeabilities"] if fixed else [] if "--site-model" in extra else ["model averaging"])), dt, nloci, ncols, ntaxa,
              nloci * ncols / dt, nbytes / 1e9, "/dev/shm" if shm_ok else tempfile.gettempdir()))
     print("stages (s): " + ", ".join("%s %.2f" % kv for kv in cli.LAST_TIMINGS.items()))
 finally:
