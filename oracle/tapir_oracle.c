@@ -91,24 +91,27 @@ void orc_net_pi(const double *rates, int64_t n, int32_t T, double *net_out) {
     }
 }
 
-/* closed form: F(t) = -(4rt+1)exp(-4rt);  integral = F(b)-F(a) = g(4ra)-g(4rb)... written with
- * g(x) = 1-(1+x)exp(-x) (series for small x) so that tiny rates keep their digits. */
-static double g_small(double x) {
-    if (x < 0.1) { /* g(x) = sum_{k>=2} (-1)^k (k-1) x^k / k!  =  x^2/2 - x^3/3 + x^4/8 - ... */
-        double term = x * x * 0.5, sum = 0.0; /* term = x^k / k! */
-        for (int k = 2; k < 40; ++k) {
-            double add = term * (double)(k - 1);
-            sum += (k & 1) ? -add : add;
-            if (add <= 1e-20 * fabs(sum)) break;
-            term = term * x / (double)(k + 1);
-        }
-        return sum;
-    }
-    return 1.0 - (1.0 + x) * exp(-x);
-}
+/* closed form: F(t) = -(4rt+1)exp(-4rt);  integral = F(b)-F(a) = exp(-xa) * (xa * m + g) with xa = 4ra, d = 4r(b-a),
+ * m = 1 - exp(-d), g = 1-(1+d)exp(-d) (series for small d, so that tiny rates keep their digits):
+ * a sum of two non-negative terms, where g(4rb) - g(4ra) cancelled catastrophically once 4ra was large. */
 double orc_integral_closed(double a, double b, double r) {
     if (isnan(r)) return NAN;
-    return g_small(4.0 * r * b) - g_small(4.0 * r * a);
+    double xa = 4.0 * r * a, d = 4.0 * r * (b - a), m = 0.0, g = 0.0;
+    if (d < 0.1) { /* m = d - d^2/2 + d^3/6 - ...,  g = d^2/2 - d^3/3 + d^4/8 - ... */
+        double term = d; /* d^k / k! */
+        for (int k = 1; k < 40; ++k) {
+            double add = term * (double)(k - 1);
+            m += (k & 1) ? term : -term;
+            g += (k & 1) ? -add : add;
+            if (k > 1 && add <= 1e-20 * fabs(g)) break;
+            term = term * d / (double)(k + 1);
+        }
+    } else {
+        double e = exp(-d);
+        m = 1.0 - e;
+        g = m - d * e;
+    }
+    return exp(-xa) * (xa * m + g);
 }
 
 /* ---- QUADPACK dqk21: 21-point Gauss-Kronrod rule --------------------------------------------- */

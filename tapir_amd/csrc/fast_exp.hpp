@@ -60,18 +60,22 @@ __device__ __constant__ const double kExp2Table[64] = {
     1.9152065613971474, 1.9360617934922943, 1.9571441241754002, 1.978456026387951};
 
 // Table-driven exp(x), x <= 0 (Tang 1989 with a 64-entry table): x = (64 n + j) ln2/64 + r, |r| <= ln2/128,
-// exp(x) = 2^n * T[j] * (1 + q(r)), q of degree 5 (truncation r^6/720 < 4e-17).  11 FP64 ops + one LDS read
-// instead of 19 FP64 ops; error <= 1.5 ulp.
+// exp(x) = 2^n * T[j] * (1 + q(r)), q of degree 5 (truncation r^6/720 < 4e-17).  12 FP64 ops (the clamp included) + one
+// LDS read instead of 19 FP64 ops; error <= 1.5 ulp for every x <= 0, -inf included (0 where exp(x) underflows).
 // c4: the polynomial's coefficient 1/24 held in a VGPR by the caller.  fma(r, 1/120, 1/24) has two constant operands and a
 // VOP3 instruction takes one from the scalar side, so the compiler re-materialised the other with a v_mov_b64 in front of
 // every exp (3 per tree op); a register the compiler cannot see through (empty asm, see site_rate_kernel) stays put.
 __device__ __forceinline__ double exp_nonpos_tab(double x, const double* __restrict__ etab, double c4 = 4.1666666666666664e-02) {
     const double INV = 92.33248261689366;           // 64 / ln2
-    const double L_HI = 0.01083042469326756;        // ln2/64, 32 significant bits: k*L_HI is exact for |k| < 2^20
+    const double L_HI = 0.01083042469326756;        // ln2/64, 32 significant bits: k*L_HI is exact for |k| < 2^20 (the clamp below)
     const double L_LO = 2.9815858269852933e-12;
     const double SHIFT = 6755399441055744.0;        // 1.5 * 2^52
-    // (no clamp at -708: 2^n is applied with ldexp, which underflows to 0 by itself, and the shift trick holds for
-    //  |x| < 2^24 / INV * 2^7 -- site rates stop at s = 1e4, so |x| = |lambda t s| stays below ~1e5)
+    // k is read from the low 32 bits of t, so it wraps once |k| >= 2^31 (x < -2^31 ln2/64 = -2.33e7): n = k >> 6 then
+    // turns positive and ldexp overflows to +inf.  Nothing bounds |x| = |lambda_k| t s there (a branch of 2330 units at
+    // s = 1e4 is enough), so x is clamped first.  exp(-1e4) underflows to 0 like every x below -745.2, so the clamp
+    // changes no result for x > -2.33e7 (one v_max_f64; a NaN x comes out as 0).  2^n is applied with ldexp, which
+    // underflows to 0 by itself: no clamp at -708 is needed.
+    x = fmax(x, -1.0e4);
     const double t = fma(x, INV, SHIFT);            // low 32 bits of t = k = 64 n + j
     const double kd = t - SHIFT;
     double r = fma(-kd, L_HI, x);
@@ -85,7 +89,8 @@ __device__ __forceinline__ double exp_nonpos_tab(double x, const double* __restr
     q = q * r;                                      // q = exp(r) - 1
     const double p = fma(T, q, T);                  // in [0.99, 2.0)
     // 2^n through v_ldexp_f64 (shift + ldexp) rather than integer arithmetic on the exponent field (shift, mask,
-    // add): same bits (n >= -1022 after the clamp), one instruction fewer per exp, C3 site rates -1 % (A/B on one box)
+    // add): same bits where the result is normal, a correctly rounded subnormal or 0 below, one instruction fewer per exp,
+    // C3 site rates -1 % (A/B on one box)
     return ldexp(p, k >> 6);
 }
 

@@ -438,22 +438,29 @@ __device__ __forceinline__ void quad_townsend_factored(double a, double b, doubl
     if (!accept) dqagse_adaptive<false>(rate, a, b, g, nullptr, &result, &abserr);
 }
 
-// Closed form: int_a^b 16 r^2 t exp(-4 r t) dt = g(4rb) - g(4ra), g(x) = 1 - (1+x) exp(-x); series for small x.
-__device__ __forceinline__ double g_one_minus(double x) {
-    if (x < 0.1) {
-        double term = x * x * 0.5, sum = 0.0;
-        for (int k = 2; k < 40; ++k) {
-            const double add = term * (double)(k - 1);
-            sum += (k & 1) ? -add : add;
-            if (add <= 1e-20 * fabs(sum)) break;
-            term = term * x / (double)(k + 1);
-        }
-        return sum;
-    }
-    return 1.0 - (1.0 + x) * exp(-x);
-}
+// Closed form: int_a^b 16 r^2 t exp(-4 r t) dt = F(4ra) - F(4rb) with F(x) = (1+x) exp(-x).  Written as
+//   exp(-xa) * (xa * m + g),  xa = 4ra,  d = 4r(b-a),  m = 1 - exp(-d),  g = 1 - (1+d) exp(-d)
+// (m and g by their series for small d): two non-negative terms, so nothing cancels.  (g(4rb) - g(4ra) subtracted two
+// numbers close to 1 once 4ra was large: on [85,95] it lost every digit from r = 0.2 on.)  No expm1: its inlined code
+// raised pi_partial_kernel from 255 to 274 VGPRs, which cost the QUADPACK path its occupancy.
 __device__ __forceinline__ double integral_closed(double a, double b, double r) {
-    return g_one_minus(4.0 * r * b) - g_one_minus(4.0 * r * a);
+    const double xa = 4.0 * r * a, d = 4.0 * r * (b - a);
+    double m = 0.0, g = 0.0;
+    if (d < 0.1) {   // m = sum_{k>=1} (-1)^(k+1) d^k / k!,  g = sum_{k>=2} (-1)^k (k-1) d^k / k!
+        double term = d;   // d^k / k!
+        for (int k = 1; k < 40; ++k) {
+            const double add = term * (double)(k - 1);
+            m += (k & 1) ? term : -term;
+            g += (k & 1) ? -add : add;
+            if (k > 1 && add <= 1e-20 * fabs(g)) break;
+            term = term * d / (double)(k + 1);
+        }
+    } else {
+        const double e = exp(-d);
+        m = 1.0 - e;
+        g = m - d * e;
+    }
+    return exp(-xa) * (xa * m + g);
 }
 
 }  // namespace tphip

@@ -1,0 +1,222 @@
+"""Plain high-precision references for the site-likelihood and PI kernels (test helper, not a conftest).
+
+Everything here is restated from the mathematics alone, in mpmath at DPS decimal digits.  It shares no code and no
+formula arrangement with the kernels or with oracle/tapir_oracle.c: no Jacobi iteration, no rescaling, no rounding of
+intermediate results to fp64, no QUADPACK restatement (the QUADPACK reference is scipy.integrate.quad itself, which is
+what the reference program calls).
+
+* Column log-likelihood f(u) = log L(s = e^u) of one alignment column, with g = df/du and h = d2f/du2, under GTR in
+  HyPhy's parametrisation (Q_ij = r_ij pi_j for i != j, rows summing to 0, not normalised; the reported rate is
+  kappa * s with kappa = sum_i pi_i (-Q_ii)) and under F81 (r_ij = 1, P(tau) = e I + (1 - e) Pi in closed form).
+  P(tau) comes from mpmath's symmetric eigen-solver applied to D^1/2 Q D^-1/2, and the derivatives are analytic:
+  d/du P(t e^u) = (Q tau) P, d2/du2 = (Q tau + (Q tau)^2) P.  Pruning is plain (mpmath's exponent range makes
+  rescaling unnecessary).
+* PI(t) = 16 r^2 t exp(-4 r t) and its exact integral G(4rb) - G(4ra), G(x) = -(1+x) exp(-x).
+"""
+import math
+
+import mpmath
+import numpy as np
+from scipy import integrate
+
+DPS = 40
+mp = mpmath.mp
+PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))   # exchangeability order AC, AG, AT, CG, CT, GT
+
+
+def floored_pi(pi, floor=1e-12):
+    """pi as a GTR plan floors it (an absent base gets floor * sum) and renormalised."""
+    pi = np.asarray(pi, np.float64)
+    p = np.maximum(pi, floor * pi.sum())
+    return p / p.sum()
+
+
+def rate_matrix(pi, exch):
+    """HyPhy's unnormalised GTR generator (mpmath matrix) and kappa."""
+    with mp.workdps(DPS):
+        pi = [mpmath.mpf(float(x)) for x in pi]
+        tot = mpmath.fsum(pi)
+        pi = [x / tot for x in pi]
+        Q = mpmath.zeros(4, 4)
+        for (i, j), r in zip(PAIRS, exch):
+            Q[i, j] = mpmath.mpf(float(r)) * pi[j]
+            Q[j, i] = mpmath.mpf(float(r)) * pi[i]
+        for i in range(4):
+            Q[i, i] = -mpmath.fsum(Q[i, j] for j in range(4) if j != i)
+        kappa = -mpmath.fsum(pi[i] * Q[i, i] for i in range(4))
+        return Q, pi, kappa
+
+
+class _Model:
+    """Transition matrices P(tau), dP/du, d2P/du2 (tau = t e^u) as 4x4 object arrays of mpf."""
+
+    def __init__(self, pi, exch, model):
+        self.model = model
+        with mp.workdps(DPS):
+            if model == "f81":
+                p = [mpmath.mpf(float(x)) for x in pi]
+                tot = mpmath.fsum(p)
+                self.pi = [x / tot for x in p]
+                self.kappa = 1 - mpmath.fsum(x * x for x in self.pi)
+            else:
+                Q, self.pi, self.kappa = rate_matrix(pi, exch)
+                sq = [mpmath.sqrt(x) for x in self.pi]
+                S = mpmath.zeros(4, 4)
+                for i in range(4):
+                    for j in range(4):
+                        S[i, j] = sq[i] * Q[i, j] / sq[j]
+                S = (S + S.T) / 2
+                lam, V = mpmath.eigsy(S)
+                self.lam = [lam[k] for k in range(4)]
+                # P_ij(tau) = sqrt(pi_j / pi_i) sum_k V_ik V_jk exp(lam_k tau)
+                self.B = [[[V[i, k] * V[j, k] * sq[j] / sq[i] for j in range(4)] for i in range(4)] for k in range(4)]
+
+    def matrices(self, tau):
+        with mp.workdps(DPS):
+            P = np.empty((4, 4), object)
+            P1 = np.empty((4, 4), object)
+            P2 = np.empty((4, 4), object)
+            if self.model == "f81":
+                e = mpmath.exp(-tau)
+                e1, e2 = -tau * e, (tau * tau - tau) * e
+                for i in range(4):
+                    for j in range(4):
+                        d = 1 if i == j else 0
+                        P[i, j] = e * d + (1 - e) * self.pi[j]
+                        P1[i, j] = e1 * (d - self.pi[j])
+                        P2[i, j] = e2 * (d - self.pi[j])
+                return P, P1, P2
+            terms = []
+            for k in range(4):
+                x = self.lam[k] * tau
+                e = mpmath.exp(x)
+                terms.append((e, x * e, (x + x * x) * e))
+            for i in range(4):
+                for j in range(4):
+                    P[i, j] = mpmath.fsum(terms[k][0] * self.B[k][i][j] for k in range(4))
+                    P1[i, j] = mpmath.fsum(terms[k][1] * self.B[k][i][j] for k in range(4))
+                    P2[i, j] = mpmath.fsum(terms[k][2] * self.B[k][i][j] for k in range(4))
+            return P, P1, P2
+
+
+def kappa(pi, exch=None, model="gtr"):
+    return float(_Model(pi, exch, model).kappa)
+
+
+def column_curves(states, parent, blen, leaf_taxon, pi, exch, u, model="gtr"):
+    """f, g, h of every column of `states` (uint8 masks [ntaxa, ncols]) at every u: float arrays [len(u), ncols].
+    parent / blen / leaf_taxon: post-order tree arrays (root last), as the engine takes them.  pi is used as given
+    (normalised to sum 1): a GTR plan floors absent bases first, see floored_pi."""
+    states = np.asarray(states, np.uint8)
+    ntaxa, ncols = states.shape
+    parent = np.asarray(parent)
+    blen = np.asarray(blen, np.float64)
+    leaf_taxon = np.asarray(leaf_taxon)
+    M = _Model(pi, exch, model)
+    nn = len(parent)
+    children = [[] for _ in range(nn)]
+    for n in range(nn):
+        if parent[n] >= 0:
+            children[parent[n]].append(n)
+    one, zero = mpmath.mpf(1), mpmath.mpf(0)
+    tips = {}
+    for n in range(nn):
+        if leaf_taxon[n] >= 0:
+            m = states[leaf_taxon[n]] & 15
+            tips[n] = np.array([[one if (int(c) >> i) & 1 else zero for c in m] for i in range(4)], object)
+    F = np.empty((len(u), ncols))
+    G = np.empty_like(F)
+    H = np.empty_like(F)
+    with mp.workdps(DPS):
+        for iu, uu in enumerate(u):
+            s = mpmath.exp(mpmath.mpf(float(uu)))
+            part = [None] * nn
+            for n in range(nn):          # post-order: children first
+                if leaf_taxon[n] >= 0:
+                    v, d1, d2 = tips[n], None, None
+                else:
+                    v = d1 = d2 = None
+                    for c in children[n]:
+                        mv, m1, m2 = part[c]
+                        if v is None:
+                            v, d1, d2 = mv, m1, m2
+                        else:
+                            v, d1, d2 = v * mv, d1 * mv + v * m1, d2 * mv + 2 * d1 * m1 + v * m2
+                if parent[n] < 0:
+                    part[n] = (v, d1, d2)
+                    continue
+                P, P1, P2 = M.matrices(mpmath.mpf(float(blen[n])) * s)
+                if d1 is None:           # a tip: its vector does not depend on u
+                    part[n] = (P.dot(v), P1.dot(v), P2.dot(v))
+                else:
+                    part[n] = (P.dot(v), P1.dot(v) + P.dot(d1), P2.dot(v) + 2 * P1.dot(d1) + P.dot(d2))
+            v, d1, d2 = part[nn - 1]
+            pi_r = np.array(M.pi, object)
+            L, L1, L2 = pi_r.dot(v), pi_r.dot(d1), pi_r.dot(d2)
+            for c in range(ncols):
+                g = L1[c] / L[c]
+                F[iu, c] = float(mpmath.log(L[c]))
+                G[iu, c] = float(g)
+                H[iu, c] = float(L2[c] / L[c] - g * g)
+    return F, G, H
+
+
+# ---- PI ------------------------------------------------------------------------------------------------------------
+
+def finalize_rates(rates, round_decimals=4, correction=1.0, nres=None, threshold=3):
+    """What the PI stage does to a raw rate: HyPhy's 4-decimal print and parse, / correction, NaN below threshold."""
+    r = np.array([float("%.*f" % (round_decimals, v)) if (round_decimals >= 0 and np.isfinite(v)) else v
+                  for v in np.asarray(rates, np.float64)])
+    r = r / correction
+    if nres is not None:
+        r[np.asarray(nres) < threshold] = np.nan
+    return r
+
+
+def net_pi(rates, T):
+    """nansum over sites of 16 r^2 t exp(-4 r t), t = 0..T-1: math.fsum of per-term doubles (every term is >= 0)."""
+    r = np.asarray(rates, np.float64)
+    r = r[np.isfinite(r)]
+    out = np.empty(T)
+    for t in range(T):
+        out[t] = math.fsum((16.0 * r * r * t) * np.exp(-4.0 * r * t))
+    return out
+
+
+def integral_exact(a, b, r):
+    """int_a^b 16 r^2 t exp(-4 r t) dt = G(4rb) - G(4ra), G(x) = -(1+x) exp(-x), at DPS digits (mpf)."""
+    with mp.workdps(DPS):
+        r = mpmath.mpf(float(r))
+        xa, xb = 4 * r * int(a), 4 * r * int(b)
+        return (1 + xa) * mpmath.exp(-xa) - (1 + xb) * mpmath.exp(-xb)
+
+
+def net_integrals_exact(rates, intervals):
+    """Per interval: math.fsum over the finite rates of the exact integrals (rounded to fp64 one by one)."""
+    r = np.asarray(rates, np.float64)
+    r = r[np.isfinite(r) & (r != 0.0)]
+    out = []
+    for a, b in intervals:
+        out.append(math.fsum(float(integral_exact(a, b, x)) for x in r))
+    return np.array(out)
+
+
+def townsend_pi(t, r):
+    return 16 * (r ** 2) * t * np.exp(-(4 * r * t))
+
+
+def quad(a, b, r):
+    """scipy.integrate.quad as the reference calls it (tapir/compute.py:50-52): (integral, abserr)."""
+    return integrate.quad(townsend_pi, a, b, args=(r,))
+
+
+def net_integrals_quad(rates, intervals):
+    """Per interval: math.fsum of the scipy integrals and of their abserr over the finite rates."""
+    r = np.asarray(rates, np.float64)
+    r = r[np.isfinite(r)]
+    si, se = [], []
+    for a, b in intervals:
+        q = [quad(float(a), float(b), float(x)) for x in r]
+        si.append(math.fsum(v for v, _ in q))
+        se.append(math.fsum(e for _, e in q))
+    return np.array(si), np.array(se)

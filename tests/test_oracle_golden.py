@@ -81,11 +81,16 @@ def test_numpy_restatement_matches_reference_outputs(oracle, golden):
 def test_closed_form_vs_quad(oracle, golden):
     r = golden["C_rates"]
     r = r[np.isfinite(r) & (r < 1.0)]
-    for a, b in ([0, 10], [3, 7], [20, 100]):
+    import hp_reference as hp
+    for a, b in ([0, 10], [3, 7], [20, 100], [85, 95], [45, 55]):
         for rate in r[::25]:
-            q = oracle.quad_townsend(a, b, rate)[0]
+            q, e = oracle.quad_townsend(a, b, rate)[:2]
             c = oracle.lib().orc_integral_closed(float(a), float(b), float(rate))
-            assert abs(q - c) <= 3e-8 * abs(q) + 1e-15  # quad's own tolerance is 1.49e-8
+            # quad's own tolerance is 1.49e-8, relative or (tiny integrals) absolute: there its abserr says how close it is
+            assert abs(q - c) <= 3e-8 * abs(q) + min(e, 1e-15)
+            # and the closed form against the exact value, with no absolute floor (a 0 for 2e-28 passed a 1e-15 one)
+            ex = float(hp.integral_exact(a, b, rate))
+            assert abs(c - ex) <= 1e-12 * ex
 
 
 def test_site_rates_known_answer_file(oracle, golden_dir):
