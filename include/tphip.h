@@ -369,6 +369,53 @@ int tphip_eval_columns(tphip_plan *plan, const uint8_t *states, const double *u,
 int tphip_eval_columns_dev(tphip_plan *plan, const uint8_t *d_states, const double *d_u, double *d_f, double *d_g,
                            double *d_h, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Empirical-Bayes site rates under a discrete-gamma prior (Yang 1994; the Rate4Site estimator): an opt-in alternative
+ * to the per-column maximum-likelihood rate of tphip_site_rates.  Per locus the site rate is s = mu rho with rho in
+ * ncat categories (rates cat_rate[l][k], weights cat_weight[l][k], both [nloci][ncat], HOST arrays, positive; the
+ * caller builds them, e.g. equiprobable gamma(alpha, alpha) categories) and mu = scale[l].  With L_c(s) the column
+ * likelihood of the site-rate stage (tphip_eval_columns with a one-category plan), m_c = sum_k w_k L_c(mu rho_k).
+ * A category whose log(mu rho_k) is below log(1e-10) is evaluated there (the likelihood is flat to fp64).
+ * Works on TPHIP_MODEL_GTR and TPHIP_MODEL_F81 plans; the plan's own ncat / cat_rate / cat_weight are ignored, as are
+ * column weights.  Every column of a locus takes part, whatever its count of informative cells.
+ *
+ * tphip_eb_start_scale: scale[l] (HOST, out) = where the fit of mu should start: the mean over the locus' columns of the
+ *   parsimony start rate the site-rate stage gives each column (0 for columns without a change), or 1 / tree length for a
+ *   locus without a change.  It lies on the near side of the plateau l reaches as mu grows, whatever the tree's units.
+ * tphip_eb_fit_scale: for every locus at once, maximise l(mu) = sum over the locus' columns of log m_c over log mu,
+ *   starting from scale[l] (in/out; tphip_eb_start_scale gives a start), by a safeguarded Newton
+ *   iteration on the device.  locus_lnl[l] = l and curvature[l] = d2l/d(log mu)2 at the returned scale (may be NULL);
+ *   iters[l] (may be NULL) = evaluations used, negated if the limit was reached first.  The alpha search is the caller's.
+ * tphip_eb_posterior: per column rate = kappa mu E[rho | column] (expected substitutions per unit of tree time, the
+ *   unit of tphip_site_rates' rate), rate_sd = kappa mu sd[rho | column], lnl = log m_c, nres as tphip_site_rates
+ *   reports it; tphip_corrected_rates / tphip_pi_tables take rate and nres unchanged.
+ * use_patterns = 1 evaluates one column per site pattern of a locus; results are bit-identical either way.
+ * The plain functions take HOST states; the _dev twins take DEVICE states (and device rate / rate_sd / lnl / nres), keep
+ * the small per-locus arrays on the host, enqueue on `stream` and, for the fit, synchronise it before returning.
+ * Thread-safety: as for every call that takes a plan -- calls on one plan must not overlap (they share the plan's
+ * workspace); different plans may be used from different threads. */
+typedef struct tphip_eb_opts {
+    uint32_t struct_size;  /* sizeof(tphip_eb_opts) of the caller */
+    int32_t ncat;          /* 2..16 */
+    int32_t maxit_scale;   /* limit of the Newton iteration, 0 = default (60) */
+    int32_t use_patterns;  /* 1 = compress columns to site patterns on the device first */
+    double tol_scale;      /* stop when the Newton step in log mu is below this, 0 = default (1e-9) */
+} tphip_eb_opts;
+
+int tphip_eb_start_scale(tphip_plan *plan, const uint8_t *states, double *scale);
+int tphip_eb_start_scale_dev(tphip_plan *plan, const uint8_t *d_states, double *scale, void *stream);
+int tphip_eb_fit_scale(tphip_plan *plan, const uint8_t *states, const tphip_eb_opts *opts, const double *cat_rate,
+                       const double *cat_weight, double *scale, double *locus_lnl, double *curvature, int32_t *iters);
+int tphip_eb_fit_scale_dev(tphip_plan *plan, const uint8_t *d_states, const tphip_eb_opts *opts, const double *cat_rate,
+                           const double *cat_weight, double *scale, double *locus_lnl, double *curvature,
+                           int32_t *iters, void *stream);
+int tphip_eb_posterior(tphip_plan *plan, const uint8_t *states, const tphip_eb_opts *opts, const double *cat_rate,
+                       const double *cat_weight, const double *scale, double *rate, double *rate_sd, double *lnl,
+                       int32_t *nres);
+int tphip_eb_posterior_dev(tphip_plan *plan, const uint8_t *d_states, const tphip_eb_opts *opts, const double *cat_rate,
+                           const double *cat_weight, const double *scale, double *d_rate, double *d_rate_sd,
+                           double *d_lnl, int32_t *d_nres, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

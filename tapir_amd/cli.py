@@ -84,12 +84,42 @@ def get_args(argv=None):
                           "jc = Jukes-Cantor (equal base frequencies, exchangeabilities 1; PhyDesign's other model); "
                           "f81 = exchangeabilities 1 with the locus' empirical base frequencies.  jc and f81 skip stage 1 "
                           "and run a closed-form site-rate kernel")
+    new.add_argument('--rate-estimator', choices=['ml', 'eb'], default='ml',
+                     help="ml = each site's maximum-likelihood rate (the reference's estimator); eb = empirical Bayes: the "
+                          "posterior mean of the site's rate under a discrete-gamma prior whose scale and shape are fitted "
+                          "to the locus (Yang 1994), so a site without a change gets a small positive rate instead of 0")
+    new.add_argument('--eb-categories', type=int, default=None,
+                     help="categories of the empirical-Bayes prior, 2..16 (default 8); needs --rate-estimator eb")
+    new.add_argument('--eb-alpha', type=float, default=None,
+                     help="fix the shape of the empirical-Bayes prior (default: estimated per locus); needs --rate-estimator eb")
+    new.add_argument('--eb-alpha-bounds', type=_two_floats, default=None,
+                     help="LO,HI: range in which the shape is estimated (default 0.2,50); needs --rate-estimator eb")
     args = parser.parse_args(argv)
     if args.site_model != 'locus':
         for flag, given in (('--exchangeabilities', args.exchangeabilities is not None), ('--subs-model', bool(args.subs_model)),
                             ('--site-rates', args.site_rates)):
             if given:
                 parser.error("--site-model {0} fixes the model: it cannot be combined with {1}".format(args.site_model, flag))
+    eb_flags = (('--eb-categories', args.eb_categories), ('--eb-alpha', args.eb_alpha), ('--eb-alpha-bounds', args.eb_alpha_bounds))
+    if args.rate_estimator != 'eb':
+        for flag, value in eb_flags:
+            if value is not None:
+                parser.error("{0} needs --rate-estimator eb".format(flag))
+    else:
+        if args.site_rates:
+            parser.error("--rate-estimator eb estimates the site rates: it cannot be combined with --site-rates")
+        if args.gamma_categories > 1:
+            parser.error("--rate-estimator eb has its own prior (--eb-categories): it cannot be combined with --gamma-categories above 1")
+        if args.eb_categories is None:
+            args.eb_categories = 8
+        if not 2 <= args.eb_categories <= 16:
+            parser.error("--eb-categories must be in 2..16")
+        if args.eb_alpha is not None and not args.eb_alpha > 0:
+            parser.error("--eb-alpha must be positive")
+        if args.eb_alpha_bounds is None:
+            args.eb_alpha_bounds = (0.2, 50.0)
+        if not 0 < args.eb_alpha_bounds[0] < args.eb_alpha_bounds[1]:
+            parser.error("--eb-alpha-bounds must be LO,HI with 0 < LO < HI")
     return args
 
 
@@ -99,6 +129,15 @@ def _six_floats(string):
         assert len(v) == 6
     except Exception as e:
         raise argparse.ArgumentTypeError("Cannot convert exchangeabilities to six numbers: {0}".format(e))
+    return v
+
+
+def _two_floats(string):
+    try:
+        v = tuple(float(x) for x in string.split(','))
+        assert len(v) == 2
+    except Exception as e:
+        raise argparse.ArgumentTypeError("Cannot convert bounds to two numbers: {0}".format(e))
     return v
 
 
@@ -267,7 +306,10 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
                                                start_rule=1 if args.reference_start else 0,
                                                during_write=store if world == 1 else None,
                                                table_sink=_TableSink() if world == 1 else None,
-                                               site_model=args.site_model)
+                                               site_model=args.site_model, rate_estimator=args.rate_estimator,
+                                               eb_options=None if args.rate_estimator != 'eb' else dict(
+                                                   categories=args.eb_categories, alpha=args.eb_alpha,
+                                                   alpha_bounds=args.eb_alpha_bounds))
             tables = out["final_tables"]
             stored = bool(out.get("during_write_done"))
             sqlite_seconds = LAST_TIMINGS.get("sqlite")

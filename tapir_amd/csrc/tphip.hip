@@ -61,6 +61,7 @@ int tphip_plan_destroy(tphip_plan* plan) {
     if (plan->d_value_packed) { (void)hipFree(plan->d_value_packed); plan->d_value_packed = nullptr; }
     if (plan->d_part) { (void)hipFree(plan->d_part); plan->d_part = nullptr; }
     if (plan->d_col_weight) { (void)hipFree(plan->d_col_weight); plan->d_col_weight = nullptr; }
+    if (plan->d_eb_ws) { (void)hipFree(plan->d_eb_ws); plan->d_eb_ws = nullptr; }
     if (plan->d_grad_params) { (void)hipFree(plan->d_grad_params); plan->d_grad_params = nullptr; }
     plan->d_grad2_fops.release(); plan->d_grad2_rops.release();
     if (plan->d_grad2_ws) { (void)hipFree(plan->d_grad2_ws); plan->d_grad2_ws = nullptr; }
@@ -747,6 +748,67 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
     }
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 1], st));
     if (dedup) dedup_scatter_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
+    HIP_TRY(hipGetLastError());
+    return TPHIP_OK;
+}
+
+// Where the empirical-Bayes fit of a locus' scale starts: the mean over ALL its columns of classify_kernel's parsimony start
+// rate s0 (start_log_rate; 0 for the columns it answers in closed form), or 1 / tree length for a locus without a change.
+// One workgroup per locus, thread-strided sums and a binary tree: the order depends on the locus alone.
+__global__ __launch_bounds__(256) void eb_start_scale_kernel(const int64_t* __restrict__ locus_offsets, const uint8_t* __restrict__ flag,
+                                                            const double* __restrict__ start_log, double chrono_length,
+                                                            double* __restrict__ start) {
+    __shared__ double red[256];
+    const int locus = blockIdx.x;
+    const int64_t lo = locus_offsets[locus], hi = locus_offsets[locus + 1];
+    double sum = 0.0;
+    for (int64_t c = lo + threadIdx.x; c < hi; c += 256)
+        if (flag[c] == TPHIP_FLAG_OK) sum += exp(start_log[c]);
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) start[locus] = (red[0] > 0.0 && hi > lo) ? red[0] / (double)(hi - lo) : 1.0 / chrono_length;
+}
+
+// Front end of the empirical-Bayes calls (eb_driver.hip): classify_kernel for the informative-cell counts and the packed
+// tip words, then -- every column takes part in the mixture, constant ones included -- either all columns, or the first
+// column of every site pattern of a locus as a compacted work list (the stage-2 de-duplication kernels, forced on).
+int tphip_internal_eb_prepare(tphip_plan* p, const uint8_t* d_states, const EbPrep* B, int32_t use_patterns, double* d_start,
+                              void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (p->n_pi_chunks <= 0) return TPHIP_OK;
+    ClassifyParams C;
+    C.states = d_states; C.ncols_total = p->ncols; C.ntaxa = p->ntaxa; C.models = p->d_models.p;
+    C.locus_offsets = p->d_offsets.p; C.chunk_locus = p->d_pi_chunk_locus.p; C.chunk_index = p->d_pi_chunk_index.p;
+    C.rate = B->scratch[0]; C.subst = B->scratch[1]; C.lnl = B->scratch[2]; C.flag = B->flag; C.nres = B->nres;
+    C.chrono_length = p->prog.chrono_length;
+    C.ops = p->d_ops.p; C.nops = (int32_t)p->prog.ops.size();
+    C.packed = B->packed;
+    C.tip_taxon = p->d_tip_taxon.p;
+    C.start_scale = 1.0;
+    C.hash = use_patterns ? B->hash : nullptr;
+    classify_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(kPiBlock), 0, st>>>(C);
+    if (d_start)   // before the flags are reset: they tell which columns carry a start rate
+        eb_start_scale_kernel<<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(p->d_offsets.p, B->flag, B->scratch[0],
+                                                                             p->prog.chrono_length, d_start);
+    HIP_TRY(hipMemsetAsync(B->flag, TPHIP_FLAG_OK, (size_t)p->ncols, st));
+    HIP_TRY(hipMemsetAsync(B->dup_of, 0xff, sizeof(int32_t) * (size_t)p->ncols, st));
+    if (use_patterns) {
+        DedupParams D;
+        D.locus_offsets = p->d_offsets.p; D.chunk_locus = p->d_pi_chunk_locus.p; D.chunk_index = p->d_pi_chunk_index.p;
+        D.hash = B->hash; D.packed = B->packed; D.nwords = p->nwords; D.ncols_total = p->ncols; D.flag = B->flag;
+        D.dup_of = B->dup_of; D.tab_key = B->tab_key; D.tab_val = B->tab_val; D.on = B->on; D.mode = DEDUP_ON;
+        D.rate = nullptr; D.subst = nullptr; D.lnl = nullptr;
+        if (p->max_locus_cols > 2048) dedup_estimate_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(D);
+        else dedup_estimate_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(D);
+        dedup_insert_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
+        dedup_resolve_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
+        if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(B->flag, p->d_offsets.p, B->work_cols, B->work_count);
+        else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(B->flag, p->d_offsets.p, B->work_cols, B->work_count);
+    }
     HIP_TRY(hipGetLastError());
     return TPHIP_OK;
 }

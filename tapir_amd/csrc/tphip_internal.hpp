@@ -131,6 +131,8 @@ struct tphip_plan {
     double* d_grad2_ws = nullptr;    // per-candidate transition matrices + branch tables of one chunk of candidates
     size_t grad2_ws_bytes = 0;
     void* d_grad2_params = nullptr;
+    void* d_eb_ws = nullptr;         // workspace of the empirical-Bayes calls (eb_driver.hip), grown on demand
+    size_t eb_ws_bytes = 0;
     double* d_col_weight = nullptr;  // optional column multiplicities for the locus likelihood / gradient kernels
     double* d_part = nullptr;   // per-slice partial sums of the locus likelihood / gradient kernels, grown on demand
     size_t part_bytes = 0;
@@ -162,6 +164,22 @@ struct tphip_plan {
     int64_t acc_launches = 0;
 };
 
+// Device buffers tphip_internal_eb_prepare fills for eb_driver.hip: what classify_kernel leaves (informative-cell counts,
+// packed tip words) and, with site patterns, the pattern representatives as a compacted work list per locus.
+struct EbPrep {
+    uint32_t* packed;             // [nwords][ncols]
+    int32_t* nres;                // [ncols]
+    uint8_t* flag;                // [ncols] scratch
+    double* scratch[3];           // [ncols] each: classify_kernel's rate / subst / lnl slots (overwritten later)
+    uint64_t* hash;               // [ncols]       (patterns)
+    int32_t* dup_of;              // [ncols] representative column of a repeated pattern, or -1
+    unsigned long long* tab_key;  // [2 * ncols]   (patterns)
+    int32_t* tab_val;             // [2 * ncols]   (patterns)
+    int32_t* on;                  // [nloci]       (patterns)
+    int32_t* work_cols;           // [ncols]       (patterns)
+    int32_t* work_count;          // [nloci]       (patterns)
+};
+
 // helpers of tphip.hip for the other translation units of the library (not declared in include/tphip.h)
 // (hidden visibility: the shared library exports exactly what include/tphip.h declares)
 extern "C" {
@@ -171,6 +189,8 @@ __attribute__((visibility("hidden"))) const tphip_plan_desc* tphip_internal_save
 __attribute__((visibility("hidden"))) int tphip_internal_compress_dev(const uint8_t* d_s, int64_t ncols_total, int32_t ntaxa,
                                                                     const int64_t* d_off, int64_t nloci, uint8_t** d_out,
                                                                     int64_t** d_newoff, double** d_w, int64_t* npat);
+__attribute__((visibility("hidden"))) int tphip_internal_eb_prepare(tphip_plan* p, const uint8_t* d_states, const EbPrep* B,
+                                                                  int32_t use_patterns, double* d_start, void* stream);
 __attribute__((visibility("hidden"))) int tphip_internal_store_pi(tphip_plan* p, const double* pi);
 __attribute__((visibility("hidden"))) int tphip_internal_set_models_dev(tphip_plan* p, const double* d_pi, const double* d_exch,
                                                                       void* stream);

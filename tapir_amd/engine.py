@@ -44,6 +44,11 @@ class Stage1Opts(ctypes.Structure):
                 ("row_pitch", _i64)]
 
 
+class EbOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ncat", _i32), ("maxit_scale", _i32), ("use_patterns", _i32),
+                ("tol_scale", _f64)]
+
+
 # every symbol include/tphip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("tphip_version", ctypes.c_int, []),
@@ -91,6 +96,12 @@ SYMBOLS = [
     ("tphip_stage1_fit_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(Stage1Opts)] + [_vp] * 10),
     ("tphip_stage1_fit", ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(Stage1Opts)] + [_vp] * 9),
     ("tphip_plan_set_models", ctypes.c_int, [_vp, _vp, _vp]),
+    ("tphip_eb_start_scale", ctypes.c_int, [_vp, _vp, _vp]),
+    ("tphip_eb_start_scale_dev", ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    ("tphip_eb_fit_scale", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tphip_eb_fit_scale_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tphip_eb_posterior", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tphip_eb_posterior_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None
@@ -330,6 +341,63 @@ class Plan:
 
     def eval_columns_dev(self, d_states, d_u, d_f, d_g, d_h, stream=0):
         _check(self._lib.tphip_eval_columns_dev(self._h, _ptr(d_states), _ptr(d_u), _ptr(d_f), _ptr(d_g), _ptr(d_h), stream))
+
+    def _eb_args(self, cat_rate, cat_weight, scale, use_patterns, maxit_scale=0, tol_scale=0.0):
+        cr = _np(cat_rate, np.float64)
+        cw = _np(cat_weight, np.float64)
+        if cr.ndim != 2 or cr.shape[0] != self.nloci or cw.shape != cr.shape:
+            raise TphipError("cat_rate and cat_weight must be [nloci][ncat]")
+        sc = np.array(scale, dtype=np.float64).reshape(-1)   # a copy: the fit writes into it
+        if sc.shape != (self.nloci,):
+            raise TphipError("scale must be [nloci]")
+        opts = EbOpts(ctypes.sizeof(EbOpts), int(cr.shape[1]), int(maxit_scale), 1 if use_patterns else 0, float(tol_scale))
+        return opts, cr, cw, sc
+
+    def eb_start_scale(self, states):
+        """Start of the scale fit per locus (tphip_eb_start_scale): the locus' mean parsimony start rate."""
+        states = _np(states, np.uint8)
+        sc = np.empty(self.nloci)
+        _check(self._lib.tphip_eb_start_scale(self._h, states.ctypes.data, sc.ctypes.data))
+        return sc
+
+    def eb_start_scale_dev(self, d_states, stream=0):
+        sc = np.empty(self.nloci)
+        _check(self._lib.tphip_eb_start_scale_dev(self._h, _ptr(d_states), sc.ctypes.data, stream))
+        return sc
+
+    def eb_fit_scale(self, states, cat_rate, cat_weight, scale, use_patterns=True, maxit_scale=0, tol_scale=0.0):
+        """Empirical-Bayes inner problem (tphip_eb_fit_scale): for every locus the scale mu that maximises
+        sum_c log sum_k w_k L_c(mu rho_k), by Newton iteration in log mu from scale[nloci].
+        Returns dict(scale, locus_lnl, curvature, iters); iters < 0 marks a locus that hit the iteration limit."""
+        states = _np(states, np.uint8)
+        opts, cr, cw, sc = self._eb_args(cat_rate, cat_weight, scale, use_patterns, maxit_scale, tol_scale)
+        lnl, curv, it = np.empty(self.nloci), np.empty(self.nloci), np.zeros(self.nloci, dtype=np.int32)
+        _check(self._lib.tphip_eb_fit_scale(self._h, states.ctypes.data, ctypes.byref(opts), cr.ctypes.data, cw.ctypes.data,
+                                            sc.ctypes.data, lnl.ctypes.data, curv.ctypes.data, it.ctypes.data))
+        return dict(scale=sc, locus_lnl=lnl, curvature=curv, iters=it)
+
+    def eb_posterior(self, states, cat_rate, cat_weight, scale, use_patterns=True):
+        """Per column (tphip_eb_posterior): rate = kappa mu E[rho | column], sd, lnl = log m_c, nres."""
+        states = _np(states, np.uint8)
+        opts, cr, cw, sc = self._eb_args(cat_rate, cat_weight, scale, use_patterns)
+        rate, sd, lnl = np.empty(self.ncols), np.empty(self.ncols), np.empty(self.ncols)
+        nres = np.empty(self.ncols, dtype=np.int32)
+        _check(self._lib.tphip_eb_posterior(self._h, states.ctypes.data, ctypes.byref(opts), cr.ctypes.data, cw.ctypes.data,
+                                            sc.ctypes.data, rate.ctypes.data, sd.ctypes.data, lnl.ctypes.data, nres.ctypes.data))
+        return dict(rate=rate, sd=sd, lnl=lnl, nres=nres)
+
+    def eb_fit_scale_dev(self, d_states, cat_rate, cat_weight, scale, use_patterns=True, maxit_scale=0, tol_scale=0.0, stream=0):
+        """eb_fit_scale with the alignment already on the device (d_states: device pointer or tensor)."""
+        opts, cr, cw, sc = self._eb_args(cat_rate, cat_weight, scale, use_patterns, maxit_scale, tol_scale)
+        lnl, curv, it = np.empty(self.nloci), np.empty(self.nloci), np.zeros(self.nloci, dtype=np.int32)
+        _check(self._lib.tphip_eb_fit_scale_dev(self._h, _ptr(d_states), ctypes.byref(opts), cr.ctypes.data, cw.ctypes.data,
+                                                sc.ctypes.data, lnl.ctypes.data, curv.ctypes.data, it.ctypes.data, stream))
+        return dict(scale=sc, locus_lnl=lnl, curvature=curv, iters=it)
+
+    def eb_posterior_dev(self, d_states, cat_rate, cat_weight, scale, d_rate, d_sd, d_lnl, d_nres, use_patterns=True, stream=0):
+        opts, cr, cw, sc = self._eb_args(cat_rate, cat_weight, scale, use_patterns)
+        _check(self._lib.tphip_eb_posterior_dev(self._h, _ptr(d_states), ctypes.byref(opts), cr.ctypes.data, cw.ctypes.data,
+                                                sc.ctypes.data, _ptr(d_rate), _ptr(d_sd), _ptr(d_lnl), _ptr(d_nres), stream))
 
     def corrected_rates(self, rates, nres=None):
         """parse_site_rates (+ cull when nres is given) as the PI stage applies them: round4(rate) / correction."""

@@ -206,7 +206,7 @@ def _rates_template(n):
     return t
 
 
-def dumps_rates_json(freqs, exch, site, subst, rate, ll, corrected):
+def dumps_rates_json(freqs, exch, site, subst, rate, ll, corrected, sd=None, eb=None):
     """The text `json.dumps(format_rates_json(...), indent=4)` would produce, built by bulk string operations: the generic
     encoder spends ~30 us per site (it dominated the whole CLI), a formatted row per site ~2 us, this ~1.2 us, of which
     0.6 are the four float.__repr__ (every per-site step -- rounding, repr, placing the numbers in the fixed text -- runs
@@ -216,6 +216,11 @@ def dumps_rates_json(freqs, exch, site, subst, rate, ll, corrected):
             '            "T": %s\n        },\n        "subs_matrix": {\n            "AC": %s,\n            "AG": %s,\n'
             '            "AT": %s,\n            "CG": %s,\n            "CT": %s,\n            "GT": %s\n        },\n'
             % tuple(repr(float(x)) for x in list(freqs) + list(exch)))
+    if eb is not None:   # empirical-Bayes rates: the prior's fit in the header, every row with the posterior sd
+        head += ('        "estimator": "eb",\n        "gamma_alpha": %s,\n        "gamma_scale": %s,\n        "gamma_categories": %d,\n'
+                 '        "locus_lnl": %s,\n' % (repr(float(eb["alpha"])), repr(float(eb["scale"])), int(eb["categories"]),
+                                                 repr(float(eb["locus_lnl"]))))
+        return head + _eb_rows(site, subst, rate, ll, corrected, sd) + "    }\n}"
     site = np.asarray(site).astype(np.int64).reshape(-1)
     n = site.size
     cor = map(repr, np.ascontiguousarray(corrected, dtype=np.float64).reshape(-1).tolist())   # json writes float.__repr__
@@ -237,10 +242,31 @@ def dumps_rates_json(freqs, exch, site, subst, rate, ll, corrected):
     return head + body + "    }\n}"
 
 
-def _write_rates_file(path, freqs, exch, subst, rate4, lnl, corrected):
+_EROW = ('            {\n                "site": ', ',\n                "subst": ', ',\n                "rate": ',
+         ',\n                "ll": ', ',\n                "sd": ', '\n            },\n')
+
+
+def _eb_rows(site, subst, rate, ll, corrected, sd):
+    """The two arrays of an empirical-Bayes `.rates` document: the rows of the maximum-likelihood one plus "sd"."""
+    from itertools import chain, repeat
+    site = np.asarray(site).astype(np.int64).reshape(-1)
+    if site.size == 0:
+        return '        "rates": [],\n        "corrected_rates": []\n'
+    sub, rat, lls, sds = _repr_rounded(subst), _repr_rounded(rate), _repr_rounded(ll), _repr_rounded(sd)
+    cor = map(repr, np.ascontiguousarray(corrected, dtype=np.float64).reshape(-1).tolist())
+    sites = list(map(str, site.tolist()))
+    a, b, c, d, e, f = _EROW
+    rows = "".join(chain.from_iterable(zip(repeat(a), sites, repeat(b), sub, repeat(c), rat, repeat(d), lls, repeat(e), sds,
+                                           repeat(f))))[:-2]
+    a, b, e = _CROW
+    crow = "".join(chain.from_iterable(zip(repeat(a), sites, repeat(b), cor, repeat(e))))[:-2]
+    return '        "rates": [\n%s\n        ],\n        "corrected_rates": [\n%s\n        ]\n' % (rows, crow)
+
+
+def _write_rates_file(path, freqs, exch, subst, rate4, lnl, corrected, sd=None, eb=None):
     n = len(subst)
     with open(path, "w") as fh:
-        fh.write(dumps_rates_json(freqs, exch, np.arange(1, n + 1), subst, rate4, lnl, corrected))
+        fh.write(dumps_rates_json(freqs, exch, np.arange(1, n + 1), subst, rate4, lnl, corrected, sd=sd, eb=eb))
 
 
 _SHARED_VIEWS = {}
@@ -248,12 +274,16 @@ _SHARED_VIEWS = {}
 
 def _write_job(job):
     """Pool worker: format one locus' .rates file from the per-site arrays the parent left in a shared file."""
-    path, shared, total, a, b, freqs, exch = job
+    path, shared, total, a, b, freqs, exch = job[:7]
+    eb = job[7] if len(job) > 7 else None   # empirical-Bayes runs: the locus' fit, and a fifth row (sd) in the shared file
     arr = _SHARED_VIEWS.get(shared)
     if arr is None:
         _SHARED_VIEWS.clear()   # one run at a time: drop the mapping of a previous run
-        arr = _SHARED_VIEWS[shared] = np.memmap(shared, dtype=np.float64, mode="r", shape=(4, total))
-    _write_rates_file(path, freqs, exch, arr[0, a:b], arr[1, a:b], arr[2, a:b], arr[3, a:b])
+        arr = _SHARED_VIEWS[shared] = np.memmap(shared, dtype=np.float64, mode="r", shape=(4 if eb is None else 5, total))
+    if eb is not None:
+        _write_rates_file(path, freqs, exch, arr[0, a:b], arr[1, a:b], arr[2, a:b], arr[3, a:b], sd=arr[4, a:b], eb=eb)
+    else:
+        _write_rates_file(path, freqs, exch, arr[0, a:b], arr[1, a:b], arr[2, a:b], arr[3, a:b])
     return path
 
 
@@ -357,6 +387,26 @@ def model_averaged_exchangeabilities(eng, states, offsets, pi, ntaxa, parent, bl
 STREAM_BLOCK_LOCI = 8192   # loci per block of the streamed run (_run_streamed)
 
 
+def _eb_meta(fit, l):
+    return dict(alpha=fit["alpha"][l], scale=fit["scale"][l], categories=fit["categories"], locus_lnl=fit["locus_lnl"][l])
+
+
+def _eb_rates(plan, states, offsets, parent, blen, leaf, eb_options, tables=True):
+    """The empirical-Bayes estimator in the place of the site-rate launch (tapir_amd/eb.py): the per-column arrays run_fused
+    returns (rate = posterior mean, lnl = log marginal likelihood, subst = rate x tree length, flag = 0) plus sd and the
+    per-locus fit; the PI tables come from the same tphip_pi_tables call, fed with these rates."""
+    from . import eb
+    est = eb.estimate(plan, states, ncat=eb_options["categories"], alpha=eb_options.get("alpha"),
+                      alpha_bounds=eb_options.get("alpha_bounds") or eb.ALPHA_BOUNDS)
+    length = float(np.asarray(blen, np.float64)[np.asarray(parent) >= 0].sum())
+    out = dict(rate=est["rate"], subst=est["rate"] * length, lnl=est["lnl"], flag=np.zeros(len(est["rate"]), np.uint8),
+               nres=est["nres"], sd=est["sd"],
+               eb=dict(alpha=est["alpha"], scale=est["scale"], locus_lnl=est["locus_lnl"], categories=est["categories"]))
+    if tables:
+        out["tables"] = plan.pi_tables(out["rate"], out["nres"])
+    return out
+
+
 def _block_sizes():
     """(stage-1 block, stream block) in loci; TPHIP_STREAM_BLOCK=n sets both to n (tests: a streamed and an unstreamed run of
     the same small batch then fit the same loci together and must write the same bytes)."""
@@ -377,7 +427,7 @@ def _fixed_model_pi(eng, site_model, states, offsets, device):
 
 def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
                   pi, output_dir, device, integ_mode, round_decimals, extra, pool, progress, table_sink, timings, lap,
-                  site_model="locus"):
+                  site_model="locus", eb_options=None):
     """The whole pipeline block by block, host and device working at the same time.
 
     Block k of the loci: stage 1 (one tphip_stage1_fit call on the block's column range of the pinned batch array), its
@@ -396,6 +446,11 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
     new = getattr(eng, "pinned_empty", None) or np.empty
     out = dict(rate=new(total, np.float64), subst=new(total, np.float64), lnl=new(total, np.float64), flag=new(total, np.uint8),
                nres=new(total, np.int32), tables=new((L, W), np.float64))
+    nrow = 4
+    if eb_options is not None:   # the posterior sd is a fifth per-site array; the per-locus fits go into the .rates headers
+        nrow = 5
+        out["sd"] = np.empty(total)
+        out["eb"] = dict(alpha=np.empty(L), scale=np.empty(L), locus_lnl=np.empty(L), categories=int(eb_options["categories"]))
     exch_all, pi_all = np.empty((L, 6)), np.empty((L, 4))
     per_locus = [None] * L
     fd, shared = tempfile.mkstemp(prefix="tapir_amd_", suffix=".f64", dir=_shared_dir(32 * max(total, 1)))
@@ -421,7 +476,7 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
         sink_thread = threading.Thread(target=drain, name="tapir_amd-sqlite")
         sink_thread.start()
     try:
-        arr = np.memmap(shared, dtype=np.float64, mode="w+", shape=(4, max(total, 1)))
+        arr = np.memmap(shared, dtype=np.float64, mode="w+", shape=(nrow, max(total, 1)))
         step = _block_sizes()[1]
         for l0 in range(0, L, step):
             l1 = min(L, l0 + step)
@@ -445,8 +500,17 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
                     lap("stage1_model_averaging")
                     exch_all[l0:l1], pi_all[l0:l1] = res["exch"], res["pi"]
                     plan.set_models(exch=res["exch"])
-                plan.run_fused_into(cols, out, col0=a, locus0=l0)
-                lap("site_rates_and_pi_incl_pcie")
+                if eb_options is not None:
+                    blk = _eb_rates(plan, np.ascontiguousarray(cols), offsets[l0:l1 + 1] - a, parent, blen, leaf, eb_options)
+                    for k in ("rate", "subst", "lnl", "flag", "nres", "sd"):
+                        out[k][a:b] = blk[k]
+                    out["tables"][l0:l1] = blk["tables"]
+                    for k in ("alpha", "scale", "locus_lnl"):
+                        out["eb"][k][l0:l1] = blk["eb"][k]
+                    lap("eb_rates_and_pi_incl_pcie")
+                else:
+                    plan.run_fused_into(cols, out, col0=a, locus0=l0)
+                    lap("site_rates_and_pi_incl_pcie")
             finally:
                 plan.close()
             rate4 = compute.round_like_hyphy(out["rate"][a:b], round_decimals) if round_decimals >= 0 else out["rate"][a:b]
@@ -458,6 +522,9 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
             lap("round_correct_cull")
             jobs = [(os.path.join(output_dir, os.path.basename(alignments[l]) + ".rates"), shared, max(total, 1), int(offsets[l]),
                      int(offsets[l + 1]), pi_all[l], exch_all[l]) for l in range(l0, l1)]
+            if eb_options is not None:
+                arr[4, a:b] = out["sd"][a:b]
+                jobs = [job + (_eb_meta(out["eb"], l),) for job, l in zip(jobs, range(l0, l1))]
             pending.append(pool.write_rates_async(jobs))
             if sink_thread is not None:
                 q.put((alignments[l0:l1], out["tables"][l0:l1].copy()))
@@ -492,7 +559,7 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
 def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
                    exch, pi=None, subsets=None, output_dir=None, device=0, integ_mode=0, round_decimals=4,
                    engine_mod=None, progress=None, pool=None, cat_rates=None, cat_weights=None, start_rule=0,
-                   during_write=None, table_sink=None, site_model="locus"):
+                   during_write=None, table_sink=None, site_model="locus", rate_estimator="ml", eb_options=None):
     """Site rates + PI for a list of NEXUS alignments.  Returns a list of worker()-shaped tuples
     (alignment, rates, mean_rate, None, pi_net, pi_times, pi_epochs) in the order of `alignments`.
 
@@ -506,9 +573,25 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
     site_model: "locus" (the GTR model above), or a fixed model without stage 1 that runs the engine's F81 kernel:
     "jc" (Jukes-Cantor: pi = 1/4, exchangeabilities 1) or "f81" (the loci's empirical pi, exchangeabilities 1); exch and pi
     must then be None.
+    rate_estimator: "ml" (each column's maximum-likelihood rate) or "eb" (empirical Bayes under a discrete-gamma prior fitted
+    per locus, tapir_amd/eb.py; eb_options: dict(categories, alpha or None, alpha_bounds)); under "eb" the `.rates` documents
+    carry the fit and a posterior sd per site, everything downstream of the rates is the same code.
     pool: a HostPool created before the process touched the GPU (parallel parsing and .rates writing), or None."""
     if site_model not in ("locus", "jc", "f81"):
         raise PipelineError("unknown site model %r" % (site_model,))
+    if rate_estimator not in ("ml", "eb"):
+        raise PipelineError("unknown rate estimator %r" % (rate_estimator,))
+    if rate_estimator == "eb":
+        from . import eb as _eb
+        eb_options = dict(eb_options or {})
+        eb_options.setdefault("categories", _eb.DEFAULT_CATEGORIES)
+        if not _eb.MIN_CATEGORIES <= int(eb_options["categories"]) <= _eb.MAX_CATEGORIES:
+            raise PipelineError("the empirical-Bayes prior takes 2..16 categories")
+        if cat_rates is not None and len(cat_rates) > 1:
+            raise PipelineError("the empirical-Bayes estimator has its own prior: it cannot run on top of the rate mixture")
+    else:
+        if eb_options is not None:
+            raise PipelineError("eb_options need rate_estimator='eb'")
     fixed = site_model != "locus"
     if fixed and (exch is not None or pi is not None):
         raise PipelineError("site model %s fixes the exchangeabilities and base frequencies" % site_model)
@@ -540,12 +623,12 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
             pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
         return _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction,
                              threshold, pi, output_dir, device, integ_mode, round_decimals, extra, pool, progress, table_sink,
-                             timings, lap, site_model=site_model)
+                             timings, lap, site_model=site_model, eb_options=eb_options)
     if fixed:
         pi = _fixed_model_pi(eng, site_model, states, offsets, device)
         lap("base_frequencies")
         out = _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                        round_decimals, integ_mode, device, extra, pi, None, need_subset, pinned, model="f81")
+                        round_decimals, integ_mode, device, extra, pi, None, need_subset, pinned, eb_options=eb_options, model="f81")
         lap("site_rates_and_pi_incl_pcie")
         exch = np.ones((L, 6))
         return _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction,
@@ -564,7 +647,7 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
     if exch.ndim == 1:
         exch = np.tile(exch, (L, 1))
     out = _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                    round_decimals, integ_mode, device, extra, pi, exch, need_subset, pinned)
+                    round_decimals, integ_mode, device, extra, pi, exch, need_subset, pinned, eb_options=eb_options)
     lap("site_rates_and_pi_incl_pcie")
     return _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
                    round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool, progress, during_write,
@@ -572,12 +655,14 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
 
 
 def _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold, round_decimals,
-              integ_mode, device, extra, pi, exch, need_subset, pinned, **model):
+              integ_mode, device, extra, pi, exch, need_subset, pinned, eb_options=None, **model):
     """One plan over the whole batch: per-site rates, and the PI tables unless a subset needs its own."""
     plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, times, intervals,
                     correction=correction, threshold=threshold, round_decimals=round_decimals,
                     integ_mode=integ_mode, device=device, **extra, **model)
     try:
+        if eb_options is not None:
+            return _eb_rates(plan, states, offsets, parent, blen, leaf, eb_options, tables=not need_subset)
         if need_subset:
             return plan.site_rates(states)
         return plan.run_fused(states, pinned=True) if pinned else plan.run_fused(states)
@@ -590,6 +675,7 @@ def _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, ti
             timings, lap):
     """Rounding, culling, the `.rates` files and the worker()-shaped tuples of run_alignments."""
     L = len(alignments)
+    ebfit = out.get("eb")   # the per-locus fits of an empirical-Bayes run (None: maximum-likelihood rates)
     # what tapir would have after parse_site_rates + cull (bin/tapir_compute.py:100-102)
     rate4 = compute.round_like_hyphy(out["rate"], round_decimals) if round_decimals >= 0 else out["rate"]
     corrected = rate4 / correction
@@ -612,10 +698,14 @@ def _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, ti
             os.close(fd)
             side = None
             try:
-                arr = np.memmap(shared, dtype=np.float64, mode="w+", shape=(4, max(total, 1)))
+                arr = np.memmap(shared, dtype=np.float64, mode="w+", shape=(4 if ebfit is None else 5, max(total, 1)))
                 arr[0, :total], arr[1, :total], arr[2, :total], arr[3, :total] = out["subst"], rate4, out["lnl"], corrected
+                if ebfit is not None:
+                    arr[4, :total] = out["sd"]
                 arr.flush()
                 jobs = [(paths[l], shared, max(total, 1), int(offsets[l]), int(offsets[l + 1]), pi[l], exch[l]) for l in range(L)]
+                if ebfit is not None:
+                    jobs = [job + (_eb_meta(ebfit, l),) for l, job in enumerate(jobs)]
                 if during_write is not None and not need_subset:
                     side = _SideThread(during_write, lambda: _tuples(alignments, per_locus, out["tables"], T, times, intervals))
                 pool.write_rates(jobs, progress)
@@ -628,6 +718,12 @@ def _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, ti
         else:
             for l in range(L):
                 sl = slice(offsets[l], offsets[l + 1])
+                if ebfit is not None:
+                    _write_rates_file(paths[l], pi[l], exch[l], out["subst"][sl], rate4[sl], out["lnl"][sl], corrected[sl],
+                                      sd=out["sd"][sl], eb=_eb_meta(ebfit, l))
+                    if progress:
+                        progress()
+                    continue
                 _write_rates_file(paths[l], pi[l], exch[l], out["subst"][sl], rate4[sl], out["lnl"][sl], corrected[sl])
                 if progress:
                     progress()
