@@ -41,28 +41,22 @@ struct ClassifyParams {
     uint8_t* flag;
     int32_t* nres;
     double chrono_length;
-    const TreeOp* ops;            // the tree program: tips are visited in its order, and its PUSH / POP_MUL structure
-    int32_t nops;                 // drives the parsimony pass that seeds the optimiser (ColumnScan::fitch_*)
+    // the tree program as the parsimony pass sees it (TreeProgram::cls_steps, built once per plan): per tip k in program
+    // order {alignment row, ctl}, ctl = (stack pops before the tip << 1) | (push before the tip); padded to a multiple of 8
+    const int2* steps;
+    int32_t tail_pops;            // pops after the last tip
+    int32_t max_pops;             // most pops before one tip
     uint32_t* packed;             // [ceil(ntaxa/8)][ncols_total] out: 8 four-bit masks per word, program tip order
-    const int32_t* tip_taxon;     // [ntaxa] alignment row of the k-th tip of the program
     double start_scale;           // 1: start at the parsimony rate; 0: at HyPhy's siteRate = 1 (bf:1050), TPHIP_START_*
     uint64_t* hash;               // [ncols_total] out (may be null): hash of the column's packed words, for the
                                   // per-pattern de-duplication of the site-rate stage (pattern_kernels.hpp)
 };
 
-// Scalar loads of wave-uniform table entries.  classify_kernel also stores, so through plain pointers the compiler
-// cannot prove the tables invariant and fetches them with vector loads (one memory round trip per op, per lane).
-__device__ __forceinline__ int32_t scalar_load_i32(const int32_t* p) {   // p must be wave-uniform
-    int32_t r;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p));
-    return r;
-}
-typedef int SI8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ SI8 scalar_load_i32x8(const int32_t* p) {     // p wave-uniform and 32-byte aligned
-    SI8 r;
-    asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p));
-    return r;
-}
+// The step table through the constant address space: classify_kernel also stores, so through a plain pointer the
+// compiler cannot prove the table invariant and fetches it with vector loads.  As constant memory its wave-uniform
+// entries come in with scalar loads that the compiler is free to issue early and batch (no wait per entry).
+typedef const __attribute__((address_space(4))) int2 ConstInt2;
+__device__ __forceinline__ ConstInt2* as_constant(const int2* p) { return (ConstInt2*)(uintptr_t)p; }
 
 // Per-column bookkeeping of classify_kernel, as its finishing code reads it.
 struct ColumnScan {
@@ -86,7 +80,6 @@ struct ColumnScan4 {
     uint32_t res8 = 0, inf8 = 0, chg8 = 0;            // byte counters since the last flush
     uint32_t a8 = 0, c8 = 0, g8 = 0;                  // ... of the plain A / C / G cells
     int base[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-    uint32_t word[4] = {0, 0, 0, 0};
     uint64_t hsh[4] = {0x243F6A8885A308D3ull, 0x243F6A8885A308D3ull, 0x243F6A8885A308D3ull, 0x243F6A8885A308D3ull};
     int resolved[4] = {0, 0, 0, 0}, informative[4] = {0, 0, 0, 0};
     unsigned changes[4] = {0, 0, 0, 0};
@@ -94,7 +87,13 @@ struct ColumnScan4 {
     // 0x01 in every byte whose low nibble (the only bits set) is nonzero / equals 15
     static __device__ __forceinline__ uint32_t nonzero(uint32_t x) { return ((x + k0f) >> 4) & k01; }
     static __device__ __forceinline__ uint32_t is15(uint32_t x) { return ((x + k01) >> 4) & k01; }
-    static __device__ __forceinline__ uint32_t spread(uint32_t b) { return (b << 4) - b; }   // 0x01 -> 0x0f per byte
+    // 0x01 -> 0x0f per byte.  The empty asm keeps the shift opaque: folded, (b << 4) - b becomes b * 15, a quarter-rate
+    // v_mul_lo_u32 (three per tip)
+    static __device__ __forceinline__ uint32_t spread(uint32_t b) {
+        uint32_t s = b << 4;
+        asm("" : "+v"(s));
+        return s - b;
+    }
     __device__ __forceinline__ void flush() {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -125,8 +124,8 @@ struct ColumnScan4 {
         for (int j = 0; j < 4; ++j) { x4 |= (uint32_t)(stk[j] & 15ull) << (8 * j); stk[j] >>= 4; }
         fitch_join(x4);
     }
-    // v: the state bytes of tip number k (program order) for the four columns
-    __device__ __forceinline__ void tip(uint32_t v, int k) {
+    // v: the state bytes of the next tip (program order) for the four columns; returns its four masks (one per byte)
+    __device__ __forceinline__ uint32_t tip(uint32_t v) {
         uint32_t m4 = v & k0f;
         m4 |= spread(nonzero(m4) ^ k01);              // code 0 (nothing allowed) reads as "anything": 15
         const uint32_t res = is15(m4) ^ k01;          // resolved: not a gap / ? / N
@@ -137,10 +136,22 @@ struct ColumnScan4 {
         a8 += single & m4;                            // ... and it is bit 0 / 1 / 2 (the neighbour byte's bit that a shift
         c8 += single & (m4 >> 1);                     // brings into bit 7 is masked away by `single`)
         g8 += single & (m4 >> 2);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) word[j] |= ((m4 >> (8 * j)) & 15u) << (4 * (k & 7));
         fitch_join(m4);
-        if ((k & 63) == 63) flush();   // <= 64 tip joins + <= 64 + 16 sibling joins per window: no byte overflows
+        return m4;
+    }
+    // The packed tip words of eight tips: word[j] nibble i = byte j of m[i].  Pairs of tips first share a byte
+    // (a01 byte j = m[0] nibble | m[1] nibble << 4), then a 4 x 4 byte transpose in eight byte permutes.
+    static __device__ __forceinline__ void pack8(const uint32_t* m, uint32_t* word) {
+        const uint32_t a01 = m[0] | (m[1] << 4), a23 = m[2] | (m[3] << 4), a45 = m[4] | (m[5] << 4), a67 = m[6] | (m[7] << 4);
+        // __builtin_amdgcn_perm(hi, lo, sel): byte n of the result = byte sel_n of the 8-byte value hi:lo
+        const uint32_t t_lo = __builtin_amdgcn_perm(a23, a01, 0x05010400u);   // a01.b0 a23.b0 a01.b1 a23.b1
+        const uint32_t t_hi = __builtin_amdgcn_perm(a23, a01, 0x07030602u);   // a01.b2 a23.b2 a01.b3 a23.b3
+        const uint32_t u_lo = __builtin_amdgcn_perm(a67, a45, 0x05010400u);
+        const uint32_t u_hi = __builtin_amdgcn_perm(a67, a45, 0x07030602u);
+        word[0] = __builtin_amdgcn_perm(u_lo, t_lo, 0x05040100u);   // a01.b0 a23.b0 a45.b0 a67.b0
+        word[1] = __builtin_amdgcn_perm(u_lo, t_lo, 0x07060302u);
+        word[2] = __builtin_amdgcn_perm(u_hi, t_hi, 0x05040100u);
+        word[3] = __builtin_amdgcn_perm(u_hi, t_hi, 0x07060302u);
     }
     __device__ __forceinline__ ColumnScan column(int j) const {   // after flush()
         ColumnScan c;
@@ -235,6 +246,89 @@ __device__ __forceinline__ void classify_finish(const ClassifyParams& P, const L
     }
 }
 
+// The tip loop of classify_kernel, one instance per access kind (kFast: aligned dword loads and 16-byte stores; the
+// byte path's per-column conditions would otherwise sit between every load and its use) and, for the trees that allow
+// it, with the pops before a tip written out (kPopsUnrolled: no inner loop).
+constexpr int kMaxUnrolledPops = 6;
+template <bool kFast, bool kPopsUnrolled>
+__device__ __forceinline__ void classify_scan(const ClassifyParams& P, int64_t c0, int n, ColumnScan4& c) {
+    ConstInt2* steps = as_constant(P.steps);
+    // the state dwords of the eight tips of group g (missing columns of a ragged thread read as gaps)
+    auto load_group = [&](int g, uint32_t* buf) {
+        const uint8_t* row[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) row[i] = P.states + (int64_t)steps[8 * g + i].x * P.ncols_total + c0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (kFast) {
+                buf[i] = *reinterpret_cast<const uint32_t*>(row[i]);
+            } else {
+                uint32_t w = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (j < n) w |= (uint32_t)row[i][j] << (8 * j);
+                buf[i] = w;
+            }
+        }
+    };
+    // Tips go in groups of eight, written out in full so that a tip's state dword is a fixed register (no select chain
+    // on the tip index).  The next group's dwords are requested before this group is worked on.  (steps is padded to
+    // a multiple of 8.)
+    auto group = [&](int g, const uint32_t* cur) {
+        uint32_t m[8];
+        int ctl[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ctl[i] = steps[8 * g + i].y;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            m[i] = 0;
+            if (8 * g + i < P.ntaxa) {   // wave-uniform: only the last group can be partial
+                const int np = ctl[i] >> 1;
+                if (kPopsUnrolled) {   // the plan saw at most kMaxUnrolledPops between two tips: no inner loop
+#pragma unroll
+                    for (int q = 0; q < kMaxUnrolledPops; ++q) if (q < np) c.fitch_pop();
+                } else {
+                    for (int q = np; q > 0; --q) c.fitch_pop();
+                }
+                if (ctl[i] & 1) c.fitch_push();
+                m[i] = c.tip(cur[i]);
+            }
+        }
+        if ((g & 7) == 7) c.flush();   // after every 64th tip: <= 64 tip joins + <= 64 + 16 sibling joins per window, no byte overflows
+        uint32_t word[4];
+        ColumnScan4::pack8(m, word);
+        if (kFast) {
+            *reinterpret_cast<uint4*>(P.packed + (int64_t)g * P.ncols_total + c0) = make_uint4(word[0], word[1], word[2], word[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (j < n) P.packed[(int64_t)g * P.ncols_total + c0 + j] = word[j];
+        }
+        if (P.hash) {   // wave-uniform
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint64_t h = (c.hsh[j] ^ word[j]) * 0x9E3779B97F4A7C15ull;
+                c.hsh[j] = h ^ (h >> 29);
+            }
+        }
+    };
+    // two buffers, two groups per trip: no register copies between a load and its use
+    const int ngroups = (P.ntaxa + 7) >> 3;
+    uint32_t b0[8], b1[8];
+    load_group(0, b0);
+    // (the empty asm statements pin the loads ahead of the group they overlap: the scheduler would otherwise sink them
+    // down to their first use)
+    int g = 0;
+    for (; g + 1 < ngroups; g += 2) {
+        load_group(g + 1, b1);
+        asm volatile("" ::: "memory");
+        group(g, b0);
+        if (g + 2 < ngroups) load_group(g + 2, b0);
+        asm volatile("" ::: "memory");
+        group(g + 1, b1);
+    }
+    if (g < ngroups) group(g, b0);
+    for (int q = P.tail_pops; q > 0; --q) c.fitch_pop();
+}
+
 // HBM-bound byte kernel.  Each thread owns 4 CONSECUTIVE columns: when the row addresses are 4-byte aligned
 // (alignment of the states pointer, of ncols_total and of the locus offset: true for every BASELINE shape) a taxon
 // row is read as one dword per lane (256 B per wave instruction instead of 64), the packed tip words and the
@@ -253,56 +347,11 @@ __global__ __launch_bounds__(kPiBlock) void classify_kernel(ClassifyParams P) {
     const int n = full ? 4 : (int)(hi - c0);
     const bool fast = __all(aligned);   // wave-uniform: only the last wave of a locus can have a ragged thread
     ColumnScan4 c;
-    uint32_t buf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int k = 0;
-    for (int ip = 0; ip < P.nops; ++ip) {
-        const int code = scalar_load_i32(&P.ops[ip].code);
-        if (code == OP_PUSH) { c.fitch_push(); continue; }
-        if (code == OP_POP_MUL) { c.fitch_pop(); continue; }
-        if (code == OP_BRANCH) continue;
-        // The state dwords of eight tips are requested together when the first of them comes up: fetched one tip
-        // at a time (address from the op just read, value needed at once) every tip cost a full memory round trip
-        // and the kernel ran at 1.2 TB/s whatever its arithmetic.  (tip_taxon is padded to a multiple of 8.)
-        if ((k & 7) == 0) {
-            const SI8 tx = scalar_load_i32x8(P.tip_taxon + k);
-            const int t8[8] = {tx.s0, tx.s1, tx.s2, tx.s3, tx.s4, tx.s5, tx.s6, tx.s7};
-            if (fast) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    buf[i] = *reinterpret_cast<const uint32_t*>(P.states + (int64_t)t8[i] * P.ncols_total + c0);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const uint8_t* row = P.states + (int64_t)t8[i] * P.ncols_total + c0;
-                    uint32_t w = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) if (j < n) w |= (uint32_t)row[j] << (8 * j);   // missing columns read as gaps
-                    buf[i] = w;
-                }
-            }
-        }
-        uint32_t v = buf[0];
-#pragma unroll
-        for (int i = 1; i < 8; ++i) v = ((k & 7) == i) ? buf[i] : v;   // k is wave-uniform: scalar compares
-        c.tip(v, k);
-        if ((k & 7) == 7 || k == P.ntaxa - 1) {
-            if (fast) {
-                *reinterpret_cast<uint4*>(P.packed + (int64_t)(k >> 3) * P.ncols_total + c0) = make_uint4(c.word[0], c.word[1], c.word[2], c.word[3]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) if (j < n) P.packed[(int64_t)(k >> 3) * P.ncols_total + c0 + j] = c.word[j];
-            }
-            if (P.hash) {   // wave-uniform
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uint64_t h = (c.hsh[j] ^ c.word[j]) * 0x9E3779B97F4A7C15ull;
-                    c.hsh[j] = h ^ (h >> 29);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c.word[j] = 0;
-        }
-        ++k;
+    if (fast) {
+        if (P.max_pops <= kMaxUnrolledPops) classify_scan<true, true>(P, c0, n, c);
+        else classify_scan<true, false>(P, c0, n, c);
+    } else {
+        classify_scan<false, false>(P, c0, n, c);
     }
     c.flush();
     uint8_t f[4] = {0, 0, 0, 0};
@@ -551,8 +600,13 @@ __global__ __launch_bounds__(kPiBlock) void pi_partial_kernel(PiParams P) {
     }
 }
 
-// tables[l] = [net(T) | disc(n_t) | integral(n_i) | error(n_i)], summing the locus' chunks in order.
-__global__ void pi_reduce_kernel(const double* __restrict__ partial, const int64_t* __restrict__ locus_chunk_offsets,
+// tables[l] = [net(T) | disc(n_t) | integral(n_i) | error(n_i)], summing the locus' chunks in order.  A thread's sum
+// is a chain of dependent adds whose operands are independent loads: they are requested eight at a time, so the chain
+// waits for one memory round trip per eight chunks instead of one per chunk (the order of the adds is unchanged).
+// 64 threads: with 128 (one thread per entry on the C2-C5 rows) site_rate_kernel of the next pass ran 22 % slower on C2
+// (0.36 -> 0.45 ms at the same evaluation count), the front-of-kernel effect noted at dedup_estimate_kernel
+constexpr int kPiReduceBlock = 64;
+__global__ __launch_bounds__(kPiReduceBlock) void pi_reduce_kernel(const double* __restrict__ partial, const int64_t* __restrict__ locus_chunk_offsets,
                                  int32_t T, const int32_t* __restrict__ times, int32_t n_t, int32_t n_i,
                                  double* __restrict__ tables) {
     const int locus = blockIdx.x;
@@ -563,7 +617,15 @@ __global__ void pi_reduce_kernel(const double* __restrict__ partial, const int64
         // w < Wp: a partial column; else a --times entry, which is net[times[k]] (tapir/compute.py:76-79)
         const int src = (w < Wp) ? w : times[w - Wp];
         double s = 0.0;
-        for (int64_t c = c0; c < c1; ++c) s += partial[(size_t)c * Wp + src];
+        int64_t c = c0;
+        for (; c + 8 <= c1; c += 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = partial[(size_t)(c + u) * Wp + src];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += v[u];
+        }
+        for (; c < c1; ++c) s += partial[(size_t)c * Wp + src];
         const int dst = (w < T) ? w : (w < Wp ? w + n_t : T + (w - Wp));
         row[dst] = s;
     }

@@ -48,7 +48,7 @@ int tphip_plan_destroy(tphip_plan* plan) {
     plan->d_ops.release(); plan->d_fused_ops.release(); plan->d_models.release(); plan->d_offsets.release();
     plan->d_locus_pichunk_offsets.release(); plan->d_site_chunk_locus.release(); plan->d_site_chunk_index.release();
     plan->d_pi_chunk_locus.release(); plan->d_pi_chunk_index.release(); plan->d_times.release();
-    plan->d_intervals.release(); plan->d_evals.release(); plan->d_tip_taxon.release(); plan->d_op_node.release();
+    plan->d_intervals.release(); plan->d_evals.release(); plan->d_tip_taxon.release(); plan->d_op_node.release(); plan->d_cls_steps.release();
     plan->d_lik_ops.release();
     plan->d_value_ops.release();
     plan->d_value_tip_node.release();
@@ -316,8 +316,9 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     std::vector<int32_t> tip_taxon;
     for (const TreeOp& op : p->prog.ops) if (op.code <= OP_TIP_MUL) tip_taxon.push_back(op.taxon);
     p->nwords = (int32_t)((tip_taxon.size() + 7) / 8);
-    while (tip_taxon.size() % 8) tip_taxon.push_back(tip_taxon.back());   // classify_kernel reads it eight at a time
+    while (tip_taxon.size() % 8) tip_taxon.push_back(tip_taxon.back());   // read eight at a time
     if (e == hipSuccess) e = p->d_tip_taxon.upload(tip_taxon);
+    if (e == hipSuccess) e = p->d_cls_steps.upload(p->prog.cls_steps);
     if (e == hipSuccess) e = p->d_op_node.upload(p->prog.op_node);
     if (e == hipSuccess && !cat.empty()) e = p->d_cat.upload(cat);
     if (e == hipSuccess) {
@@ -679,9 +680,8 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
     C.locus_offsets = p->d_offsets.p; C.chunk_locus = p->d_pi_chunk_locus.p; C.chunk_index = p->d_pi_chunk_index.p;
     C.rate = d_rate; C.subst = d_subst; C.lnl = d_lnl; C.flag = d_flag; C.nres = d_nres;
     C.chrono_length = p->prog.chrono_length;
-    C.ops = p->d_ops.p; C.nops = (int32_t)p->prog.ops.size();
+    C.steps = (const int2*)p->d_cls_steps.p; C.tail_pops = p->prog.cls_tail_pops; C.max_pops = p->prog.cls_max_pops;
     C.packed = (uint32_t*)((char*)ws + p->ws_packed);
-    C.tip_taxon = p->d_tip_taxon.p;
     C.start_scale = (p->start_rule == TPHIP_START_REFERENCE) ? 0.0 : 1.0;
     const bool dedup = p->dedup_mode != DEDUP_OFF && p->n_pi_chunks > 0;
     C.hash = dedup ? (uint64_t*)((char*)ws + p->ws_hash) : nullptr;
@@ -785,9 +785,8 @@ int tphip_internal_eb_prepare(tphip_plan* p, const uint8_t* d_states, const EbPr
     C.locus_offsets = p->d_offsets.p; C.chunk_locus = p->d_pi_chunk_locus.p; C.chunk_index = p->d_pi_chunk_index.p;
     C.rate = B->scratch[0]; C.subst = B->scratch[1]; C.lnl = B->scratch[2]; C.flag = B->flag; C.nres = B->nres;
     C.chrono_length = p->prog.chrono_length;
-    C.ops = p->d_ops.p; C.nops = (int32_t)p->prog.ops.size();
+    C.steps = (const int2*)p->d_cls_steps.p; C.tail_pops = p->prog.cls_tail_pops; C.max_pops = p->prog.cls_max_pops;
     C.packed = B->packed;
-    C.tip_taxon = p->d_tip_taxon.p;
     C.start_scale = 1.0;
     C.hash = use_patterns ? B->hash : nullptr;
     classify_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(kPiBlock), 0, st>>>(C);
@@ -818,7 +817,7 @@ static int launch_pi_tables(tphip_plan* p, const double* d_rates, const int32_t*
     PiParams Q = pi_params(p, d_rates, d_nres, ws);
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 2], st));
     if (p->n_pi_chunks > 0) pi_partial_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(kPiBlock), 0, st>>>(Q);
-    pi_reduce_kernel<<<dim3((unsigned)p->nloci), dim3(64), 0, st>>>(Q.partial, p->d_locus_pichunk_offsets.p, p->T,
+    pi_reduce_kernel<<<dim3((unsigned)p->nloci), dim3(kPiReduceBlock), 0, st>>>(Q.partial, p->d_locus_pichunk_offsets.p, p->T,
                                                                    p->d_times.p, p->n_t, p->n_i, d_tables);
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 3], st));
     HIP_TRY(hipGetLastError());

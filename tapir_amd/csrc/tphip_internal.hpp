@@ -96,6 +96,7 @@ struct tphip_plan {
     DevBuf<LocusModel> d_models;
     DevBuf<int64_t> d_offsets, d_locus_pichunk_offsets;
     DevBuf<int32_t> d_tip_taxon, d_op_node;
+    DevBuf<int32_t> d_cls_steps;   // TreeProgram::cls_steps, read as int2 by classify_kernel
     // launch configuration of the locus likelihood / gradient kernels, fixed at plan creation: LDS bytes, whether the
     // gradient kernel stages its state masks, resident gradient blocks per CU
     size_t lik_lds = 0, grad_lds = 0;

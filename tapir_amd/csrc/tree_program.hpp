@@ -48,6 +48,13 @@ struct TreeProgram {
     std::vector<int32_t> op_tape;     // reverse-mode tape slot written by a BRANCH / PUSH op (-1 otherwise)
     std::vector<int32_t> op_partner;  // POP_MUL: tape slot of the PUSH it pops (-1 otherwise)
     int32_t ntape = 0;
+    // The program as the parsimony pass of classify_kernel sees it (BRANCH ops do nothing there): per tip in program
+    // order {taxon, (pops before it << 1) | push before it}, padded with {last taxon, 0} to a multiple of 8 tips; the
+    // pops that follow the last tip in cls_tail_pops.  Between two tips the program only ever finishes subtrees
+    // (BRANCH, POP_MUL) and then enters at most one new sibling subtree (one PUSH before its first tip).
+    std::vector<int32_t> cls_steps;
+    int32_t cls_tail_pops = 0;
+    int32_t cls_max_pops = 0;   // most pops before one tip
     int32_t stack_depth = 0;   // LDS slots per lane
     double chrono_length = 0;  // sum of all branch lengths (bf:1006-1013)
     int32_t nleaves = 0;
@@ -154,6 +161,29 @@ inline std::string build_tree_program(int32_t ntaxa, int32_t nnodes, const int32
         }
     }
     if (!pushed.empty()) return "internal error: unbalanced PUSH";
+    out->cls_steps.clear();
+    out->cls_max_pops = 0;
+    int32_t pops = 0, push = 0;
+    for (const TreeOp& op : out->ops) {
+        if (op.code == OP_PUSH) {
+            if (push) return "internal error: two PUSH ops between tips";
+            push = 1;
+        } else if (op.code == OP_POP_MUL) {
+            if (push) return "internal error: POP_MUL after a PUSH between tips";
+            ++pops;
+        } else if (op.code == OP_TIP_SET || op.code == OP_TIP_MUL) {
+            out->cls_steps.push_back(op.taxon);
+            out->cls_steps.push_back(pops * 2 + push);
+            out->cls_max_pops = std::max(out->cls_max_pops, pops);
+            pops = push = 0;
+        }
+    }
+    if (push) return "internal error: PUSH after the last tip";
+    out->cls_tail_pops = pops;
+    while (out->cls_steps.size() % 16) {
+        out->cls_steps.push_back(out->cls_steps[out->cls_steps.size() - 2]);
+        out->cls_steps.push_back(0);
+    }
     out->fused_ops.clear();
     int32_t pending = 0;
     for (size_t i = 0; i < out->ops.size(); ++i) {
