@@ -416,6 +416,64 @@ int tphip_eb_posterior_dev(tphip_plan *plan, const uint8_t *d_states, const tphi
                            const double *cat_weight, const double *scale, double *d_rate, double *d_rate_sd,
                            double *d_lnl, int32_t *d_nres, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Site bootstrap of the per-locus PI rows (an extension: the reference reports the rows without an error bar).
+ * A column's final rate depends on the column and the locus' model only, so an alignment resampled with replacement has
+ * the same per-site rates with multiplicities.  Replicate b of locus l draws n_l column indices with replacement from all
+ * n_l columns of the locus (culled ones included); with c[b][i] the counts and p_i[w] site i's values -- 16 r^2 t e^(-4rt)
+ * at t = 0..T-1, then the integral over each of the n_i intervals, by the device functions of the PI tables under the
+ * plan's integ_mode; all zero for a NaN (culled) or zero rate -- the replicate row is X_b[w] = sum_i c[b][i] p_i[w],
+ * w < Wb = T + n_i.  The sum(error) columns are not resampled and the --times entries are net[times[k]], left to the
+ * caller.  The locus' model (and an empirical-Bayes prior) are held fixed: the bands are conditional on the fitted model.
+ * Inputs are those of tphip_pi_tables: raw rates and an optional nres, finalised by the plan's rounding, correction, cull.
+ *
+ * Generator: Philox4x32-10 (Salmon et al. 2011), key = (seed & 0xffffffff, seed >> 32), counter = (j, b, locus_id &
+ * 0xffffffff, locus_id >> 32); the output words (x0, x1, x2, x3) give draw 2j = ((x1 * 2^32 + x0) * n_l) >> 64 and draw
+ * 2j + 1 likewise from (x3, x2), j = 0 .. ceil(n_l / 2) - 1; the last draw of an odd n_l is discarded.  Counts are 16-bit.
+ *
+ * Determinism: the replicate rows of a locus depend on seed, locus id, b, the locus' final rates and the schedule only --
+ * not on the other loci of the plan, on the number of replicates, on the workspace size or on how a batch is sharded.
+ *
+ * Summary per locus and entry w over the B replicates, layout [L][4][Wb]: mean, sd (B - 1 in the denominator, two-pass),
+ * lo and hi = the quantiles at (1 - level) / 2 and 1 - (1 - level) / 2 by numpy's default (linear) rule.
+ * Calls on one plan must not overlap. */
+typedef struct tphip_bootstrap_opts {
+    uint32_t struct_size;      /* sizeof(tphip_bootstrap_opts) of the caller */
+    int32_t replicates;        /* B, 2..4096 */
+    double level;              /* coverage of [lo, hi], in (0, 1) */
+    uint64_t seed;
+    const int64_t *locus_ids;  /* HOST [nloci] stream id per locus, NULL = the plan's locus index 0..L-1; read before the
+                                  call returns */
+} tphip_bootstrap_opts;
+
+/* Wb = T + n_i */
+int32_t tphip_bootstrap_width(const tphip_plan *plan);
+/* Device workspace of tphip_pi_bootstrap_dev: any size >= *min_bytes works and gives the same bits (the library blocks over
+ * loci and, for a locus too long for the workspace, over replicate ranges); *preferred_bytes (<= about 1 GiB, or the
+ * minimum) lets it take more loci per block.  opts = NULL sizes the workspace of tphip_pi_resample_dev instead, which holds
+ * per-site integrals only and does not depend on nrep (a bootstrap workspace is always large enough for it too). */
+int tphip_bootstrap_workspace_bytes(const tphip_plan *plan, const tphip_bootstrap_opts *opts, size_t *min_bytes,
+                                    size_t *preferred_bytes);
+/* The weighted-sum core on caller-supplied counts (jackknife, delete-half, site weighting): d_counts is uint16
+ * [nrep][ncols] over the plan's columns, d_rows [nloci][nrep][Wb].  Enqueues on `stream`, does not synchronise. */
+int tphip_pi_resample_dev(tphip_plan *plan, const double *d_rates, const int32_t *d_nres, const uint16_t *d_counts,
+                          int32_t nrep, double *d_rows, void *d_workspace, size_t workspace_bytes, void *stream);
+/* Draws the counts, runs the core and summarises, block by block.  d_summary [nloci][4][Wb]; d_rows [nloci][B][Wb] or NULL.
+ * Enqueues on `stream` and does not synchronise when opts.locus_ids is NULL.  With locus_ids set the ids are copied to the
+ * device first and `stream` is synchronised once before any kernel is enqueued (the caller's array need not outlive the
+ * call): such a call blocks and cannot be captured into a graph. */
+int tphip_pi_bootstrap_dev(tphip_plan *plan, const double *d_rates, const int32_t *d_nres, const tphip_bootstrap_opts *opts,
+                           double *d_summary, double *d_rows, void *d_workspace, size_t workspace_bytes, void *stream);
+/* host-pointer twins: the library allocates its own workspace, as tphip_pi_tables does */
+int tphip_pi_resample(tphip_plan *plan, const double *rates, const int32_t *nres, const uint16_t *counts, int32_t nrep,
+                      double *rows);
+int tphip_pi_bootstrap(tphip_plan *plan, const double *rates, const int32_t *nres, const tphip_bootstrap_opts *opts,
+                       double *summary, double *rows);
+/* The draw kernel alone (host pointers, plan-less): counts_out uint16 [nrep][n] = the counts of replicates rep0 .. rep0 +
+ * nrep - 1 of a locus of n columns with stream id locus_id. */
+int tphip_bootstrap_counts(int32_t device, uint64_t seed, int64_t locus_id, int64_t n, int64_t rep0, int32_t nrep,
+                           uint16_t *counts_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@ Same positionals, same required/optional flags and defaults, same output directo
 (Tree_<factor>_<depth>.newick, <alignment>.rates JSON per locus, phylogenetic-informativeness.sqlite).
 `--hyphy` and `--template` are accepted for compatibility and ignored (there is no subprocess);
 `--multiprocessing` parallelises the host side only (NEXUS parsing, .rates files).  New, opt-in flags only: --device, --exchangeabilities / --subs-model,
---integral-mode, --full-precision-rates, --gamma-categories / --gamma-alpha, --site-model.
+--integral-mode, --full-precision-rates, --gamma-categories / --gamma-alpha, --site-model, --rate-estimator,
+--bootstrap / --bootstrap-seed / --bootstrap-level (site-bootstrap bands in a second file,
+phylogenetic-informativeness-bootstrap.sqlite; the other outputs stay byte for byte the same).
 
 Several GPUs: launch it with `python -m torch.distributed.run --nproc-per-node G bin/tapir_compute.py ...` (one process
 per GPU).  The files are dealt round-robin over the ranks (what `Pool.map(worker, params)` did over cores,
@@ -94,7 +96,29 @@ def get_args(argv=None):
                      help="fix the shape of the empirical-Bayes prior (default: estimated per locus); needs --rate-estimator eb")
     new.add_argument('--eb-alpha-bounds', type=_two_floats, default=None,
                      help="LO,HI: range in which the shape is estimated (default 0.2,50); needs --rate-estimator eb")
+    new.add_argument('--bootstrap', type=int, default=0, metavar='B',
+                     help="B in 2..4096: site bootstrap of every locus' PI profile and interval integrals with B resamples of "
+                          "its columns (the fitted model held fixed); mean, sd and a confidence band per entry go into "
+                          "phylogenetic-informativeness-bootstrap.sqlite.  0 = off")
+    new.add_argument('--bootstrap-seed', type=int, default=None, help="seed of the resampling (default 1); needs --bootstrap")
+    new.add_argument('--bootstrap-level', type=float, default=None,
+                     help="coverage of the band [lo, hi], in (0, 1) (default 0.95); needs --bootstrap")
     args = parser.parse_args(argv)
+    if args.bootstrap == 0:
+        for flag, value in (('--bootstrap-seed', args.bootstrap_seed), ('--bootstrap-level', args.bootstrap_level)):
+            if value is not None:
+                parser.error("{0} needs --bootstrap".format(flag))
+    else:
+        if not 2 <= args.bootstrap <= 4096:
+            parser.error("--bootstrap must be in 2..4096")
+        if args.bootstrap_seed is None:
+            args.bootstrap_seed = 1
+        if not 0 <= args.bootstrap_seed < 2 ** 64:
+            parser.error("--bootstrap-seed must be in 0..2^64-1")
+        if args.bootstrap_level is None:
+            args.bootstrap_level = 0.95
+        if not 0.0 < args.bootstrap_level < 1.0:
+            parser.error("--bootstrap-level must be in (0, 1)")
     if args.site_model != 'locus':
         for flag, given in (('--exchangeabilities', args.exchangeabilities is not None), ('--subs-model', bool(args.subs_model)),
                             ('--site-rates', args.site_rates)):
@@ -351,6 +375,22 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
         sys.stdout.write("DONE")
         sys.stdout.flush()
         print("\n")
+    if args.bootstrap:
+        # (after the main database is stored: a failure of this opt-in stage leaves a finished run's outputs in place)
+        # every rank resamples its own loci from their final rates; the generator's stream ids are the global file indices,
+        # so the bands do not depend on the world size.  The summaries travel like the PI rows.
+        eng = engine_mod
+        if eng is None:
+            from . import engine as eng
+        Wb = T + len(args.intervals)
+        ids = list(tdist.shard_loci(len(files), rank, world))
+        boot = pipeline.bootstrap_tables(eng, [p[1] for p in pis], leaf_names, parent, blen, leaf, T, args.intervals,
+                                         args.device, integ_mode, ids, args.bootstrap, args.bootstrap_seed, args.bootstrap_level)
+        all_boot = _gather_rows(boot.reshape(len(ids), 4 * Wb), len(files), rank, world, on_gpu)
+        if rank == 0:
+            db.write_bootstrap_db(os.path.join(args.output, 'phylogenetic-informativeness-bootstrap.sqlite'), files,
+                                  all_boot.reshape(len(files), 4, Wb), T, args.times, args.intervals, args.bootstrap,
+                                  args.bootstrap_seed, args.bootstrap_level)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -1,0 +1,345 @@
+// bootstrap_driver.hip -- site bootstrap of the per-locus PI rows: the C entry points
+// tphip_pi_resample / tphip_pi_bootstrap / tphip_bootstrap_counts and the blocking of loci and replicate ranges over the
+// caller's workspace.  The kernels are in bootstrap_kernels.hpp.
+//
+// A block is a run of consecutive loci whose counts [B][columns], per-site integrals [columns][n_i] and replicate rows
+// [loci][B][Wb] fit the workspace together; a locus too long for that is taken alone, its counts drawn and multiplied one
+// replicate range at a time.  A replicate row is computed by one wave from the locus' own columns in a fixed order
+// (bootstrap_matrix_kernel), so the blocking changes no bit of it.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+#include <vector>
+
+#include "bootstrap_kernels.hpp"
+#include "tphip_internal.hpp"
+
+namespace {
+
+constexpr size_t kBsAlign = 256;
+constexpr size_t kBsPreferredCap = (size_t)1 << 30;   // like stage 1's chunks: about 1 GiB of workspace at most
+constexpr int32_t kBsMaxResampleReps = 1 << 20;
+
+PiParams bs_pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres) {
+    PiParams Q;
+    Q.rates = d_rates; Q.nres = d_nres; Q.locus_offsets = p->d_offsets.p;
+    Q.chunk_locus = nullptr; Q.chunk_index = nullptr;
+    Q.T = p->T; Q.intervals = p->d_intervals.p; Q.n_i = p->n_i; Q.integ_mode = p->integ_mode;
+    Q.correction = p->correction; Q.threshold = p->threshold;
+    Q.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
+    Q.partial = nullptr;
+    return Q;
+}
+
+inline int32_t bs_width(const tphip_plan* p) { return p->T + p->n_i; }
+inline size_t bs_pitch(int64_t cols) { return (size_t)((cols + 1) & ~(int64_t)1); }   // 16-bit counters per row: whole words
+inline size_t bs_integ_bytes(const tphip_plan* p, int64_t cols) { return align_up(sizeof(double) * (size_t)cols * (size_t)p->n_i, kBsAlign); }
+inline size_t bs_counts_bytes(int64_t cols, int64_t reps) { return align_up(sizeof(uint16_t) * bs_pitch(cols) * (size_t)reps, kBsAlign); }
+inline size_t bs_rows_bytes(const tphip_plan* p, int64_t loci, int64_t reps) {
+    return align_up(sizeof(double) * (size_t)loci * (size_t)reps * (size_t)bs_width(p), kBsAlign);
+}
+inline size_t bs_ids_bytes(const tphip_plan* p) { return align_up(sizeof(int64_t) * (size_t)p->nloci, kBsAlign); }
+// replicates drawn together when a locus goes through the workspace in ranges: whole replicate tiles of the matrix kernel
+inline int64_t bs_min_range(int64_t B) { return std::min<int64_t>(B, kBsRepTile); }
+
+struct BsOpts {
+    int32_t replicates = 0;
+    double level = 0.0;
+    uint64_t seed = 0;
+    const int64_t* locus_ids = nullptr;
+};
+
+int bs_read_opts(const tphip_bootstrap_opts* o, BsOpts* out) {
+    if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_bootstrap_opts");
+    if (o->struct_size < offsetof(tphip_bootstrap_opts, seed) + sizeof(uint64_t))
+        return fail(TPHIP_ERR_INVALID, "tphip_bootstrap_opts.struct_size is too small: set it to sizeof(tphip_bootstrap_opts)");
+    out->replicates = o->replicates;
+    out->level = o->level;
+    out->seed = o->seed;
+    out->locus_ids = (o->struct_size >= offsetof(tphip_bootstrap_opts, locus_ids) + sizeof(const int64_t*)) ? o->locus_ids : nullptr;
+    if (out->replicates < 2 || out->replicates > kBsMaxReplicates)
+        return fail(TPHIP_ERR_INVALID, "bootstrap replicates must be in 2..4096");
+    if (!(out->level > 0.0 && out->level < 1.0)) return fail(TPHIP_ERR_INVALID, "bootstrap level must be in (0, 1)");
+    return TPHIP_OK;
+}
+
+void bs_workspace(const tphip_plan* p, int64_t B, size_t* min_bytes, size_t* preferred) {
+    size_t mn = 0;
+    for (int64_t l = 0; l < p->nloci; ++l) {
+        const int64_t n = p->h_offsets[l + 1] - p->h_offsets[l];
+        mn = std::max(mn, bs_integ_bytes(p, n) + bs_counts_bytes(n, bs_min_range(B)) + bs_rows_bytes(p, 1, B));
+    }
+    const size_t fixed = kBsAlign + bs_ids_bytes(p);
+    const size_t all = bs_integ_bytes(p, p->ncols) + bs_counts_bytes(p->ncols, B) + bs_rows_bytes(p, p->nloci, B);
+    *min_bytes = fixed + mn;
+    *preferred = fixed + std::max(mn, std::min(all, kBsPreferredCap));
+}
+
+// numpy.quantile's default rule for n sorted values: virtual index n q + (1 + q (1 - 1 - 1)) - 1 evaluated as numpy does,
+// lower neighbour = its floor, weight of the upper neighbour = the fractional part
+void bs_quantile_index(int32_t n, double q, int32_t* idx, double* frac) {
+    volatile double nq = (double)n * q;
+    volatile double inner = 1.0 + q * -1.0;
+    volatile double sum = nq + inner;
+    const double vi = sum - 1.0;
+    double fl = std::floor(vi);
+    if (fl < 0.0) { *idx = 0; *frac = 0.0; return; }
+    if (vi >= (double)(n - 1)) { *idx = n - 1; *frac = 0.0; return; }
+    *idx = (int32_t)fl;
+    *frac = vi - fl;
+}
+
+// integrals of the columns [c0, c1) into `integ`
+int bs_launch_integrals(const tphip_plan* p, const PiParams& Q, int64_t c0, int64_t c1, double* integ, hipStream_t st) {
+    if (c1 > c0 && p->n_i > 0) {
+        bootstrap_integrals_kernel<<<dim3((unsigned)((c1 - c0 + 127) / 128)), dim3(128), 0, st>>>(Q, c0, c1 - c0, integ);
+        HIP_TRY(hipGetLastError());
+    }
+    return TPHIP_OK;
+}
+
+// rows of the loci [l0, l1) for `nrep` replicates whose counts are counts[r * pitch + (column - col_base)]
+int bs_launch_matrix(const tphip_plan* p, const PiParams& Q, int64_t l0, int64_t l1, const uint16_t* counts, int64_t pitch,
+                     int64_t col_base, const double* integ, int64_t integ_col_base, double* rows, int64_t rows_reps,
+                     int64_t rows_rep0, int32_t nrep, hipStream_t st) {
+    const int32_t Wb = bs_width(p);
+    if (l1 <= l0 || nrep <= 0 || Wb <= 0) return TPHIP_OK;
+    BootMatParams M;
+    M.pi = Q; M.counts = counts; M.count_pitch = pitch; M.col_base = col_base;
+    M.integ = integ; M.integ_col_base = integ_col_base;
+    M.rows = rows; M.rows_reps = rows_reps; M.rows_rep0 = rows_rep0;
+    M.locus0 = (int32_t)l0; M.nrep = nrep; M.Tp = (p->T + 15) & ~15;
+    const int Wi = M.Tp + p->n_i;
+    bootstrap_matrix_kernel<<<dim3((unsigned)(l1 - l0), (unsigned)((nrep + kBsRepTile - 1) / kBsRepTile),
+                                   (unsigned)((Wi + kBsOutTile - 1) / kBsOutTile)), dim3(kBsBlock), 0, st>>>(M);
+    HIP_TRY(hipGetLastError());
+    return TPHIP_OK;
+}
+
+int bs_launch_draw(const int64_t* d_offsets, const int64_t* d_ids, int64_t single_n, int64_t single_id, int64_t l0, int64_t l1,
+                   int64_t max_cols, int64_t rep0, int32_t nrep, uint64_t seed, uint16_t* counts, int64_t pitch,
+                   int64_t col_base, hipStream_t st) {
+    if (l1 <= l0 || nrep <= 0 || max_cols <= 0) return TPHIP_OK;
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(uint16_t) * (size_t)pitch * (size_t)nrep, st));
+    DrawParams D;
+    D.locus_offsets = d_offsets; D.locus_ids = d_ids; D.single_n = single_n; D.single_id = single_id;
+    D.locus0 = (int32_t)l0; D.nrep = nrep; D.rep0 = rep0; D.seed = seed;
+    D.words = (uint32_t*)counts; D.pitch = pitch; D.col_base = col_base;
+    const int64_t calls = (max_cols + 1) / 2;
+    const int64_t gx = (l1 - l0) * (int64_t)nrep, gy = (calls + kBsDrawBlock - 1) / kBsDrawBlock;
+    if (gx > 0x7fffffffll || gy > 65535) return fail(TPHIP_ERR_INVALID, "bootstrap block too large for one launch");
+    bootstrap_draw_kernel<<<dim3((unsigned)gx, (unsigned)gy), dim3(kBsDrawBlock), 0, st>>>(D);
+    HIP_TRY(hipGetLastError());
+    return TPHIP_OK;
+}
+
+char* bs_ws_base(void* ws, size_t ws_bytes, size_t* usable) {
+    const uintptr_t a = (uintptr_t)ws, b = (a + kBsAlign - 1) / kBsAlign * kBsAlign;
+    *usable = ws_bytes > (size_t)(b - a) ? ws_bytes - (size_t)(b - a) : 0;
+    return (char*)b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t tphip_bootstrap_width(const tphip_plan* p) { return p ? bs_width(p) : 0; }
+
+int tphip_bootstrap_workspace_bytes(const tphip_plan* p, const tphip_bootstrap_opts* opts, size_t* min_bytes, size_t* preferred_bytes) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    size_t mn = 0, pf = 0;
+    if (!opts) {   // tphip_pi_resample_dev: the per-site integrals of the loci of a block, nothing that depends on nrep
+        mn = kBsAlign + bs_integ_bytes(p, p->max_locus_cols);
+        pf = kBsAlign + std::max(bs_integ_bytes(p, p->max_locus_cols), std::min(bs_integ_bytes(p, p->ncols), kBsPreferredCap));
+    } else {
+        BsOpts o;
+        int rc = bs_read_opts(opts, &o);
+        if (rc) return rc;
+        bs_workspace(p, o.replicates, &mn, &pf);
+    }
+    if (min_bytes) *min_bytes = mn;
+    if (preferred_bytes) *preferred_bytes = pf;
+    return TPHIP_OK;
+}
+
+int tphip_pi_resample_dev(tphip_plan* p, const double* d_rates, const int32_t* d_nres, const uint16_t* d_counts, int32_t nrep,
+                          double* d_rows, void* ws, size_t ws_bytes, void* stream) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    if (nrep < 1 || nrep > kBsMaxResampleReps) return fail(TPHIP_ERR_INVALID, "nrep must be in 1..2^20");
+    const int32_t Wb = bs_width(p);
+    if (p->nloci == 0 || Wb == 0) return TPHIP_OK;
+    if (!d_rows || (p->ncols && (!d_rates || !d_counts))) return fail(TPHIP_ERR_INVALID, "null device pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    size_t usable = 0;
+    char* base = ws ? bs_ws_base(ws, ws_bytes, &usable) : nullptr;
+    const PiParams Q = bs_pi_params(p, d_rates, d_nres);
+    // the workspace holds the per-site integrals only: consecutive loci as far as it reaches
+    int64_t l0 = 0;
+    while (l0 < p->nloci) {
+        int64_t l1 = l0;
+        while (l1 < p->nloci && (l1 == l0 || bs_integ_bytes(p, p->h_offsets[l1 + 1] - p->h_offsets[l0]) <= usable)) ++l1;
+        const int64_t c0 = p->h_offsets[l0], c1 = p->h_offsets[l1];
+        if (p->n_i > 0 && c1 > c0 && (!base || bs_integ_bytes(p, c1 - c0) > usable))
+            return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than the minimum of tphip_bootstrap_workspace_bytes()");
+        int rc = bs_launch_integrals(p, Q, c0, c1, (double*)base, st);
+        if (rc) return rc;
+        rc = bs_launch_matrix(p, Q, l0, l1, d_counts, p->ncols, 0, (const double*)base, c0,
+                              d_rows + (size_t)l0 * (size_t)nrep * (size_t)Wb, nrep, 0, nrep, st);
+        if (rc) return rc;
+        l0 = l1;
+    }
+    return TPHIP_OK;
+}
+
+int tphip_pi_bootstrap_dev(tphip_plan* p, const double* d_rates, const int32_t* d_nres, const tphip_bootstrap_opts* opts,
+                           double* d_summary, double* d_rows, void* ws, size_t ws_bytes, void* stream) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    BsOpts o;
+    int rc = bs_read_opts(opts, &o);
+    if (rc) return rc;
+    const int32_t Wb = bs_width(p), B = o.replicates;
+    if (p->nloci == 0 || Wb == 0) return TPHIP_OK;
+    if (!d_summary || !ws || (p->ncols && !d_rates)) return fail(TPHIP_ERR_INVALID, "null device pointer");
+    size_t mn = 0, pf = 0;
+    bs_workspace(p, B, &mn, &pf);
+    if (ws_bytes < mn) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than the minimum of tphip_bootstrap_workspace_bytes()");
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    size_t usable = 0;
+    char* base = bs_ws_base(ws, ws_bytes, &usable);
+    int64_t* d_ids = nullptr;
+    if (o.locus_ids) {
+        // read now: the caller's array need not outlive the call
+        d_ids = (int64_t*)base;
+        HIP_TRY(hipMemcpyAsync(d_ids, o.locus_ids, sizeof(int64_t) * (size_t)p->nloci, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    base += bs_ids_bytes(p);
+    usable -= bs_ids_bytes(p);
+    const PiParams Q = bs_pi_params(p, d_rates, d_nres);
+    SummaryParams S;
+    S.B = B; S.Wb = Wb;
+    S.npow2 = 2;
+    while (S.npow2 < B) S.npow2 <<= 1;
+    const double q_lo = (1.0 - o.level) / 2.0, q_hi = 1.0 - (1.0 - o.level) / 2.0;
+    bs_quantile_index(B, q_lo, &S.idx_lo, &S.frac_lo);
+    bs_quantile_index(B, q_hi, &S.idx_hi, &S.frac_hi);
+    int64_t l0 = 0;
+    while (l0 < p->nloci) {
+        // as many consecutive loci as fit with all B replicates' counts; a locus that does not fit alone goes in ranges
+        int64_t l1 = l0;
+        while (l1 < p->nloci) {
+            const int64_t n = p->h_offsets[l1 + 1] - p->h_offsets[l0];
+            if (l1 - l0 >= 65535 || bs_integ_bytes(p, n) + bs_counts_bytes(n, B) + bs_rows_bytes(p, l1 + 1 - l0, B) > usable) break;
+            ++l1;
+        }
+        int64_t range = B;
+        if (l1 == l0) {
+            l1 = l0 + 1;
+            const int64_t n = p->h_offsets[l1] - p->h_offsets[l0];
+            const size_t left = usable - bs_integ_bytes(p, n) - bs_rows_bytes(p, 1, B);   // >= one minimal range: ws_bytes >= mn
+            range = bs_min_range(B);
+            while (range + kBsRepTile <= B && bs_counts_bytes(n, range + kBsRepTile) <= left) range += kBsRepTile;
+        }
+        const int64_t c0 = p->h_offsets[l0], c1 = p->h_offsets[l1], n = c1 - c0;
+        int64_t max_cols = 0;
+        for (int64_t l = l0; l < l1; ++l) max_cols = std::max(max_cols, p->h_offsets[l + 1] - p->h_offsets[l]);
+        double* integ = (double*)base;
+        uint16_t* counts = (uint16_t*)(base + bs_integ_bytes(p, n));
+        double* ws_rows = (double*)(base + bs_integ_bytes(p, n) + bs_counts_bytes(n, range));
+        double* rows = d_rows ? d_rows + (size_t)l0 * (size_t)B * (size_t)Wb : ws_rows;
+        rc = bs_launch_integrals(p, Q, c0, c1, integ, st);
+        if (rc) return rc;
+        for (int64_t r0 = 0; r0 < B; r0 += range) {
+            const int32_t nr = (int32_t)std::min<int64_t>(range, B - r0);
+            rc = bs_launch_draw(p->d_offsets.p, d_ids, 0, 0, l0, l1, max_cols, r0, nr, o.seed, counts, (int64_t)bs_pitch(n), c0, st);
+            if (rc) return rc;
+            rc = bs_launch_matrix(p, Q, l0, l1, counts, (int64_t)bs_pitch(n), c0, integ, c0, rows, B, r0, nr, st);
+            if (rc) return rc;
+        }
+        S.rows = rows;
+        S.summary = d_summary + (size_t)l0 * 4 * (size_t)Wb;
+        bootstrap_summary_kernel<<<dim3((unsigned)((l1 - l0) * Wb)), dim3(256), 0, st>>>(S);
+        HIP_TRY(hipGetLastError());
+        l0 = l1;
+    }
+    return TPHIP_OK;
+}
+
+int tphip_pi_resample(tphip_plan* p, const double* rates, const int32_t* nres, const uint16_t* counts, int32_t nrep, double* rows) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    if (nrep < 1 || nrep > kBsMaxResampleReps) return fail(TPHIP_ERR_INVALID, "nrep must be in 1..2^20");
+    const size_t n = (size_t)p->ncols, Wb = (size_t)bs_width(p), nrows = (size_t)p->nloci * (size_t)nrep * Wb;
+    if (nrows == 0) return TPHIP_OK;
+    if (!rows || (n && (!rates || !counts))) return fail(TPHIP_ERR_INVALID, "null host pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    Scratch S;
+    double* d_r = S.get<double>(n);
+    int32_t* d_n = nres ? S.get<int32_t>(n) : nullptr;
+    uint16_t* d_c = S.get<uint16_t>(n * (size_t)nrep);
+    double* d_rows = S.get<double>(nrows);
+    const size_t ws_bytes = kBsAlign + std::min(bs_integ_bytes(p, p->ncols), std::max(kBsPreferredCap, bs_integ_bytes(p, p->max_locus_cols)));
+    char* ws = S.get<char>(ws_bytes);
+    if (!d_r || (nres && !d_n) || !d_c || !d_rows || !ws) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
+    if (n) {
+        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
+        if (nres) HIP_TRY(hipMemcpy(d_n, nres, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_c, counts, sizeof(uint16_t) * n * (size_t)nrep, hipMemcpyHostToDevice));
+    }
+    int rc = tphip_pi_resample_dev(p, d_r, d_n, d_c, nrep, d_rows, ws, ws_bytes, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(rows, d_rows, sizeof(double) * nrows, hipMemcpyDeviceToHost));
+    return TPHIP_OK;
+}
+
+int tphip_pi_bootstrap(tphip_plan* p, const double* rates, const int32_t* nres, const tphip_bootstrap_opts* opts, double* summary,
+                       double* rows) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    BsOpts o;
+    int rc = bs_read_opts(opts, &o);
+    if (rc) return rc;
+    const size_t n = (size_t)p->ncols, Wb = (size_t)bs_width(p), L = (size_t)p->nloci, B = (size_t)o.replicates;
+    if (L * Wb == 0) return TPHIP_OK;
+    if (!summary || (n && !rates)) return fail(TPHIP_ERR_INVALID, "null host pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    size_t mn = 0, pf = 0;
+    bs_workspace(p, o.replicates, &mn, &pf);
+    Scratch S;
+    double* d_r = S.get<double>(n);
+    int32_t* d_n = nres ? S.get<int32_t>(n) : nullptr;
+    double* d_sum = S.get<double>(L * 4 * Wb);
+    double* d_rows = rows ? S.get<double>(L * B * Wb) : nullptr;
+    char* ws = S.get<char>(pf);
+    if (!d_r || (nres && !d_n) || !d_sum || (rows && !d_rows) || !ws) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
+    if (n) {
+        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
+        if (nres) HIP_TRY(hipMemcpy(d_n, nres, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    }
+    rc = tphip_pi_bootstrap_dev(p, d_r, d_n, opts, d_sum, d_rows, ws, pf, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(summary, d_sum, sizeof(double) * L * 4 * Wb, hipMemcpyDeviceToHost));
+    if (rows) HIP_TRY(hipMemcpy(rows, d_rows, sizeof(double) * L * B * Wb, hipMemcpyDeviceToHost));
+    return TPHIP_OK;
+}
+
+int tphip_bootstrap_counts(int32_t device, uint64_t seed, int64_t locus_id, int64_t n, int64_t rep0, int32_t nrep, uint16_t* counts_out) {
+    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
+    if (n < 0 || nrep < 0 || rep0 < 0 || rep0 + nrep > ((int64_t)1 << 32)) return fail(TPHIP_ERR_INVALID, "bad arguments");
+    if (n == 0 || nrep == 0) return TPHIP_OK;
+    if (!counts_out) return fail(TPHIP_ERR_INVALID, "null host pointer");
+    if ((double)n * (double)nrep > 2147483648.0) return fail(TPHIP_ERR_INVALID, "n * nrep beyond 2^31 counts");
+    HIP_TRY(hipSetDevice(device));
+    Scratch S;
+    const size_t pitch = bs_pitch(n);
+    uint16_t* d_c = S.get<uint16_t>(pitch * (size_t)nrep);
+    if (!d_c) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
+    int rc = bs_launch_draw(nullptr, nullptr, n, locus_id, 0, 1, n, rep0, nrep, seed, d_c, (int64_t)pitch, 0, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy2D(counts_out, sizeof(uint16_t) * (size_t)n, d_c, sizeof(uint16_t) * pitch, sizeof(uint16_t) * (size_t)n,
+                        (size_t)nrep, hipMemcpyDeviceToHost));
+    return TPHIP_OK;
+}
+
+}  // extern "C"

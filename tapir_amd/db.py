@@ -80,3 +80,50 @@ def insert_tables(conn, c, names, tables, T, times, intervals):
         c.executemany("INSERT INTO interval VALUES (?,?,?,?)",
                       zip(np.repeat(keys, n_i).tolist(), labels * L, tables[:, T + n_t:T + n_t + n_i].reshape(-1).tolist(),
                           tables[:, T + n_t + n_i:T + n_t + 2 * n_i].reshape(-1).tolist()))
+
+
+BOOTSTRAP_DDL = [
+    "CREATE TABLE loci (id INTEGER PRIMARY KEY AUTOINCREMENT, locus TEXT)",
+    "CREATE TABLE net_bootstrap (id INT, time INT, mean FLOAT, sd FLOAT, lo FLOAT, hi FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE discrete_bootstrap (id INT, time INT, mean FLOAT, sd FLOAT, lo FLOAT, hi FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE interval_bootstrap (id INT, interval TEXT, mean FLOAT, sd FLOAT, lo FLOAT, hi FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE meta (key TEXT PRIMARY KEY, value TEXT)",
+]
+
+
+def write_bootstrap_db(db_name, names, summary, T, times, intervals, replicates, seed, level):
+    """phylogenetic-informativeness-bootstrap.sqlite, a file of its own beside the main database (which stays byte for
+    byte what it is without --bootstrap).  summary [L, 4, T + n_i] = mean, sd, lo, hi per locus (pipeline.bootstrap_tables);
+    the --times rows are the net rows at those times.  Loci get the ids 1..L in file order, as in the main database.
+    Bulk inserts as in insert_tables."""
+    import numpy as np
+    if os.path.exists(db_name):
+        os.remove(db_name)
+    conn = sqlite3.connect(db_name)
+    c = conn.cursor()
+    for stmt in BOOTSTRAP_DDL:
+        c.execute(stmt)
+    L, n_t, n_i = len(names), len(times), len(intervals)
+    summary = np.asarray(summary, dtype=np.float64).reshape(L, 4, T + n_i)
+    c.executemany("INSERT INTO loci(locus) VALUES (?)", [(locus_name(n),) for n in names])
+    keys = np.asarray([r[0] for r in c.execute("SELECT id FROM loci ORDER BY id").fetchall()], dtype=np.int64)
+
+    def stats(block):   # [L, 4, k] -> four flat columns, locus by locus
+        return [block[:, j, :].reshape(-1).tolist() for j in range(4)]
+
+    if L and T:
+        c.executemany("INSERT INTO net_bootstrap VALUES (?,?,?,?,?,?)",
+                      zip(np.repeat(keys, T).tolist(), np.tile(np.arange(T), L).tolist(), *stats(summary[:, :, :T])))
+    if L and n_t:
+        tt = np.asarray(times, dtype=np.int64)
+        c.executemany("INSERT INTO discrete_bootstrap VALUES (?,?,?,?,?,?)",
+                      zip(np.repeat(keys, n_t).tolist(), np.tile(tt, L).tolist(), *stats(summary[:, :, tt])))
+    if L and n_i:
+        labels = ["{0}-{1}".format(a, b) for a, b in intervals]
+        c.executemany("INSERT INTO interval_bootstrap VALUES (?,?,?,?,?,?)",
+                      zip(np.repeat(keys, n_i).tolist(), labels * L, *stats(summary[:, :, T:])))
+    c.executemany("INSERT INTO meta VALUES (?,?)", [("replicates", str(int(replicates))), ("seed", str(int(seed))),
+                                                    ("level", repr(float(level)))])
+    conn.commit()
+    c.close()
+    conn.close()

@@ -49,6 +49,11 @@ class EbOpts(ctypes.Structure):
                 ("tol_scale", _f64)]
 
 
+class BootstrapOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("replicates", _i32), ("level", _f64), ("seed", ctypes.c_uint64),
+                ("locus_ids", _vp)]
+
+
 # every symbol include/tphip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("tphip_version", ctypes.c_int, []),
@@ -102,6 +107,14 @@ SYMBOLS = [
     ("tphip_eb_fit_scale_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tphip_eb_posterior", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tphip_eb_posterior_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tphip_bootstrap_width", _i32, [_vp]),
+    ("tphip_bootstrap_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(BootstrapOpts), ctypes.POINTER(ctypes.c_size_t),
+                                                       ctypes.POINTER(ctypes.c_size_t)]),
+    ("tphip_pi_resample_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("tphip_pi_bootstrap_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(BootstrapOpts), _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("tphip_pi_resample", ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    ("tphip_pi_bootstrap", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(BootstrapOpts), _vp, _vp]),
+    ("tphip_bootstrap_counts", ctypes.c_int, [_i32, ctypes.c_uint64, _i64, _i64, _i64, _i32, _vp]),
 ]
 
 _lib = None
@@ -552,6 +565,79 @@ class Plan:
         _check(self._lib.tphip_pi_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), _ptr(d_tables), _ptr(d_ws),
                                              d_ws.numel() * d_ws.element_size(), stream))
 
+    # ---- site bootstrap of the PI rows (csrc/bootstrap_driver.hip) ------------------------------
+    def _bootstrap_opts(self, replicates, seed, level, locus_ids):
+        ids = None
+        if locus_ids is not None:
+            ids = _np(locus_ids, np.int64).reshape(-1)
+            if ids.size != self.nloci:
+                raise TphipError("locus_ids must have one entry per locus of the plan")
+        opts = BootstrapOpts(struct_size=ctypes.sizeof(BootstrapOpts), replicates=int(replicates), level=float(level),
+                             seed=int(seed) & 0xFFFFFFFFFFFFFFFF, locus_ids=_ptr(ids))
+        return opts, ids
+
+    @property
+    def bootstrap_width(self):
+        """Wb = T + n_i: net PI at t = 0..T-1, then one integral per interval."""
+        return int(self._lib.tphip_bootstrap_width(self._h))
+
+    def bootstrap_workspace_bytes(self, replicates, seed=1, level=0.95):
+        """(min, preferred) bytes of device workspace for pi_bootstrap_dev; any size >= min gives the same bits."""
+        opts, _ = self._bootstrap_opts(replicates, seed, level, None)
+        mn, pf = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(self._lib.tphip_bootstrap_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(mn), ctypes.byref(pf)))
+        return mn.value, pf.value
+
+    def resample_workspace_bytes(self):
+        """(min, preferred) bytes of device workspace for pi_resample_dev (per-site integrals only; any nrep)."""
+        mn, pf = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(self._lib.tphip_bootstrap_workspace_bytes(self._h, None, ctypes.byref(mn), ctypes.byref(pf)))
+        return mn.value, pf.value
+
+    def pi_bootstrap(self, rates, nres=None, replicates=200, seed=1, level=0.95, locus_ids=None, return_rows=False):
+        """Site bootstrap of the PI rows (tphip_pi_bootstrap): `replicates` resamples of every locus' columns with
+        replacement, the locus' model held fixed.  rates / nres as for pi_tables.  Returns summary [L, 4, Wb] (mean, sd,
+        lo, hi; [lo, hi] covers `level`) and, with return_rows, the replicate rows [L, B, Wb] as a second array.
+        locus_ids: the generator's stream id per locus (default: the plan's locus index); a locus gives the same rows
+        whatever plan it is part of as long as its id, the seed and its rates are the same."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        nres = None if nres is None else _np(nres, np.int32)
+        opts, ids = self._bootstrap_opts(replicates, seed, level, locus_ids)
+        Wb = self.bootstrap_width
+        summary = np.zeros((self.nloci, 4, Wb))
+        rows = np.zeros((self.nloci, int(replicates), Wb)) if return_rows else None
+        _check(self._lib.tphip_pi_bootstrap(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), summary.ctypes.data,
+                                            _ptr(rows)))
+        return (summary, rows) if return_rows else summary
+
+    def pi_resample(self, rates, nres, counts):
+        """The weighted-sum core on caller-supplied counts (tphip_pi_resample): counts uint16 [nrep, ncols] over the plan's
+        columns -> rows [L, nrep, Wb], rows[l, b] = sum over the locus' columns of counts[b, i] * (site i's PI values)."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        nres = None if nres is None else _np(nres, np.int32)
+        counts = _np(counts, np.uint16)
+        if counts.ndim != 2 or counts.shape[1] != self.ncols:
+            raise TphipError("counts must be uint16 [nrep, ncols]")
+        rows = np.zeros((self.nloci, counts.shape[0], self.bootstrap_width))
+        _check(self._lib.tphip_pi_resample(self._h, rates.ctypes.data, _ptr(nres), counts.ctypes.data, counts.shape[0],
+                                           rows.ctypes.data))
+        return rows
+
+    def pi_bootstrap_dev(self, d_rates, d_nres, d_summary, d_rows, d_ws, replicates, seed=1, level=0.95, locus_ids=None,
+                         stream=0, ws_bytes=None):
+        """tphip_pi_bootstrap_dev on device tensors (d_nres / d_rows may be None); ws_bytes: use only that much of d_ws."""
+        opts, ids = self._bootstrap_opts(replicates, seed, level, locus_ids)
+        nbytes = d_ws.numel() * d_ws.element_size() if ws_bytes is None else int(ws_bytes)
+        _check(self._lib.tphip_pi_bootstrap_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_summary),
+                                                _ptr(d_rows), _ptr(d_ws), nbytes, stream))
+
+    def pi_resample_dev(self, d_rates, d_nres, d_counts, nrep, d_rows, d_ws, stream=0):
+        """tphip_pi_resample_dev on device tensors: d_counts int16/uint16 [nrep, ncols], d_rows [L, nrep, Wb]."""
+        _check(self._lib.tphip_pi_resample_dev(self._h, _ptr(d_rates), _ptr(d_nres), _ptr(d_counts), int(nrep), _ptr(d_rows),
+                                               _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
+
     def profile_enable(self, on=True):
         _check(self._lib.tphip_profile_enable(self._h, 1 if on else 0))
 
@@ -574,6 +660,15 @@ class _DeviceCache:
         if self.ptr:
             _check(self.plan._lib.tphip_free_device(self.plan._h, self.ptr))
             self.ptr = _vp()
+
+
+def bootstrap_counts(n, rep0=0, nrep=1, seed=1, locus_id=0, device=0):
+    """The bootstrap's draw kernel alone (tphip_bootstrap_counts): uint16 [nrep, n], row k = how often each of the n columns
+    of a locus with stream id `locus_id` is drawn in replicate rep0 + k."""
+    out = np.zeros((int(nrep), int(n)), np.uint16)
+    _check(load().tphip_bootstrap_counts(device, int(seed) & 0xFFFFFFFFFFFFFFFF, int(locus_id), int(n), int(rep0), int(nrep),
+                                         out.ctypes.data))
+    return out
 
 
 def state_histogram(states, locus_offsets, device=0):

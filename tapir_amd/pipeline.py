@@ -778,6 +778,28 @@ def _tables_for_rates(eng, per_locus, leaf_names, parent, blen, leaf, T, times, 
         plan.close()
 
 
+def bootstrap_tables(eng, per_locus, leaf_names, parent, blen, leaf, T, intervals, device, integ_mode, locus_ids,
+                     replicates, seed=1, level=0.95):
+    """Site-bootstrap summaries [L, 4, T + n_i] (mean, sd, lo, hi of the net-PI profile and of the interval integrals) for
+    already-final rates (NaN = culled), on a no-rounding plan exactly as _tables_for_rates: every path that ends in
+    per-locus final rates (streamed or not, --subset-pi-map-file, --site-rates, --rate-estimator eb) is served without
+    being touched.  locus_ids: the generator's stream id per locus -- the command line passes the global file indices, so
+    a locus' bands do not depend on which rank, or which loci beside it, it was computed with.  The locus' model (and under
+    eb the fitted prior) are held fixed: the bands are conditional on them."""
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
+    rates = np.concatenate(per_locus) if per_locus else np.zeros(0)
+    L = len(per_locus)
+    if L == 0:
+        return np.zeros((0, 4, T + len(intervals)))
+    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, np.full((L, 4), 0.25), np.ones((L, 6)), T, [],
+                    intervals, correction=1.0, threshold=0, round_decimals=-1, integ_mode=integ_mode, device=device)
+    try:
+        return plan.pi_bootstrap(rates, None, replicates=replicates, seed=seed, level=level,
+                                 locus_ids=np.asarray(locus_ids, dtype=np.int64))
+    finally:
+        plan.close()
+
+
 def _tuples(names, per_locus, tables, T, times, intervals):
     n_t, n_i = len(times), len(intervals)
     out = []
