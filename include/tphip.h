@@ -474,6 +474,45 @@ int tphip_pi_bootstrap(tphip_plan *plan, const double *rates, const int32_t *nre
 int tphip_bootstrap_counts(int32_t device, uint64_t seed, int64_t locus_id, int64_t n, int64_t rep0, int32_t nrep,
                            uint16_t *counts_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Quartet signal and noise (an extension: Townsend, Su & Tekle 2012; Su et al. 2014).  For the four-taxon tree
+ * ((a:T, b:T)u, (c:T, d:T)v) with the internode u-v of length t_o, both in the tree's original time units, a site of final
+ * rate r under the locus' model normalised to one substitution has M = exp(Q r T / kappa), N = exp(Q r t_o / kappa) and,
+ * with w_xy = pi_x N_xy,
+ *   signal y = sum_xy w_xy sum_{i != j} M_xi^2 M_yj^2              (tip pattern iijj)
+ *   noise  x = sum_xy w_xy 2 sum_{i < j} (M_xi M_yi)(M_xj M_yj)    (tip pattern ijij; ijji has the same probability).
+ * A NaN (culled) or zero rate gives exactly 0 for both.  Inputs are those of tphip_pi_tables: raw rates and an optional
+ * nres, finalised by the plan's rounding, correction and cull; the models are the plan's (GTR or F81).
+ *
+ * Row per (locus, quartet), 8 doubles, rows [nloci][n_q][8]: Y = sum y, X = sum x, Yy = sum y^2, Xx = sum x^2,
+ * XY = sum x y over the locus' columns, then p_correct, p_incorrect, p_polytomy: the probabilities that the locus' counts
+ * of signal sites S and of the two kinds of noise sites N1, N2 give S - N > 0.5 for both, N - S > 0.5 with that N ahead of the
+ * other, or neither -- by a bivariate-normal approximation with continuity correction (Var S = Y - Yy, Var N = X - Xx,
+ * Cov(S, N) = -XY, Cov(N1, N2) = -Xx; 64-point Gauss-Legendre for the bivariate integral); (0, 0, 1) when the variance is 0.
+ *
+ * Determinism: a row depends on the locus' final rates, its model and the quartet's (T, t_o) only -- not on the other loci
+ * of the plan, on the other quartets of the list or on how a batch is sharded.  Calls on one plan must not overlap. */
+typedef struct tphip_quartet_opts {
+    uint32_t struct_size;      /* sizeof(tphip_quartet_opts) of the caller */
+    int32_t n_q;               /* quartets, 1..256 */
+    const double *tip;         /* HOST [n_q] T >= 0; read before the call returns */
+    const double *internode;   /* HOST [n_q] t_o > 0; read before the call returns */
+} tphip_quartet_opts;
+
+/* bytes of device workspace (8-byte aligned) tphip_quartet_tables_dev needs for these options */
+int tphip_quartet_workspace_bytes(const tphip_plan *plan, const tphip_quartet_opts *opts, size_t *bytes);
+/* d_rows [nloci][n_q][8].  Enqueues on `stream`, does not synchronise. */
+int tphip_quartet_tables_dev(tphip_plan *plan, const double *d_rates, const int32_t *d_nres, const tphip_quartet_opts *opts,
+                             double *d_rows, void *d_workspace, size_t workspace_bytes, void *stream);
+/* the per-site values: d_sites [2][n_q][ncols], y then x.  Enqueues on `stream`, does not synchronise. */
+int tphip_quartet_sites_dev(tphip_plan *plan, const double *d_rates, const int32_t *d_nres, const tphip_quartet_opts *opts,
+                            double *d_sites, void *stream);
+/* host-pointer twins: the library allocates its own buffers, as tphip_pi_tables does */
+int tphip_quartet_tables(tphip_plan *plan, const double *rates, const int32_t *nres, const tphip_quartet_opts *opts,
+                         double *rows);
+int tphip_quartet_sites(tphip_plan *plan, const double *rates, const int32_t *nres, const tphip_quartet_opts *opts,
+                        double *sites);
+
 #ifdef __cplusplus
 }
 #endif

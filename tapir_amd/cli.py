@@ -7,7 +7,8 @@ Same positionals, same required/optional flags and defaults, same output directo
 `--multiprocessing` parallelises the host side only (NEXUS parsing, .rates files).  New, opt-in flags only: --device, --exchangeabilities / --subs-model,
 --integral-mode, --full-precision-rates, --gamma-categories / --gamma-alpha, --site-model, --rate-estimator,
 --bootstrap / --bootstrap-seed / --bootstrap-level (site-bootstrap bands in a second file,
-phylogenetic-informativeness-bootstrap.sqlite; the other outputs stay byte for byte the same).
+phylogenetic-informativeness-bootstrap.sqlite; the other outputs stay byte for byte the same), --quartets (quartet signal
+and noise in another file of its own, phylogenetic-informativeness-quartets.sqlite; again nothing else changes).
 
 Several GPUs: launch it with `python -m torch.distributed.run --nproc-per-node G bin/tapir_compute.py ...` (one process
 per GPU).  The files are dealt round-robin over the ranks (what `Pool.map(worker, params)` did over cores,
@@ -103,7 +104,17 @@ def get_args(argv=None):
     new.add_argument('--bootstrap-seed', type=int, default=None, help="seed of the resampling (default 1); needs --bootstrap")
     new.add_argument('--bootstrap-level', type=float, default=None,
                      help="coverage of the band [lo, hi], in (0, 1) (default 0.95); needs --bootstrap")
+    new.add_argument('--quartets', type=_quartets, default=None, metavar='T:to[,T:to...]',
+                     help="signal and noise of four-taxon trees ((a:T,b:T),(c:T,d:T)) with an internode of length to, both in "
+                          "the tree's time units (floats; to > 0, T >= 0, T + to <= tree depth): per locus the expected numbers "
+                          "of signal and noise sites and the probabilities that it resolves the internode correctly, "
+                          "incorrectly or not at all (Townsend, Su & Tekle 2012) go into "
+                          "phylogenetic-informativeness-quartets.sqlite.  With --site-rates it needs the loci's model: "
+                          "--site-model jc|f81 or --exchangeabilities")
     args = parser.parse_args(argv)
+    if args.quartets is not None and args.site_rates and args.site_model == 'locus' and args.exchangeabilities is None:
+        parser.error("--quartets needs the loci's substitution model, which --site-rates does not read: "
+                     "add --site-model jc, --site-model f81 or --exchangeabilities")
     if args.bootstrap == 0:
         for flag, value in (('--bootstrap-seed', args.bootstrap_seed), ('--bootstrap-level', args.bootstrap_level)):
             if value is not None:
@@ -121,7 +132,7 @@ def get_args(argv=None):
             parser.error("--bootstrap-level must be in (0, 1)")
     if args.site_model != 'locus':
         for flag, given in (('--exchangeabilities', args.exchangeabilities is not None), ('--subs-model', bool(args.subs_model)),
-                            ('--site-rates', args.site_rates)):
+                            ('--site-rates', args.site_rates and args.quartets is None)):   # (with --quartets: the model of that stage)
             if given:
                 parser.error("--site-model {0} fixes the model: it cannot be combined with {1}".format(args.site_model, flag))
     eb_flags = (('--eb-categories', args.eb_categories), ('--eb-alpha', args.eb_alpha), ('--eb-alpha-bounds', args.eb_alpha_bounds))
@@ -154,6 +165,27 @@ def _six_floats(string):
     except Exception as e:
         raise argparse.ArgumentTypeError("Cannot convert exchangeabilities to six numbers: {0}".format(e))
     return v
+
+
+def _quartets(string):
+    """T:to[,T:to...] -> [(label as typed, T, to)]"""
+    out = []
+    for item in string.split(','):
+        try:
+            a, b = item.split(':')
+            tip, internode = float(a), float(b)
+        except Exception:
+            raise argparse.ArgumentTypeError("Cannot convert quartet %r to T:to (two numbers)" % item)
+        if not (np.isfinite(tip) and np.isfinite(internode)):
+            raise argparse.ArgumentTypeError("quartet %r: T and to must be finite" % item)
+        if not internode > 0:
+            raise argparse.ArgumentTypeError("quartet %r: the internode length to must be positive" % item)
+        if not tip >= 0:
+            raise argparse.ArgumentTypeError("quartet %r: the tip length T must not be negative" % item)
+        out.append((item.strip(), tip, internode))
+    if not 1 <= len(out) <= 256:
+        raise argparse.ArgumentTypeError("--quartets takes 1..256 quartets")
+    return out
 
 
 def _two_floats(string):
@@ -260,6 +292,9 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
     args.output, tree_depth, correction, tree = _broadcast(setup, rank, world)
     # generate a vector of times given start and stops
     T = int(tree_depth)
+    for label, tip, internode in args.quartets or []:
+        if tip + internode > tree_depth:
+            raise ValueError("--quartets {0}: T + to = {1} exceeds the tree depth {2}".format(label, tip + internode, tree_depth))
     subset_pi = dict()
     if args.subset_pi_map_file:
         subset_pi = dict(base.parse_subset_map_file(args.subset_pi_map_file))
@@ -335,6 +370,7 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
                                                    categories=args.eb_categories, alpha=args.eb_alpha,
                                                    alpha_bounds=args.eb_alpha_bounds))
             tables = out["final_tables"]
+            models = out.get("models")
             stored = bool(out.get("during_write_done"))
             sqlite_seconds = LAST_TIMINGS.get("sqlite")
             LAST_TIMINGS.clear()
@@ -342,8 +378,9 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
             if stored:
                 LAST_TIMINGS["sqlite"] = sqlite_seconds
         else:
-            pis, tables = [], np.zeros((0, W))
+            pis, tables, models = [], np.zeros((0, W)), None
     else:
+        models = None
         if rank == 0:
             print("Estimating PI for files (--site-rate option):")
         files = base.get_files(args.alignments, '*.rates')
@@ -391,11 +428,48 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
             db.write_bootstrap_db(os.path.join(args.output, 'phylogenetic-informativeness-bootstrap.sqlite'), files,
                                   all_boot.reshape(len(files), 4, Wb), T, args.times, args.intervals, args.bootstrap,
                                   args.bootstrap_seed, args.bootstrap_level)
+    if args.quartets:
+        # (as the bootstrap: an opt-in stage after the main database, from every rank's final rates; rows travel like the PI rows)
+        eng = engine_mod
+        if eng is None:
+            from . import engine as eng
+        labels = [q[0] for q in args.quartets]
+        lengths = np.array([[q[1], q[2]] for q in args.quartets], dtype=np.float64)
+        ids = list(tdist.shard_loci(len(files), rank, world))
+        if args.site_rates:
+            models = _site_rates_models(mine, args)
+        elif models is None:
+            models = dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)), model="gtr" if args.site_model == 'locus' else "f81")
+        rows = pipeline.quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent, blen, leaf, T,
+                                       args.device, lengths, model=models["model"])
+        all_rows = _gather_rows(rows.reshape(len(ids), 8 * len(labels)), len(files), rank, world, on_gpu)
+        if rank == 0:
+            db.write_quartet_db(os.path.join(args.output, 'phylogenetic-informativeness-quartets.sqlite'), files,
+                                all_rows.reshape(len(files), len(labels), 8), labels, lengths, models["model"])
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
     return args.output
+
+
+def _site_rates_models(rate_files, args):
+    """The loci's models for --quartets under --site-rates, which reads rates only: Jukes-Cantor, or the base frequencies the
+    `.rates` documents carry with exchangeabilities of 1 (f81) or the --exchangeabilities given."""
+    import json
+    L = len(rate_files)
+    if args.site_model == 'jc':
+        return dict(pi=np.full((L, 4), 0.25), exch=None, model="f81")
+    pi = np.empty((L, 4))
+    for l, f in enumerate(rate_files):
+        with open(f) as fh:
+            freqs = json.load(fh)["sites"].get("freqs")
+        if not freqs:
+            raise IOError("{0} carries no base frequencies (\"freqs\"): --quartets can only use --site-model jc with it".format(f))
+        pi[l] = [freqs[k] for k in "ACGT"]
+    if args.site_model == 'f81':
+        return dict(pi=pi, exch=None, model="f81")
+    return dict(pi=pi, exch=np.tile(np.array(args.exchangeabilities, dtype=np.float64), (L, 1)), model="gtr")
 
 
 if __name__ == '__main__':

@@ -127,3 +127,40 @@ def write_bootstrap_db(db_name, names, summary, T, times, intervals, replicates,
     conn.commit()
     c.close()
     conn.close()
+
+
+QUARTET_DDL = [
+    "CREATE TABLE loci (id INTEGER PRIMARY KEY AUTOINCREMENT, locus TEXT)",
+    "CREATE TABLE quartet (id INT, quartet TEXT, tip FLOAT, internode FLOAT, signal FLOAT, noise FLOAT, p_correct FLOAT, "
+    "p_incorrect FLOAT, p_polytomy FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE meta (key TEXT PRIMARY KEY, value TEXT)",
+]
+
+
+def write_quartet_db(db_name, names, rows, labels, quartets, model):
+    """phylogenetic-informativeness-quartets.sqlite, a file of its own beside the main database (which stays byte for byte
+    what it is without --quartets).  rows [L, n_q, 8] from pipeline.quartet_tables; labels: the quartets "T:to" as typed;
+    quartets [n_q, 2] their values.  signal and noise are the expected numbers of signal sites (Y) and of noise sites for
+    one wrong topology (X).  Loci get the ids 1..L in file order, as in the main database."""
+    import numpy as np
+    if os.path.exists(db_name):
+        os.remove(db_name)
+    conn = sqlite3.connect(db_name)
+    c = conn.cursor()
+    for stmt in QUARTET_DDL:
+        c.execute(stmt)
+    L, n_q = len(names), len(labels)
+    rows = np.asarray(rows, dtype=np.float64).reshape(L, n_q, 8)
+    quartets = np.asarray(quartets, dtype=np.float64).reshape(n_q, 2)
+    c.executemany("INSERT INTO loci(locus) VALUES (?)", [(locus_name(n),) for n in names])
+    keys = np.asarray([r[0] for r in c.execute("SELECT id FROM loci ORDER BY id").fetchall()], dtype=np.int64)
+    if L and n_q:
+        c.executemany("INSERT INTO quartet VALUES (?,?,?,?,?,?,?,?,?)",
+                      zip(np.repeat(keys, n_q).tolist(), list(labels) * L, np.tile(quartets[:, 0], L).tolist(),
+                          np.tile(quartets[:, 1], L).tolist(), rows[:, :, 0].reshape(-1).tolist(), rows[:, :, 1].reshape(-1).tolist(),
+                          rows[:, :, 5].reshape(-1).tolist(), rows[:, :, 6].reshape(-1).tolist(), rows[:, :, 7].reshape(-1).tolist()))
+    c.executemany("INSERT INTO meta VALUES (?,?)", [("quartets", ",".join(labels)), ("model", str(model)),
+                                                    ("approximation", "bivariate normal with continuity correction")])
+    conn.commit()
+    c.close()
+    conn.close()

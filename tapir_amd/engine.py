@@ -54,6 +54,10 @@ class BootstrapOpts(ctypes.Structure):
                 ("locus_ids", _vp)]
 
 
+class QuartetOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("tip", _vp), ("internode", _vp)]
+
+
 # every symbol include/tphip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("tphip_version", ctypes.c_int, []),
@@ -115,6 +119,11 @@ SYMBOLS = [
     ("tphip_pi_resample", ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
     ("tphip_pi_bootstrap", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(BootstrapOpts), _vp, _vp]),
     ("tphip_bootstrap_counts", ctypes.c_int, [_i32, ctypes.c_uint64, _i64, _i64, _i64, _i32, _vp]),
+    ("tphip_quartet_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(QuartetOpts), ctypes.POINTER(ctypes.c_size_t)]),
+    ("tphip_quartet_tables_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp, _vp, ctypes.c_size_t, _vp]),
+    ("tphip_quartet_sites_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp, _vp]),
+    ("tphip_quartet_tables", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp]),
+    ("tphip_quartet_sites", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp]),
 ]
 
 _lib = None
@@ -637,6 +646,56 @@ class Plan:
         """tphip_pi_resample_dev on device tensors: d_counts int16/uint16 [nrep, ncols], d_rows [L, nrep, Wb]."""
         _check(self._lib.tphip_pi_resample_dev(self._h, _ptr(d_rates), _ptr(d_nres), _ptr(d_counts), int(nrep), _ptr(d_rows),
                                                _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
+
+    # ---- quartet signal and noise (csrc/quartet_driver.hip) -------------------------------------
+    @staticmethod
+    def _quartet_opts(quartets):
+        """quartets: [n_q, 2] rows (T, t_o).  Returns the options and the arrays they point into (keep them alive)."""
+        q = _np(quartets, np.float64).reshape(-1, 2)
+        tip, internode = np.ascontiguousarray(q[:, 0]), np.ascontiguousarray(q[:, 1])
+        opts = QuartetOpts(struct_size=ctypes.sizeof(QuartetOpts), n_q=len(q), tip=tip.ctypes.data, internode=internode.ctypes.data)
+        return opts, (tip, internode)
+
+    def quartet_workspace_bytes(self, quartets):
+        """bytes of device workspace for quartet_tables_dev with these quartets."""
+        opts, keep = self._quartet_opts(quartets)
+        n = ctypes.c_size_t()
+        _check(self._lib.tphip_quartet_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
+        return n.value
+
+    def quartet_tables(self, rates, nres, quartets):
+        """Signal and noise of the quartets ((a:T, b:T), (c:T, d:T)) with internode t_o under the plan's models
+        (tphip_quartet_tables).  rates / nres as for pi_tables; quartets [n_q, 2] rows (T, t_o) in the tree's original time
+        units.  Returns rows [L, n_q, 8]: Y, X, Yy, Xx, XY, p_correct, p_incorrect, p_polytomy."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        nres = None if nres is None else _np(nres, np.int32)
+        opts, keep = self._quartet_opts(quartets)
+        rows = np.zeros((self.nloci, opts.n_q, 8))
+        _check(self._lib.tphip_quartet_tables(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), rows.ctypes.data))
+        return rows
+
+    def quartet_sites(self, rates, nres, quartets):
+        """The per-site values behind quartet_tables (tphip_quartet_sites): [2, n_q, ncols], signal y then noise x; exactly
+        0 for a culled or zero-rate column."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        nres = None if nres is None else _np(nres, np.int32)
+        opts, keep = self._quartet_opts(quartets)
+        sites = np.zeros((2, opts.n_q, self.ncols))
+        _check(self._lib.tphip_quartet_sites(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), sites.ctypes.data))
+        return sites
+
+    def quartet_tables_dev(self, d_rates, d_nres, quartets, d_rows, d_ws, stream=0):
+        """tphip_quartet_tables_dev on device tensors (d_nres may be None): d_rows [L, n_q, 8]; enqueues, does not synchronise."""
+        opts, keep = self._quartet_opts(quartets)
+        _check(self._lib.tphip_quartet_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_rows),
+                                                  _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
+
+    def quartet_sites_dev(self, d_rates, d_nres, quartets, d_sites, stream=0):
+        """tphip_quartet_sites_dev on device tensors: d_sites [2, n_q, ncols]; enqueues, does not synchronise."""
+        opts, keep = self._quartet_opts(quartets)
+        _check(self._lib.tphip_quartet_sites_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
 
     def profile_enable(self, on=True):
         _check(self._lib.tphip_profile_enable(self._h, 1 if on else 0))

@@ -553,6 +553,7 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
     out["timings"] = timings
     out["final_tables"] = out["tables"]
     out["streamed_blocks"] = (L + step - 1) // step
+    out["models"] = dict(pi=pi_all, exch=exch_all, model="gtr" if site_model == "locus" else "f81")
     return _tuples(alignments, per_locus, out["tables"], T, times, intervals), out
 
 
@@ -631,9 +632,11 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
                         round_decimals, integ_mode, device, extra, pi, None, need_subset, pinned, eb_options=eb_options, model="f81")
         lap("site_rates_and_pi_incl_pcie")
         exch = np.ones((L, 6))
-        return _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction,
-                       threshold, round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool,
-                       progress, during_write, timings, lap)
+        tuples, out = _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction,
+                              threshold, round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool,
+                              progress, during_write, timings, lap)
+        out["models"] = dict(pi=np.asarray(pi, dtype=np.float64), exch=exch, model="f81")
+        return tuples, out
     if pi is None and exch is not None:
         hist = eng.state_histogram(states, offsets, device=device)
         pi = nexus.base_frequencies_from_histogram(hist)
@@ -649,9 +652,11 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
     out = _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
                     round_decimals, integ_mode, device, extra, pi, exch, need_subset, pinned, eb_options=eb_options)
     lap("site_rates_and_pi_incl_pcie")
-    return _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                   round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool, progress, during_write,
-                   timings, lap)
+    tuples, out = _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
+                          round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool, progress,
+                          during_write, timings, lap)
+    out["models"] = dict(pi=pi, exch=exch, model="gtr")   # the loci's models, for stages that need them (quartet_tables)
+    return tuples, out
 
 
 def _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold, round_decimals,
@@ -796,6 +801,36 @@ def bootstrap_tables(eng, per_locus, leaf_names, parent, blen, leaf, T, interval
     try:
         return plan.pi_bootstrap(rates, None, replicates=replicates, seed=seed, level=level,
                                  locus_ids=np.asarray(locus_ids, dtype=np.int64))
+    finally:
+        plan.close()
+
+
+def quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr"):
+    """Quartet signal and noise rows [L, n_q, 8] (Y, X, Yy, Xx, XY, p_correct, p_incorrect, p_polytomy; DESIGN.md section
+    3.6) for already-final rates (NaN = culled), on a no-rounding plan exactly as bootstrap_tables: every path that ends in
+    per-locus final rates is served without being touched.  Unlike the PI stage this one needs the loci's models: pi [L, 4]
+    and exch [L, 6] (model "gtr"), or pi alone with exch None (model "f81": exchangeabilities of 1; Jukes-Cantor is pi = 1/4).
+    quartets: [n_q, 2] rows (T, t_o) in the tree's original time units, the units of --times.  A locus' rows depend on its
+    rates, its model and the quartets only, so they do not depend on which rank, or which loci beside it, it was computed
+    with."""
+    quartets = np.asarray(quartets, dtype=np.float64).reshape(-1, 2)
+    L = len(per_locus)
+    if L == 0:
+        return np.zeros((0, len(quartets), 8))
+    if model not in ("gtr", "f81"):
+        raise PipelineError("unknown model %r" % (model,))
+    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
+    if model == "gtr":
+        exch = np.asarray(exch, dtype=np.float64)
+        exch = np.tile(exch, (L, 1)) if exch.ndim == 1 else exch.reshape(L, 6)
+    else:
+        exch = None
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
+    rates = np.concatenate(per_locus)
+    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, [], [], correction=1.0, threshold=0,
+                    round_decimals=-1, device=device, model=model)
+    try:
+        return plan.quartet_tables(rates, None, quartets)
     finally:
         plan.close()
 
