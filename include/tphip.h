@@ -303,6 +303,9 @@ int tphip_profile_enable(tphip_plan *plan, int32_t on);
 int tphip_profile_read(tphip_plan *plan, double *site_rate_ms, double *pi_ms, int64_t *launches, int32_t reset);
 /* total likelihood evaluations (Newton iterations summed over columns) of the last site-rate launch */
 int tphip_last_eval_count(tphip_plan *plan, int64_t *evals);
+/* evaluation rounds of the last site-rate launch summed over its wavefronts (a round = one likelihood evaluation issued for all
+ * 64 lanes of a wavefront, busy or not): evals / (64 * rounds) is the fraction of issued lane-evaluations that carried a column */
+int tphip_last_round_count(tphip_plan *plan, int64_t *rounds);
 
 /* ------------------------------------------------------------------------------------------------
  * Host-pointer entry points: same stages, library does the copies (PCIe time included by construction).

@@ -851,8 +851,8 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
         }
     }
     unsigned evals = 0;
+    unsigned rounds = 0;   // evaluation rounds of this wave (wave-uniform: a scalar register): evals / (64 rounds) = lane use
 #ifdef TPHIP_SITE_TRACE_ROUNDS
-    unsigned rounds = 0;
     const unsigned long long tick0 = wall_clock64();
 #endif
     int64_t gpos = g0;
@@ -871,7 +871,44 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
             begin = (int)(gpos - pbeg);
             end = (int)(seg_end_g - pbeg);
             gpos = seg_end_g;
-            __syncthreads();  // the previous segment's readers of wtab / mtab are done
+            if (P.persistent && P.tail_order) {
+                // Slow columns first among the segment's LAST kTailWindow entries (a stable partition, in place: the segment
+                // is this wave's own and nothing reads the list in order after this launch).  The segment ends when its last
+                // lane ends: a 4-evaluation column handed out with the last entries keeps 63 drained lanes waiting, handed
+                // out two lane-fills earlier it ends with the others.  Every entry is loaded before any is stored (the
+                // ballots need all of them).
+                constexpr int kParts = kTailWindow / kSiteBlock;
+                int32_t* __restrict__ w = const_cast<int32_t*>(P.work_cols) + P.locus_offsets[locus];
+                const int wb = (end - begin > kTailWindow) ? end - kTailWindow : begin;
+                int32_t c[kParts];
+                bool in[kParts], slow[kParts];
+                unsigned long long ms[kParts], mf[kParts];   // ballots of the slow / the other entries of each 64
+                int ns = 0;
+                unsigned long long others = 0ull;
+#pragma unroll
+                for (int k = 0; k < kParts; ++k) {
+                    const int i = wb + k * kSiteBlock + lane;
+                    in[k] = i < end;
+                    c[k] = w[in[k] ? i : wb];
+                    slow[k] = in[k] && P.lnl[c[k]] != 0.0;
+                    ms[k] = __ballot(slow[k]);
+                    mf[k] = __ballot(in[k] && !slow[k]);
+                    ns += __popcll(ms[k]);
+                    others |= mf[k];
+                }
+                if (ns > 0 && others != 0ull) {   // wave-uniform; otherwise the window is in order already
+                    const unsigned long long below = (1ull << lane) - 1ull;
+                    int ps = wb, pf = wb + ns;
+#pragma unroll
+                    for (int k = 0; k < kParts; ++k) {
+                        if (in[k]) w[slow[k] ? ps + __popcll(ms[k] & below) : pf + __popcll(mf[k] & below)] = c[k];
+                        ps += __popcll(ms[k]);
+                        pf += __popcll(mf[k]);
+                    }
+                    __threadfence_block();
+                }
+            }
+            __syncthreads();  // the previous segment's readers of wtab / mtab are done (and the reordered entries are in place)
             const LocusModel* __restrict__ M = P.models + locus;
             if constexpr (F81) {
                 build_tip_table_f81(M, wtab, mtab, lane);
@@ -998,9 +1035,7 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
         while (true) {
             double f, g, h;
             evaluate_site<NW, SPILL, Regs>(P, R, wt, etab, stack, col, pk, exp(u), f, g, h);
-#ifdef TPHIP_SITE_TRACE_ROUNDS
             ++rounds;
-#endif
             if (!done) {
                 const double f_eval = f;
                 ++evals;
@@ -1174,11 +1209,13 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
     unsigned tot = evals;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
-    if (lane == 0 && P.eval_counter) atomicAdd(P.eval_counter, (unsigned long long)tot);
-#ifdef TPHIP_SITE_TRACE_ROUNDS   // diagnostic build: rounds and wall-clock ticks (100 MHz) per wave, sum and maximum
+    if (lane == 0 && P.eval_counter) {
+        atomicAdd(P.eval_counter, (unsigned long long)tot);
+        atomicAdd(P.eval_counter + 1, (unsigned long long)rounds);   // rounds summed over the waves (tphip_last_round_count)
+    }
+#ifdef TPHIP_SITE_TRACE_ROUNDS   // diagnostic build: the largest wave's rounds and wall-clock ticks (100 MHz) per wave, sum and maximum
     if (lane == 0 && P.eval_counter) {
         const unsigned long long ticks = wall_clock64() - tick0;
-        atomicAdd(P.eval_counter + 1, (unsigned long long)rounds);
         atomicMax(P.eval_counter + 2, (unsigned long long)rounds);
         atomicAdd(P.eval_counter + 3, ticks);
         atomicMax(P.eval_counter + 4, ticks);

@@ -32,6 +32,7 @@ constexpr double kUCheck = 2.995732273553991;   // log(20)
 constexpr double kSatTol = 1e-10;
 constexpr double kPlateauStride = 0.5;
 constexpr int kSiteBlock = 64;      // one wavefront per workgroup
+constexpr int kTailWindow = 2 * kSiteBlock;   // persistent mode: entries at the end of a segment that are put in slow-first order (SiteParams::tail_order)
 constexpr int kMixedLoci = 8;        // loci whose columns a wave of the mixed-loci mode carries at a time (site_rate_kernel.hpp)
 constexpr int kMixedLdsHeader = kMixedLoci * 64 + 64 + 32;   // doubles: tip tables, 2^(j/64), segment table
 constexpr int kMixedColBits = 28;    // a work entry of that mode = column | locus-in-group << 28: batches below 2^28 columns
@@ -66,6 +67,8 @@ struct SiteParams {
                                    // (the mixed-loci variants are launched with 1 and equal shares)
     int32_t first_round;           // persistent: the first `first_round` workgroups (one per resident wave) share
     double first_fraction;         //   this fraction of the work equally, the others the rest (see site_rate_kernel)
+    int32_t tail_order = 0;        // persistent, one locus at a time: before a wave starts a segment of its share it moves the
+                                   //   columns classify_kernel marked as slow to the front of the segment's last kTailWindow entries
     int32_t mixed_few_waves;       // mixed-loci mode: with fewer than mixed_switch_cols columns on the work list only this many
     int64_t mixed_switch_cols;     //   workgroups take shares (one wave per SIMD), the others leave at once
     int32_t ncat;                  // > 1: discrete rate mixture on top of the site rate (tphip_plan_desc.ncat)

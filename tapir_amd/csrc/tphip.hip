@@ -374,7 +374,7 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     if (e == hipSuccess) e = p->d_times.upload(times);
     if (e == hipSuccess) e = p->d_intervals.upload(iv);
     if (e == hipSuccess) e = p->d_models.alloc((size_t)d->nloci);
-    if (e == hipSuccess) e = p->d_evals.alloc(8);   // [0] evaluations; [1..5] diagnostics of a TPHIP_SITE_TRACE_ROUNDS build
+    if (e == hipSuccess) e = p->d_evals.alloc(8);   // [0] evaluations; [1] evaluation rounds; [2..5] diagnostics of a TPHIP_SITE_TRACE_ROUNDS build
     if (e == hipSuccess) e = hipMemset(p->d_evals.p, 0, 8 * sizeof(unsigned long long));
     if (e == hipSuccess && d->model == TPHIP_MODEL_F81)
         e = hipMemcpy(p->d_models.p, f81.data(), sizeof(LocusModel) * f81.size(), hipMemcpyHostToDevice);
@@ -534,6 +534,8 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             if (uneven && p->site_lds_depth < p->prog.stack_depth) p->site_first_fraction = 0.8;
             if (const char* e8 = getenv("TPHIP_SITE_FIRST_FRACTION")) p->site_first_fraction = atof(e8);
             if (const char* e7 = getenv("TPHIP_SITE_GRID_MULT")) { long v = atol(e7); if (v >= 1 && v <= 16) p->site_grid_mult = (int32_t)v; }
+            // A/B and test switch: 0 = the persistent shares hand their segments out in list order, as the other modes do
+            if (const char* e6 = getenv("TPHIP_SITE_TAIL_ORDER")) p->site_tail_order = (e6[0] != '0');
         }
     }
     // workspace layout
@@ -666,6 +668,23 @@ int tphip_last_eval_count(tphip_plan* p, int64_t* evals) {
     return TPHIP_OK;
 }
 
+int tphip_last_round_count(tphip_plan* p, int64_t* rounds) {
+    if (!p || !rounds) return fail(TPHIP_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(p->device));
+    unsigned long long v = 0;
+    if (p->last_run_in_parts) {
+        for (tphip_plan* q : p->parts) {
+            unsigned long long w = 0;
+            HIP_TRY(hipMemcpy(&w, q->d_evals.p + 1, sizeof w, hipMemcpyDeviceToHost));
+            v += w;
+        }
+    } else {
+        HIP_TRY(hipMemcpy(&v, p->d_evals.p + 1, sizeof v, hipMemcpyDeviceToHost));
+    }
+    *rounds = (int64_t)v;
+    return TPHIP_OK;
+}
+
 // ---- launches ------------------------------------------------------------------------------------
 
 static PiParams pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres, void* ws);
@@ -726,6 +745,7 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
     S.persistent = (p->site_persistent || p->site_mixed) ? 1 : 0;
     S.first_round = p->site_waves;
     S.mixed_few_waves = p->mixed_few_waves; S.mixed_switch_cols = p->mixed_switch_cols;
+    S.tail_order = (p->site_persistent && !p->site_mixed && p->site_tail_order) ? 1 : 0;
     S.first_fraction = (p->site_first_fraction > 0.0) ? p->site_first_fraction : 1.0 / (double)p->site_grid_mult;
     S.ncat = p->ncat; S.cat = p->d_cat.p;
     // profiling brackets exactly the dominant kernel, so the figure matches rocprofv3's per-kernel average

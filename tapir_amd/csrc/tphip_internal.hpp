@@ -157,6 +157,7 @@ struct tphip_plan {
     int32_t site_lds_depth = 0;   // parked partials kept in LDS by site_rate_kernel (< stack depth: SPILL variant)
     size_t ws_spill = 0;
     double site_first_fraction = 0.0;   // share of the work the first round of shares takes (0 = equal shares)
+    int32_t site_tail_order = 1;  // persistent mode: slow columns first in the last 128 entries of every segment (SiteParams::tail_order)
     // profiling
     bool profile = false;
     std::vector<hipEvent_t> ev;  // 4 events per slot: site start/stop, pi start/stop

@@ -84,6 +84,7 @@ SYMBOLS = [
     ("tphip_profile_enable", ctypes.c_int, [_vp, _i32]),
     ("tphip_profile_read", ctypes.c_int, [_vp, ctypes.POINTER(_f64), ctypes.POINTER(_f64), ctypes.POINTER(_i64), _i32]),
     ("tphip_last_eval_count", ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
+    ("tphip_last_round_count", ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
     ("tphip_host_alloc", _vp, [ctypes.c_size_t]),
     ("tphip_host_free", ctypes.c_int, [_vp]),
     ("tphip_site_rates", ctypes.c_int, [_vp] * 7),
@@ -708,6 +709,13 @@ class Plan:
     def last_eval_count(self):
         n = _i64()
         _check(self._lib.tphip_last_eval_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def last_round_count(self):
+        """Evaluation rounds of the last site-rate launch summed over its wavefronts: last_eval_count() / (64 * rounds) is
+        the share of the issued lane-evaluations that carried a column."""
+        n = _i64()
+        _check(self._lib.tphip_last_round_count(self._h, ctypes.byref(n)))
         return n.value
 
 
