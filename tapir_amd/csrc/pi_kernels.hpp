@@ -407,6 +407,65 @@ __global__ __launch_bounds__(kCompactBlock) void compact_kernel(const uint8_t* _
     if (threadIdx.x == 0) work_count[locus] = running;
 }
 
+// compact_kernel for the hand-out by predicted work (site_rate_kernel.hpp): the columns are also counted by class -- slow (classify_kernel's mark, a non-zero lnl slot) and easy (the
+// others) -- into work_class[locus][2], and reserve_q / 2^16 of the locus' easy columns (reserved_before: by their rank among
+// the locus' easy columns, so the choice sees this locus alone) leave the main part for a reserved tail at the end of the
+// locus' part of the list: [main part, stable][reserved tail, stable].  The tail's place is known only when the locus has
+// been counted, so its entries are collected in `scratch` (same shape as work_cols) and appended after the loop.
+// reserve_q = 0 gives the plain stable list.
+template <int kCompactBlock>
+__global__ __launch_bounds__(kCompactBlock) void compact_classes_kernel(const uint8_t* __restrict__ flag, const int64_t* __restrict__ locus_offsets,
+                                                                int32_t* __restrict__ work_cols, int32_t* __restrict__ work_count,
+                                                                const double* __restrict__ lnl, int32_t reserve_q,
+                                                                int32_t* __restrict__ scratch,
+                                                                int32_t* __restrict__ work_class) {
+    constexpr int kWaves = kCompactBlock / 64;
+    __shared__ int wave_tot[kWaves], wave_easy[kWaves];
+    __shared__ int running, running_easy;
+    const int locus = blockIdx.x;
+    const int64_t lo = locus_offsets[locus], hi = locus_offsets[locus + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) { running = 0; running_easy = 0; }
+    __syncthreads();
+    for (int64_t base = lo; base < hi; base += kCompactBlock) {
+        const int64_t col = base + threadIdx.x;
+        const bool want = (col < hi) && (flag[col] == TPHIP_FLAG_OK);
+        const bool easy = want && lnl[col] == 0.0;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long bal = __ballot(want), bal_easy = __ballot(easy);
+        const int before = __popcll(bal & below);
+        if (lane == 0) { wave_tot[wave] = __popcll(bal); wave_easy[wave] = __popcll(bal_easy); }
+        __syncthreads();
+        int off = running, tot = 0, eoff = running_easy, etot = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            off += (w < wave) ? wave_tot[w] : 0; tot += wave_tot[w];
+            eoff += (w < wave) ? wave_easy[w] : 0; etot += wave_easy[w];
+        }
+        if (want) {
+            // eoff: the easy columns of the locus before this one; that many of them were reserved, the others are ahead
+            // of this column in the main part
+            eoff += __popcll(bal_easy & below);
+            const int res = reserved_before(eoff, reserve_q);
+            if (easy && reserved_before((int64_t)eoff + 1, reserve_q) != res) scratch[lo + res] = (int32_t)col;
+            else work_cols[lo + off + before - res] = (int32_t)col;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { running += tot; running_easy += etot; }
+        __syncthreads();
+    }
+    const int n_res = reserved_before(running_easy, reserve_q), n_main = running - n_res;
+    if (n_res > 0) {
+        __threadfence_block();
+        __syncthreads();
+        for (int i = threadIdx.x; i < n_res; i += kCompactBlock) work_cols[lo + n_main + i] = scratch[lo + i];
+    }
+    if (threadIdx.x == 0) {
+        work_count[locus] = running;
+        work_class[2 * locus] = running - running_easy; work_class[2 * locus + 1] = running_easy;
+    }
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

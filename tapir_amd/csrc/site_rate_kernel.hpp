@@ -727,6 +727,58 @@ __global__ __launch_bounds__(1024) void scan_counts_kernel(const int32_t* __rest
     }
 }
 
+// scan_counts_kernel for the hand-out by predicted work: the same two scans and, from the per-locus class counts (C.cls: slow, easy; compact_kernel) three more: the column counts of the
+// loci's main parts and of their reserved tails (interleaved: C.part_prefix) and the predicted work of the main parts,
+// w_slow n_slow + w_easy (n_easy - reserved), in fixed point so that the scan is exact; and where the two parts of every
+// locus begin in the work list (C.part_start).
+__global__ __launch_bounds__(1024) void scan_classes_kernel(const int32_t* __restrict__ count, int64_t nloci, int32_t chunk_cols,
+                                                           int64_t* __restrict__ prefix, int64_t* __restrict__ slice_prefix, ScanClasses C) {
+    __shared__ long long wave_sum[16], wave_ssum[16], wave_wsum[16], wave_tsum[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t per = (nloci + 1023) / 1024;
+    const int64_t lo = t * per, hi = (lo + per < nloci) ? lo + per : nloci;
+    auto tail_of = [&](int64_t i) -> long long { return reserved_before(C.cls[2 * i + 1], C.reserve_q); };
+    auto work_of = [&](int64_t i) -> long long {
+        return (long long)C.w_slow * C.cls[2 * i] + (long long)C.w_easy * (C.cls[2 * i + 1] - tail_of(i));
+    };
+    long long s = 0, q = 0, ws = 0, ts = 0;
+    for (int64_t i = lo; i < hi; ++i) { s += count[i]; q += site_slices(count[i], chunk_cols); ws += work_of(i); ts += tail_of(i); }
+    // block-wide exclusive scan of the 1024 per-thread sums: shuffle scan inside each wave, then over the 16 wave
+    // totals (a single thread walking 1024 LDS entries took 20 us: 4 % of a C2 step)
+    auto wave_scan = [&](long long v) -> long long {   // inclusive, inside the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long a = __shfl_up(v, o);
+            if (lane >= o) v += a;
+        }
+        return v;
+    };
+    const long long inc = wave_scan(s), sinc = wave_scan(q), winc = wave_scan(ws), tinc = wave_scan(ts);
+    if (lane == 63) { wave_sum[wave] = inc; wave_ssum[wave] = sinc; wave_wsum[wave] = winc; wave_tsum[wave] = tinc; }
+    __syncthreads();
+    long long base = 0, sbase = 0, wbase = 0, tbase = 0, total = 0, stotal = 0, wtotal = 0, ttotal = 0;
+#pragma unroll 4   // (all 64 wave totals in flight at once do not fit the 128 registers of a 1024-thread workgroup)
+    for (int w = 0; w < 16; ++w) {
+        const long long a = wave_sum[w], b = wave_ssum[w], c = wave_wsum[w], d = wave_tsum[w];
+        if (w < wave) { base += a; sbase += b; wbase += c; tbase += d; }
+        total += a; stotal += b; wtotal += c; ttotal += d;
+    }
+    if (t == 0) {
+        prefix[nloci] = total; slice_prefix[nloci] = stotal;
+        C.wprefix[nloci] = wtotal; C.part_prefix[2 * nloci] = total - ttotal; C.part_prefix[2 * nloci + 1] = ttotal;
+    }
+    long long run = base + inc - s, srun = sbase + sinc - q, wrun = wbase + winc - ws, trun = tbase + tinc - ts;
+    for (int64_t i = lo; i < hi; ++i) {
+        const long long tail = tail_of(i);
+        C.wprefix[i] = wrun; wrun += work_of(i);
+        C.part_prefix[2 * i] = run - trun; C.part_prefix[2 * i + 1] = trun;
+        C.part_start[2 * i] = C.locus_offsets[i]; C.part_start[2 * i + 1] = C.locus_offsets[i] + (count[i] - tail);
+        trun += tail;
+        prefix[i] = run; run += count[i];
+        slice_prefix[i] = srun; srun += site_slices(count[i], chunk_cols);
+    }
+}
+
 // Persistent, statically balanced launch: the grid is exactly the number of waves the chip keeps resident;
 // wave w takes the w-th EQUAL share of the batch's global work list (the concatenation of every locus'
 // compacted column list, located through the prefix sums of the per-locus counts).  Inside one locus segment
@@ -748,8 +800,14 @@ __global__ __launch_bounds__(1024) void scan_counts_kernel(const int32_t* __rest
 //
 // MODEL = TPHIP_MODEL_F81: the closed-form messages above.  LDS: wtab is the indicator table [16][4]; pi.tip of the locus sits in
 // mtab[0..15] (the model slots 27..31 keep pi and kappa), MIXED: at wtab + 64 + 16 k for the group's k-th locus.
-template <int NW, bool SPILL = false, bool MIXED = false, int MODEL = TPHIP_MODEL_GTR>
+//
+// WORK (one locus at a time only): the instantiation that hands the list out by predicted work (SiteParams::share_work) and
+// walks it through part_prefix / part_start.  WORK = false is the plain list through work_prefix / locus_offsets: the two
+// tables are two more live scalar pointers, and the plain hand-out (every batch of short loci, the slice mode) does not pay
+// for them.
+template <int NW, bool SPILL = false, bool MIXED = false, int MODEL = TPHIP_MODEL_GTR, bool WORK = false>
 __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_kernel(SiteParams P) {
+    static_assert(!(WORK && MIXED), "shares by predicted work take one locus at a time");
     constexpr bool F81 = MODEL == TPHIP_MODEL_F81;
     using Regs = typename std::conditional<F81, F81Regs, ModelRegs>::type;
     extern __shared__ double lds[];
@@ -768,6 +826,10 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
     const int lane = threadIdx.x;
     etab[lane] = kExp2Table[lane];
     int64_t g0, g1, lo_l;
+    // WORK: where locus l's part begins in the numbering of g0 / g1 and in the work list (SiteParams::part_prefix, part_start);
+    // a share of the loci's reserved tails moves both pointers on to the tails' entries.
+    const int64_t* __restrict__ part_pre = WORK ? P.part_prefix : nullptr;
+    const int64_t* __restrict__ part_beg = WORK ? P.part_start : nullptr;
     if (P.persistent) {
         const int64_t total = P.work_prefix[P.nloci];
         // MIXED: one wave per SIMD or two is decided here, where the length of the work list is known (after classification
@@ -789,15 +851,48 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
             const int64_t g = (int64_t)(f * (double)total);
             return b >= N ? total : (g < total ? g : total);
         };
-        g0 = boundary(blockIdx.x);
-        g1 = boundary(blockIdx.x + 1);
+        if constexpr (WORK) {
+            // Shares by predicted work.  Every locus' part of the list is [main part][reserved tail of easy columns]
+            // (compact_kernel).  The first main_shares workgroups cut the concatenated main parts into equal predicted work:
+            // the locus of a cut from the weighted prefix, the place inside the locus by interpolation on its columns.  The
+            // others cut the concatenated reserved tails into equal column counts: those columns are all easy, a share's lanes
+            // finish nearly in step and its drain is short.  g0 and g1 count columns of the main parts or of the tails
+            // (SiteParams::part_prefix), whichever this share walks.
+            const unsigned M = (unsigned)P.main_shares;
+            if (blockIdx.x >= M) {
+                ++part_pre;
+                ++part_beg;
+                const int64_t ttotal = part_pre[2 * P.nloci];
+                g0 = (int64_t)(blockIdx.x - M) * ttotal / (nshares - M);
+                g1 = (int64_t)(blockIdx.x - M + 1) * ttotal / (nshares - M);
+            } else {
+                const int64_t wtotal = P.work_wprefix[P.nloci];
+                auto main_cut = [&](unsigned b) -> int64_t {
+                    if (b >= M) return part_pre[2 * P.nloci];
+                    const int64_t target = (int64_t)b * wtotal / M;
+                    int64_t l = 0, h = P.nloci;   // the last l with work_wprefix[l] <= target
+                    while (h - l > 1) {
+                        const int64_t mid = (l + h) >> 1;
+                        if (P.work_wprefix[mid] <= target) l = mid; else h = mid;
+                    }
+                    const int64_t wl = P.work_wprefix[l], ww = P.work_wprefix[l + 1] - wl;
+                    const int64_t mb = part_pre[2 * l], nm = part_pre[2 * l + 2] - mb;
+                    return mb + (ww > 0 ? (target - wl) * nm / ww : 0);
+                };
+                g0 = main_cut(blockIdx.x);
+                g1 = main_cut(blockIdx.x + 1);
+            }
+        } else {
+            g0 = boundary(blockIdx.x);
+            g1 = boundary(blockIdx.x + 1);
+        }
         if (g0 >= g1) return;
         // first locus of this share: the last l with prefix[l] <= g0 (binary search, wave-uniform)
         int64_t hi_l = P.nloci;
         lo_l = 0;
         while (hi_l - lo_l > 1) {
             const int64_t mid = (lo_l + hi_l) >> 1;
-            if (P.work_prefix[mid] <= g0) lo_l = mid; else hi_l = mid;
+            if ((WORK ? part_pre[2 * mid] : P.work_prefix[mid]) <= g0) lo_l = mid; else hi_l = mid;
         }
     } else {
         // Small batches (a share would be a few hundred columns): one workgroup per locus-aligned slice instead,
@@ -865,9 +960,11 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
         int myk = 0, K = 1;          // MIXED: the lane's locus within the group; loci in the group
         const int32_t* __restrict__ work;
         if constexpr (!MIXED) {
-            const int64_t pbeg = P.work_prefix[locus], pend = P.work_prefix[locus + 1];
+            const int64_t pbeg = WORK ? part_pre[2 * locus] : P.work_prefix[locus];
+            const int64_t pend = WORK ? part_pre[2 * locus + 2] : P.work_prefix[locus + 1];
             const int64_t seg_end_g = pend < g1 ? pend : g1;
             if (seg_end_g <= gpos) { ++locus; continue; }  // locus without optimiser work
+            const int64_t part_at = WORK ? part_beg[2 * locus] : P.locus_offsets[locus];   // the locus' entries (WORK: its main part, or its reserved tail)
             begin = (int)(gpos - pbeg);
             end = (int)(seg_end_g - pbeg);
             gpos = seg_end_g;
@@ -878,7 +975,7 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
                 // out two lane-fills earlier it ends with the others.  Every entry is loaded before any is stored (the
                 // ballots need all of them).
                 constexpr int kParts = kTailWindow / kSiteBlock;
-                int32_t* __restrict__ w = const_cast<int32_t*>(P.work_cols) + P.locus_offsets[locus];
+                int32_t* __restrict__ w = const_cast<int32_t*>(P.work_cols) + part_at;
                 const int wb = (end - begin > kTailWindow) ? end - kTailWindow : begin;
                 int32_t c[kParts];
                 bool in[kParts], slow[kParts];
@@ -918,7 +1015,7 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
                 R = load_model(M, mtab, lane);
             }
             kappa = mtab[31];
-            work = ((!P.persistent && P.work_cols2) ? (const int32_t*)P.work_cols2 : P.work_cols) + P.locus_offsets[locus];
+            work = ((!P.persistent && P.work_cols2) ? (const int32_t*)P.work_cols2 : P.work_cols) + part_at;
             ++locus;
         } else {
             __syncthreads();  // the previous group's readers of the tables are done

@@ -21,6 +21,14 @@ namespace tphip {
 template <int MODEL>
 static hipError_t launch_site_rate_model(int variant, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S) {
     const dim3 block(kSiteBlock);
+    if (S.share_work) {   // shares by predicted work: the instantiations that walk the list through part_prefix / part_start
+        if (variant == 2) site_rate_kernel<2, false, false, MODEL, true><<<grid, block, lds_bytes, st>>>(S);
+        else if (variant == 8) site_rate_kernel<8, false, false, MODEL, true><<<grid, block, lds_bytes, st>>>(S);
+        else if (variant == kStreamWords) site_rate_kernel<kStreamWords, false, false, MODEL, true><<<grid, block, lds_bytes, st>>>(S);
+        else if (variant == kStreamWordsSpill) site_rate_kernel<kStreamWords, true, false, MODEL, true><<<grid, block, lds_bytes, st>>>(S);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     if (variant == 2) site_rate_kernel<2, false, false, MODEL><<<grid, block, lds_bytes, st>>>(S);
     else if (variant == 8) site_rate_kernel<8, false, false, MODEL><<<grid, block, lds_bytes, st>>>(S);
     else if (variant == kMixedVariant + 2) site_rate_kernel<2, false, true, MODEL><<<grid, block, lds_bytes, st>>>(S);
@@ -90,8 +98,9 @@ hipError_t launch_site_posterior_kernel(int variant, int model, dim3 grid, size_
 }
 
 hipError_t launch_scan_counts_kernel(hipStream_t st, const int32_t* count, int64_t nloci, int32_t chunk_cols, int64_t* prefix,
-                                     int64_t* slice_prefix) {
-    scan_counts_kernel<<<dim3(1), dim3(1024), 0, st>>>(count, nloci, chunk_cols, prefix, slice_prefix);
+                                     int64_t* slice_prefix, const ScanClasses* C) {
+    if (C) scan_classes_kernel<<<dim3(1), dim3(1024), 0, st>>>(count, nloci, chunk_cols, prefix, slice_prefix, *C);
+    else scan_counts_kernel<<<dim3(1), dim3(1024), 0, st>>>(count, nloci, chunk_cols, prefix, slice_prefix);
     return hipGetLastError();
 }
 

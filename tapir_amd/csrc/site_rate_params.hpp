@@ -33,6 +33,10 @@ constexpr double kSatTol = 1e-10;
 constexpr double kPlateauStride = 0.5;
 constexpr int kSiteBlock = 64;      // one wavefront per workgroup
 constexpr int kTailWindow = 2 * kSiteBlock;   // persistent mode: entries at the end of a segment that are put in slow-first order (SiteParams::tail_order)
+constexpr int kReserveShift = 16;     // the reserved fraction of a locus' easy columns is reserve_q / 2^16 (reserved_before)
+constexpr int kShareWeightShift = 10; // predicted evaluations per column of a class, in units of 2^-10 (the weighted scan stays exact)
+constexpr double kDefaultReserve = 0.15;  // shares by predicted work (SiteParams::share_work): this fraction of every locus' easy columns
+                                          //   forms its reserved tail; TPHIP_SITE_RESERVE
 constexpr int kMixedLoci = 8;        // loci whose columns a wave of the mixed-loci mode carries at a time (site_rate_kernel.hpp)
 constexpr int kMixedLdsHeader = kMixedLoci * 64 + 64 + 32;   // doubles: tip tables, 2^(j/64), segment table
 constexpr int kMixedColBits = 28;    // a work entry of that mode = column | locus-in-group << 28: batches below 2^28 columns
@@ -69,6 +73,15 @@ struct SiteParams {
     double first_fraction;         //   this fraction of the work equally, the others the rest (see site_rate_kernel)
     int32_t tail_order = 0;        // persistent, one locus at a time: before a wave starts a segment of its share it moves the
                                    //   columns classify_kernel marked as slow to the front of the segment's last kTailWindow entries
+    int32_t share_work = 0;        // persistent, one locus at a time: shares by predicted work.  compact_kernel put a fixed fraction of
+                                   //   every locus' easy (unmarked) columns into a reserved tail of the locus' part of the list; the
+                                   //   first `main_shares` workgroups cut the main parts into equal predicted work (work_wprefix), the
+                                   //   others cut the reserved tails into equal column counts (tail_prefix).  0: shares as above
+    int32_t main_shares = 0;
+    const int64_t* work_wprefix = nullptr;   // [nloci+1] exclusive scan of the main parts' predicted work (scan_classes_kernel)
+    const int64_t* part_prefix = nullptr;    // [nloci+1][2] exclusive scans of the column counts of the main parts / the reserved tails
+    const int64_t* part_start = nullptr;     // [nloci][2] where the locus' main part / reserved tail begins in work_cols
+                                             //   (both written by scan_classes_kernel, read by the WORK instantiations only)
     int32_t mixed_few_waves;       // mixed-loci mode: with fewer than mixed_switch_cols columns on the work list only this many
     int64_t mixed_switch_cols;     //   workgroups take shares (one wave per SIMD), the others leave at once
     int32_t ncat;                  // > 1: discrete rate mixture on top of the site rate (tphip_plan_desc.ncat)
@@ -87,6 +100,13 @@ __host__ __device__ __forceinline__ int site_slices(int count, int chunk_cols) {
     if (count <= 0) return 0;
     const int ns = (count + chunk_cols / 2) / chunk_cols;
     return ns < 1 ? 1 : ns;
+}
+
+// Of the first r easy columns of a locus (in list order), how many go to the locus' reserved tail: the column of rank r
+// is reserved when this count steps from r to r + 1.  The rule sees the locus' own columns only, so which columns are
+// reserved does not depend on the other loci of the batch (or on how a batch is sharded).
+__host__ __device__ __forceinline__ int32_t reserved_before(int64_t r, int32_t reserve_q) {
+    return (int32_t)((r * (int64_t)reserve_q) >> kReserveShift);
 }
 
 constexpr int kStreamWords = -1;   // NW value of the streamed-words path
@@ -109,7 +129,16 @@ struct EvalParams {
 hipError_t launch_site_rate_kernel(int variant, int model, dim3 grid, size_t lds_bytes, hipStream_t st, const SiteParams& S);
 hipError_t site_rate_kernel_occupancy(int variant, int model, size_t lds_bytes, int* blocks_per_cu);
 hipError_t launch_eval_columns_kernel(int model, dim3 grid, size_t lds_bytes, hipStream_t st, const EvalParams& E);
+// scan_classes_kernel's view of the classes: cls [nloci][2] = slow / easy work-list columns per locus (compact_classes_kernel)
+struct ScanClasses {
+    const int32_t* cls = nullptr;
+    const int64_t* locus_offsets = nullptr;
+    int32_t reserve_q = 0, w_slow = 0, w_easy = 0;
+    int64_t* wprefix = nullptr;       // SiteParams::work_wprefix
+    int64_t* part_prefix = nullptr;   // SiteParams::part_prefix
+    int64_t* part_start = nullptr;    // SiteParams::part_start
+};
 hipError_t launch_scan_counts_kernel(hipStream_t st, const int32_t* count, int64_t nloci, int32_t chunk_cols, int64_t* prefix,
-                                     int64_t* slice_prefix);
+                                     int64_t* slice_prefix, const ScanClasses* C);   // C null: the two plain scans
 
 }  // namespace tphip

@@ -536,17 +536,42 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             if (const char* e7 = getenv("TPHIP_SITE_GRID_MULT")) { long v = atol(e7); if (v >= 1 && v <= 16) p->site_grid_mult = (int32_t)v; }
             // A/B and test switch: 0 = the persistent shares hand their segments out in list order, as the other modes do
             if (const char* e6 = getenv("TPHIP_SITE_TAIL_ORDER")) p->site_tail_order = (e6[0] != '0');
+            // Shares by predicted work (site_rate_kernel.hpp; persistent mode with one locus at a time only): the weights are the
+            // mean evaluations of a marked and of an unmarked column.  TPHIP_SITE_SHARE_WORK=0 is the A/B
+            // and test switch back to shares of equal column counts and a list without reserved tails.
+            // On where the first-round shares lie inside long loci (C3: a locus holds ~20 of them, its reserved tail thousands
+            // of columns); where a share spans several short loci the tail of a locus is a segment of a lane-fill or two with
+            // a drain of its own, and the old hand-out is faster (whole C4 +6.5 %, whole C5 +2-5 %: DESIGN section 8, r10).
+            double reserve = kDefaultReserve, w_slow = 2.9, w_easy = 2.04;
+            p->site_share_work = (uneven && share < 2 * avg_locus) ? 1 : 0;
+            if (const char* e5 = getenv("TPHIP_SITE_SHARE_WORK")) p->site_share_work = (e5[0] != '0');
+            if (const char* e4 = getenv("TPHIP_SITE_RESERVE")) reserve = atof(e4);
+            if (const char* e1 = getenv("TPHIP_SITE_CLASS_WEIGHTS")) {
+                double a = 0, b = 0;
+                if (sscanf(e1, "%lf,%lf", &a, &b) == 2 && a > 0 && b > 0 && a <= 16 && b <= 16) { w_slow = a; w_easy = b; }
+            }
+            // the interpolation inside a locus multiplies its predicted work by its column count in 64 bits
+            if (!p->site_persistent || p->site_mixed || p->max_locus_cols > ((int64_t)1 << 24)) p->site_share_work = 0;
+            p->site_w_slow = std::max<int32_t>(1, (int32_t)lround(w_slow * (1 << kShareWeightShift)));
+            p->site_w_easy = std::max<int32_t>(1, (int32_t)lround(w_easy * (1 << kShareWeightShift)));
+            // without later shares there is nobody to take a reserved tail
+            reserve = (p->site_share_work && p->site_grid_mult > 1) ? std::min(std::max(reserve, 0.0), 1.0) : 0.0;
+            p->site_reserve_q = (int32_t)lround(reserve * (1 << kReserveShift));
         }
     }
     // workspace layout
     size_t off = 0;
     p->ws_work_cols = off; off = align_up(off + sizeof(int32_t) * (size_t)ncols, 256);
-    if (!p->site_persistent) {   // small batches: slow-columns-first copy of the work list
+    if (!p->site_persistent || p->site_reserve_q > 0) {   // small batches: slow-columns-first copy of the work list; reserved tails: compact_kernel's scratch
         p->ws_work_cols2 = off; off = align_up(off + sizeof(int32_t) * (size_t)ncols, 256);
     }
     p->ws_work_count = off; off = align_up(off + sizeof(int32_t) * (size_t)d->nloci, 256);
     p->ws_work_prefix = off; off = align_up(off + sizeof(int64_t) * ((size_t)d->nloci + 1), 256);
     p->ws_slice_prefix = off; off = align_up(off + sizeof(int64_t) * ((size_t)d->nloci + 1), 256);
+    p->ws_work_class = off; off = align_up(off + sizeof(int32_t) * 2 * (size_t)d->nloci, 256);
+    p->ws_work_wprefix = off; off = align_up(off + sizeof(int64_t) * ((size_t)d->nloci + 1), 256);
+    p->ws_part_prefix = off; off = align_up(off + sizeof(int64_t) * 2 * ((size_t)d->nloci + 1), 256);
+    p->ws_part_start = off; off = align_up(off + sizeof(int64_t) * 2 * ((size_t)d->nloci + 1), 256);
     p->ws_partial = off; off = align_up(off + sizeof(double) * (size_t)p->n_pi_chunks * (size_t)(d->T + 2 * d->n_i), 256);
     p->ws_packed = off; off = align_up(off + sizeof(uint32_t) * (size_t)p->nwords * (size_t)ncols, 256);
     if (const char* e9 = getenv("TPHIP_DEDUP")) {   // test/tuning knob: 0 = never, 1 = always, anything else = automatic
@@ -721,10 +746,26 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
             dedup_insert_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
             dedup_resolve_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
         }
-        if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
-        else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
-        HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site_chunk_cols, (int64_t*)((char*)ws + p->ws_work_prefix),
-                                          (int64_t*)((char*)ws + p->ws_slice_prefix)));
+        if (p->site_share_work) {
+            // shares by predicted work: the list with class counts and reserved tails, and their scans (compact_classes_kernel
+            // reads the marks, 8 more bytes per work column in its chain of barriers, and appends the tails: C3 47 -> 100 us)
+            int32_t* work_class = (int32_t*)((char*)ws + p->ws_work_class);
+            int32_t* scratch = p->site_reserve_q > 0 ? (int32_t*)((char*)ws + p->ws_work_cols2) : nullptr;
+            if (p->max_locus_cols > 2048) compact_classes_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
+            else compact_classes_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
+            ScanClasses SC;
+            SC.cls = work_class; SC.reserve_q = p->site_reserve_q; SC.w_slow = p->site_w_slow; SC.w_easy = p->site_w_easy;
+            SC.locus_offsets = p->d_offsets.p;
+            SC.wprefix = (int64_t*)((char*)ws + p->ws_work_wprefix); SC.part_prefix = (int64_t*)((char*)ws + p->ws_part_prefix);
+            SC.part_start = (int64_t*)((char*)ws + p->ws_part_start);
+            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site_chunk_cols, (int64_t*)((char*)ws + p->ws_work_prefix),
+                                              (int64_t*)((char*)ws + p->ws_slice_prefix), &SC));
+        } else {
+            if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
+            else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
+            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site_chunk_cols, (int64_t*)((char*)ws + p->ws_work_prefix),
+                                              (int64_t*)((char*)ws + p->ws_slice_prefix), nullptr));
+        }
     }
     HIP_TRY(hipMemsetAsync(p->d_evals.p, 0, 8 * sizeof(unsigned long long), st));
     SiteParams S;
@@ -747,6 +788,10 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
     S.mixed_few_waves = p->mixed_few_waves; S.mixed_switch_cols = p->mixed_switch_cols;
     S.tail_order = (p->site_persistent && !p->site_mixed && p->site_tail_order) ? 1 : 0;
     S.first_fraction = (p->site_first_fraction > 0.0) ? p->site_first_fraction : 1.0 / (double)p->site_grid_mult;
+    S.share_work = p->site_share_work;
+    S.main_shares = (p->site_reserve_q > 0) ? p->site_waves : p->site_waves * p->site_grid_mult;
+    S.work_wprefix = (const int64_t*)((char*)ws + p->ws_work_wprefix); S.part_prefix = (const int64_t*)((char*)ws + p->ws_part_prefix);
+    S.part_start = (const int64_t*)((char*)ws + p->ws_part_start);
     S.ncat = p->ncat; S.cat = p->d_cat.p;
     // profiling brackets exactly the dominant kernel, so the figure matches rocprofv3's per-kernel average
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 0], st));

@@ -158,6 +158,11 @@ struct tphip_plan {
     size_t ws_spill = 0;
     double site_first_fraction = 0.0;   // share of the work the first round of shares takes (0 = equal shares)
     int32_t site_tail_order = 1;  // persistent mode: slow columns first in the last 128 entries of every segment (SiteParams::tail_order)
+    // persistent mode, one locus at a time: shares by predicted work (SiteParams::share_work).  reserve_q / 2^16 of every locus'
+    // easy columns go to a reserved tail that the later, small shares cut into equal column counts; the first round's shares
+    // cut the rest into equal predicted work, a slow column weighing w_slow / 2^10 evaluations and an easy one w_easy / 2^10
+    int32_t site_share_work = 0, site_reserve_q = 0, site_w_slow = 0, site_w_easy = 0;
+    size_t ws_work_class = 0, ws_work_wprefix = 0, ws_part_prefix = 0, ws_part_start = 0;
     // profiling
     bool profile = false;
     std::vector<hipEvent_t> ev;  // 4 events per slot: site start/stop, pi start/stop
