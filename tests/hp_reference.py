@@ -11,6 +11,10 @@ what the reference program calls).
   P(tau) comes from mpmath's symmetric eigen-solver applied to D^1/2 Q D^-1/2, and the derivatives are analytic:
   d/du P(t e^u) = (Q tau) P, d2/du2 = (Q tau + (Q tau)^2) P.  Pruning is plain (mpmath's exponent range makes
   rescaling unnecessary).
+* Whole-locus log-likelihood lnL = sum_c w_c log L_c at site rate 1 (stage 1's objective) with d lnL / d log t_b and
+  d2 lnL / d (log t_b)^2 of any branch, analytic (the same three matrices, carried from the branch to the root past the stored
+  sibling messages), and d lnL / d r_q of the six exchangeabilities by central differences inside mpmath at 60 digits with a
+  relative step of 1e-18 (truncation and rounding both below 1e-30).
 * PI(t) = 16 r^2 t exp(-4 r t) and its exact integral G(4rb) - G(4ra), G(x) = -(1+x) exp(-x).
 """
 import math
@@ -31,16 +35,18 @@ def floored_pi(pi, floor=1e-12):
     return p / p.sum()
 
 
-def rate_matrix(pi, exch):
-    """HyPhy's unnormalised GTR generator (mpmath matrix) and kappa."""
-    with mp.workdps(DPS):
+def rate_matrix(pi, exch, dps=None):
+    """HyPhy's unnormalised GTR generator (mpmath matrix) and kappa.  Exchangeabilities that are already mpf are taken as
+    they are (a relative step of 1e-18 must survive); anything else goes through float."""
+    with mp.workdps(dps or DPS):
         pi = [mpmath.mpf(float(x)) for x in pi]
         tot = mpmath.fsum(pi)
         pi = [x / tot for x in pi]
         Q = mpmath.zeros(4, 4)
         for (i, j), r in zip(PAIRS, exch):
-            Q[i, j] = mpmath.mpf(float(r)) * pi[j]
-            Q[j, i] = mpmath.mpf(float(r)) * pi[i]
+            r = r if isinstance(r, mpmath.mpf) else mpmath.mpf(float(r))
+            Q[i, j] = r * pi[j]
+            Q[j, i] = r * pi[i]
         for i in range(4):
             Q[i, i] = -mpmath.fsum(Q[i, j] for j in range(4) if j != i)
         kappa = -mpmath.fsum(pi[i] * Q[i, i] for i in range(4))
@@ -50,16 +56,17 @@ def rate_matrix(pi, exch):
 class _Model:
     """Transition matrices P(tau), dP/du, d2P/du2 (tau = t e^u) as 4x4 object arrays of mpf."""
 
-    def __init__(self, pi, exch, model):
+    def __init__(self, pi, exch, model, dps=None):
         self.model = model
-        with mp.workdps(DPS):
+        self.dps = dps or DPS
+        with mp.workdps(self.dps):
             if model == "f81":
                 p = [mpmath.mpf(float(x)) for x in pi]
                 tot = mpmath.fsum(p)
                 self.pi = [x / tot for x in p]
                 self.kappa = 1 - mpmath.fsum(x * x for x in self.pi)
             else:
-                Q, self.pi, self.kappa = rate_matrix(pi, exch)
+                Q, self.pi, self.kappa = rate_matrix(pi, exch, self.dps)
                 sq = [mpmath.sqrt(x) for x in self.pi]
                 S = mpmath.zeros(4, 4)
                 for i in range(4):
@@ -72,7 +79,7 @@ class _Model:
                 self.B = [[[V[i, k] * V[j, k] * sq[j] / sq[i] for j in range(4)] for i in range(4)] for k in range(4)]
 
     def matrices(self, tau):
-        with mp.workdps(DPS):
+        with mp.workdps(self.dps):
             P = np.empty((4, 4), object)
             P1 = np.empty((4, 4), object)
             P2 = np.empty((4, 4), object)
@@ -159,6 +166,127 @@ def column_curves(states, parent, blen, leaf_taxon, pi, exch, u, model="gtr"):
                 G[iu, c] = float(g)
                 H[iu, c] = float(L2[c] / L[c] - g * g)
     return F, G, H
+
+
+# ---- whole-locus log-likelihood (stage 1) -----------------------------------------------------------------------------
+
+def _locus_sweep(M, states, parent, blen, leaf_taxon, branches, want_derivs):
+    """Plain pruning of every column at once (object arrays [4, ncols] of mpf), no rescaling.  Returns per column log L_c
+    and, per requested branch, g_c = L'/L and h_c = L''/L - g_c^2 in log t_b: with only t_b moving, L is linear in P_b, so
+    L' = pi . (path to the root applied to (Q t) P l_b) and L'' the same with (Q t + (Q t)^2) P.  Every branch's message is
+    computed once; a derivative climbs from its branch to the root past the stored sibling messages."""
+    states = np.asarray(states, np.uint8)
+    ntaxa, ncols = states.shape
+    parent = np.asarray(parent)
+    leaf_taxon = np.asarray(leaf_taxon)
+    nn = len(parent)
+    children = [[] for _ in range(nn)]
+    for n in range(nn):
+        if parent[n] >= 0:
+            children[parent[n]].append(n)
+    one, zero = mpmath.mpf(1), mpmath.mpf(0)
+    mats, part, msg = [None] * nn, [None] * nn, [None] * nn
+    for n in range(nn):                  # post-order: children first
+        if leaf_taxon[n] >= 0:
+            m = states[leaf_taxon[n]] & 15
+            m = np.where(m == 0, 15, m)  # a zero byte is read as a gap
+            v = np.array([[one if (int(c) >> i) & 1 else zero for c in m] for i in range(4)], object).reshape(4, ncols)
+        else:
+            v = None
+            for c in children[n]:
+                v = msg[c] if v is None else v * msg[c]
+        part[n] = v
+        if parent[n] >= 0:
+            mats[n] = M.matrices(mpmath.mpf(float(blen[n])))
+            msg[n] = mats[n][0].dot(v)
+    roots = [n for n in range(nn) if parent[n] < 0]
+    assert roots == [nn - 1]
+    pi_r = np.array(M.pi, object)
+    L = pi_r.dot(part[nn - 1])
+    logl = np.array([mpmath.log(x) for x in L], object)
+    g, h = {}, {}
+    if not want_derivs:
+        return logl, g, h
+    if branches is None:
+        branches = [n for n in range(nn) if parent[n] >= 0]
+    for b in branches:
+        b = int(b)
+        assert parent[b] >= 0
+        a1, a2 = mats[b][1].dot(part[b]), mats[b][2].dot(part[b])
+        n = b
+        while True:
+            p = int(parent[n])
+            for s in children[p]:
+                if s != n:
+                    a1, a2 = a1 * msg[s], a2 * msg[s]
+            if parent[p] < 0:
+                break
+            a1, a2 = mats[p][0].dot(a1), mats[p][0].dot(a2)
+            n = p
+        g[b] = pi_r.dot(a1) / L
+        h[b] = pi_r.dot(a2) / L - g[b] * g[b]
+    return logl, g, h
+
+
+def _wsum(weights, vals):
+    if weights is None:
+        return mpmath.fsum(vals)
+    return mpmath.fsum(mpmath.mpf(float(w)) * v for w, v in zip(weights, vals))
+
+
+def locus_reference_columns(states, parent, blen, leaf, pi, exch, branches=None, dps=None):
+    """Per column (mpf object arrays): log L_c, and dicts branch -> L'/L and branch -> L''/L - (L'/L)^2 in log t_b.  A locus
+    made of these columns with weights w has lnL = sum w_c log L_c and the same sums for its derivatives."""
+    dps = dps or DPS
+    with mp.workdps(dps):
+        return _locus_sweep(_Model(floored_pi(pi), exch, "gtr", dps), states, parent, blen, leaf, branches, True)
+
+
+def locus_reference(states, weights, parent, blen, leaf, pi, exch, branches=None, dps=None, as_float=True):
+    """lnL = sum_c w_c log L_c of a locus at site rate 1 under GTR, and for every branch in `branches` (default: all)
+    d lnL / d log t_b and d2 lnL / d (log t_b)^2, analytic, at dps digits (default DPS).  states: uint8 masks
+    [ntaxa, ncols] (0 is read as 15); weights: per column or None; parent / blen / leaf: post-order arrays, root last; pi is
+    floored as a GTR plan floors it.  Returns (lnl, dlogt, d2logt): floats and arrays over all nodes (NaN where not
+    requested), or with as_float=False an mpf and two dicts branch -> mpf."""
+    dps = dps or DPS
+    with mp.workdps(dps):
+        logl, g, h = locus_reference_columns(states, parent, blen, leaf, pi, exch, branches, dps)
+        lnl = _wsum(weights, logl)
+        d1 = {b: _wsum(weights, g[b]) for b in g}
+        d2 = {b: _wsum(weights, h[b]) for b in h}
+        if not as_float:
+            return lnl, d1, d2
+        ga, ha = np.full(len(parent), np.nan), np.full(len(parent), np.nan)
+        for b in d1:
+            ga[b], ha[b] = float(d1[b]), float(d2[b])
+        return float(lnl), ga, ha
+
+
+def locus_dexch_reference_columns(states, parent, blen, leaf, pi, exch, dps=60, step=1e-18):
+    """Per column d log L_c / d r_q at fixed branch lengths, [6, ncols] of mpf: central differences of log L_c with a relative
+    step of `step`, evaluated at `dps` digits (truncation ~ step^2, rounding ~ 10^-dps / step: both below 1e-30)."""
+    ncols = np.asarray(states).shape[1]
+    out = np.empty((6, ncols), object)
+    with mp.workdps(dps):
+        hh = mpmath.mpf(step)
+        base = [mpmath.mpf(float(r)) for r in exch]
+        pif = floored_pi(pi)
+        for q in range(6):
+            f = []
+            for sgn in (1, -1):
+                e = list(base)
+                e[q] = base[q] * (1 + sgn * hh)
+                f.append(_locus_sweep(_Model(pif, e, "gtr", dps), states, parent, blen, leaf, None, False)[0])
+            out[q] = (f[0] - f[1]) / (2 * hh * base[q])
+    return out
+
+
+def locus_dexch_reference(states, weights, parent, blen, leaf, pi, exch, dps=60, step=1e-18, as_float=True):
+    """d lnL / d r_q at fixed branch lengths for the six exchangeabilities (see locus_dexch_reference_columns)."""
+    with mp.workdps(dps):
+        cols = locus_dexch_reference_columns(states, parent, blen, leaf, pi, exch, dps, step)
+        out = [_wsum(weights, cols[q]) for q in range(6)]
+        return np.array([float(x) for x in out]) if as_float else out
 
 
 # ---- PI ------------------------------------------------------------------------------------------------------------

@@ -4,8 +4,9 @@ independent CPU restatement in oracle/stage1_oracle.py.
 Parity unpinned against HyPhy itself: the reference holds no stage-1 output and its HyPhy binary is neither
 present nor run; what is checked is that the GPU likelihood + batched optimiser reach the same optimum, weights
 and averaged rates as scipy's L-BFGS-B over the oracle's C likelihood (tolerance 1e-3 relative, set by the
-optimisers' stopping rules on a flat likelihood surface, not by the arithmetic: the likelihood itself agrees to
-1e-10, tests/test_gpu_parity.py::test_locus_loglik_vs_oracle)."""
+optimisers' stopping rules on a flat likelihood surface, not by the arithmetic: the likelihood, its gradient and its
+curvature are pinned to a 40-digit reference on every kernel path by tests/test_gpu_stage1_numerics.py; the oracle
+shares the kernels' formulas and is a parity check only)."""
 import os
 import sys
 

@@ -108,3 +108,119 @@ def test_closed_form_cancelling_cases(oracle, a, b, r):
     ex = float(hp.integral_exact(a, b, r))
     got = oracle.lib().orc_integral_closed(float(a), float(b), float(r))
     assert abs(got - ex) <= 1e-12 * ex, (got, ex)
+
+
+# ---- whole-locus reference (stage 1) ----------------------------------------------------------------------------------
+
+def _locus_case():
+    from tapir_amd import synth
+    d = synth.simulate(1, 48, 9, 33, rate_mean=0.02)
+    pin = synth.plan_inputs(d["root"], d["names"])
+    st = d["states"].numpy()[:, :48].copy()
+    st[2, 3:9] = 5
+    st[4, 20] = 0       # a zero byte is a gap
+    return st, np.asarray(pin["parent"]), np.asarray(pin["blen"], np.float64) * 3.0, np.asarray(pin["leaf"]), d["pi"][0], d["exch"][0]
+
+
+def test_locus_reference_agrees_with_the_oracle(oracle):
+    """lnL against oracle.locus_loglik at the 1e-9 of test_gpu_parity.test_locus_loglik_vs_oracle, the analytic branch
+    derivatives and the six rate derivatives against central differences of the oracle at the 2e-6 max(1, |g|) of
+    test_locus_gradient_vs_oracle_finite_differences, the second derivatives at 1e-4 (the differences' own noise)."""
+    st, parent, blen, leaf, pi, exch = _locus_case()
+    lnl, g, h = hp.locus_reference(st, None, parent, blen, leaf, pi, exch)
+    dex = hp.locus_dexch_reference(st, None, parent, blen, leaf, pi, exch)
+    stz = np.where(st == 0, 15, st).astype(np.uint8)
+    f = lambda e, b: oracle.locus_loglik(stz, parent, b, leaf, pi, e)   # noqa: E731
+    ref = f(exch, blen)
+    assert abs(lnl - ref) < 1e-9 * abs(ref)
+    assert abs(lnl - ref) < 1e-13 * abs(ref)     # (what it really is on ordinary inputs)
+    step = 1e-5
+    rdex = np.zeros(6)
+    for q in range(6):
+        ep, em = exch.copy(), exch.copy()
+        ep[q] *= 1 + step
+        em[q] *= 1 - step
+        rdex[q] = (f(ep, blen) - f(em, blen)) / (2 * step * exch[q])
+    br = np.flatnonzero(parent >= 0)
+    rg, rh = np.zeros(len(parent)), np.zeros(len(parent))
+    s2 = 1e-3
+    for b in br:
+        bp, bm = blen.copy(), blen.copy()
+        bp[b] *= np.exp(step)
+        bm[b] *= np.exp(-step)
+        rg[b] = (f(exch, bp) - f(exch, bm)) / (2 * step)
+        bp[b], bm[b] = blen[b] * np.exp(s2), blen[b] * np.exp(-s2)
+        rh[b] = (f(exch, bp) - 2 * ref + f(exch, bm)) / (s2 * s2)
+    tol = 2e-6 * max(1.0, np.abs(rdex).max(), np.abs(rg).max())
+    assert np.abs(dex - rdex).max() < tol and np.abs(g[br] - rg[br]).max() < tol
+    assert np.abs(h[br] - rh[br]).max() < 1e-4 * max(1.0, np.abs(rh).max())
+    assert np.isnan(g[parent < 0]).all()
+    # column weights are multiplicities: weight 2 on a column = the column twice
+    w = np.ones(st.shape[1])
+    w[5], w[11] = 2.0, 3.0
+    rep = np.concatenate([st, st[:, [5, 11, 11]]], axis=1)
+    a = hp.locus_reference(st, w, parent, blen, leaf, pi, exch, branches=br[:3])
+    b = hp.locus_reference(rep, None, parent, blen, leaf, pi, exch, branches=br[:3])
+    assert abs(a[0] - b[0]) < 1e-13 * abs(b[0]) and np.allclose(a[1][br[:3]], b[1][br[:3]], rtol=1e-13, atol=0)
+    assert np.isnan(a[1][br[3]]) and np.allclose(a[2][br[:3]], b[2][br[:3]], rtol=1e-13, atol=0)
+
+
+def test_locus_reference_two_taxon_closed_form():
+    """Two taxa: L = pi_i P_ij(t_a + t_b).  Under Jukes-Cantor in HyPhy's parametrisation (Q_ij = 1/4) P is elementary:
+    P_ii = 1/4 + 3/4 e^-t, P_ij = 1/4 - 1/4 e^-t, and so are the derivatives in log t_a; under GTR P comes from mpmath's expm of
+    Q (t_a + t_b), not from the eigen-decomposition the reference uses."""
+    parent, leaf = np.array([2, 2, -1]), np.array([0, 1, -1])
+    ta, tb = 0.3, 0.045
+    st = np.array([[1, 2, 4, 8, 1, 8], [1, 2, 8, 8, 4, 2]], np.uint8)
+    same = st[0] == st[1]
+    w = np.array([3.0, 1.0, 2.0, 1.0, 1.0, 4.0])
+    lnl, g, h = hp.locus_reference(st, w, parent, [ta, tb, 0.0], leaf, [0.25] * 4, np.ones(6), as_float=False)
+    with mpmath.workdps(hp.DPS):
+        t, a = mpmath.mpf(ta) + mpmath.mpf(tb), mpmath.mpf(ta)
+        e = mpmath.exp(-t)
+        want = want_g = want_h = 0
+        for c in range(st.shape[1]):
+            L = (1 + 3 * e) / 16 if same[c] else (1 - e) / 16
+            dL = (-3 * e if same[c] else e) / 16          # dL/dt
+            d2L = -dL
+            u1, u2 = a * dL / L, (a * a * d2L + a * dL) / L   # d/dlog t_a = t_a d/dt
+            want += w[c] * mpmath.log(L)
+            want_g += w[c] * u1
+            want_h += w[c] * (u2 - u1 * u1)
+        assert abs(lnl - want) < mpmath.mpf(10) ** -35 * abs(want)
+        assert abs(g[0] - want_g) < mpmath.mpf(10) ** -35 * abs(want_g)
+        assert abs(h[0] - want_h) < mpmath.mpf(10) ** -35 * abs(want_h)
+        # GTR: pi_i expm(Q t)_ij
+        pi, exch = [0.1, 0.2, 0.3, 0.4], [0.7, 1.0, 1.9, 0.4, 2.5, 1.1]
+        Q, pim, _ = hp.rate_matrix(pi, exch)
+        P = mpmath.expm(Q * t, method="taylor")
+        idx = {1: 0, 2: 1, 4: 2, 8: 3}
+        want = mpmath.fsum(w[c] * mpmath.log(pim[idx[st[0, c]]] * P[idx[st[0, c]], idx[st[1, c]]]) for c in range(st.shape[1]))
+        lnl = hp.locus_reference(st, w, parent, [ta, tb, 0.0], leaf, pi, exch, as_float=False)[0]
+        assert abs(lnl - want) < mpmath.mpf(10) ** -30 * abs(want)
+
+
+def test_locus_reference_does_not_depend_on_its_precision():
+    """Doubling the working precision moves nothing at 1e-30: lnL, every branch derivative, the six rate derivatives (60 and
+    120 digits at the same 1e-18 step bound rounding; 1e-18 and 1e-20 steps bound truncation, through fp64 1e-15)."""
+    st, parent, blen, leaf, pi, exch = _locus_case()
+    st = st[:, :12]
+    a = hp.locus_reference(st, None, parent, blen, leaf, pi, exch, as_float=False)
+    b = hp.locus_reference(st, None, parent, blen, leaf, pi, exch, dps=2 * hp.DPS, as_float=False)
+    with mpmath.workdps(2 * hp.DPS):
+        tiny = mpmath.mpf(10) ** -30
+        assert abs(a[0] - b[0]) <= tiny * abs(b[0])
+        for k in (1, 2):
+            for n in b[k]:
+                assert abs(a[k][n] - b[k][n]) <= tiny * max(1, abs(b[k][n])), (k, n)
+    d60 = hp.locus_dexch_reference(st, None, parent, blen, leaf, pi, exch, as_float=False)
+    d120 = hp.locus_dexch_reference(st, None, parent, blen, leaf, pi, exch, dps=120, as_float=False)
+    d20 = hp.locus_dexch_reference(st, None, parent, blen, leaf, pi, exch, dps=120, step=1e-20, as_float=False)
+    with mpmath.workdps(120):
+        for q in range(6):
+            assert abs(d60[q] - d120[q]) <= tiny * max(1, abs(d120[q])) and abs(d60[q] - d20[q]) <= tiny * max(1, abs(d20[q])), q
+    # an mpf step survives rate_matrix (a float cast would round 1 + 1e-18 to 1)
+    with mpmath.workdps(60):
+        r = mpmath.mpf(1) + mpmath.mpf("1e-18")
+        Q = hp.rate_matrix([0.25] * 4, [r] + [1.0] * 5, dps=60)[0]
+        assert Q[0, 1] != Q[0, 2] and abs(Q[0, 1] / Q[0, 2] - r) < mpmath.mpf("1e-50")
