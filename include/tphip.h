@@ -516,6 +516,80 @@ int tphip_quartet_tables(tphip_plan *plan, const double *rates, const int32_t *n
 int tphip_quartet_sites(tphip_plan *plan, const double *rates, const int32_t *nres, const tphip_quartet_opts *opts,
                         double *sites);
 
+/* ------------------------------------------------------------------------------------------------
+ * Parametric bootstrap of the site rates and the PI rows (an extension).  The site bootstrap above resamples columns with
+ * their rates held fixed; this one asks how noisy the rates themselves are: every column is simulated down the plan's tree
+ * under the locus' model at the column's own rate, with the observed pattern of missing cells, its rate is re-estimated by
+ * the site-rate stage and the PI row recomputed, B times.  The locus' model and the tree are held fixed -- there is no
+ * stage-1 refit per replicate: the bands are conditional on the fitted substitution model.
+ *
+ * Simulation of column i of a locus with stream id `id`, replicate b, raw rate r (the unit of tphip_site_rates' rate,
+ * kappa * s, used exactly as given, no rounding): the root's state is drawn from the locus' pi; a node with parent state x
+ * and branch length t (the plan's) from row x of exp(Q r t / kappa) in the expm1 form of the quartet section (F81 in closed
+ * form), so that r = 0 gives the identity exactly and every cell equals the root's state.  Draw d belongs to the node with
+ * post-order index d: Philox4x32-10 with key ((seed & 0xffffffff) ^ 0x73696D75, seed >> 32) and counter
+ * (i, b | ((d >> 1) << 16), id & 0xffffffff, id >> 32); u = (((x1 << 32) | x0) >> 11) * 2^-53 for an even d, the same from
+ * (x3, x2) for an odd one.  Every node has its draw whether or not its cell is masked.  With the probabilities p[0..3]
+ * (A, C, G, T) clamped at >= 0, c0 = p0, c1 = c0 + p1, c2 = c1 + p2, c3 = c2 + p3 and v = u * c3, the state is
+ * (v >= c0) + (v >= c1) + (v >= c2): a state of probability exactly 0 is never drawn.  A NaN, infinite or negative r gives a
+ * column of 15s.  With a mask (an alignment in the plan's layout, 0 read as 15) a cell whose mask byte is not one of
+ * 1, 2, 4, 8 is copied through, every other cell is 1 << state; without one every cell is 1 << state.  Output: taxon-major
+ * [ntaxa][ncols], the plan's layout.  Multifurcations work, the root's own branch length is ignored, column weights are
+ * ignored.  Refused (TPHIP_ERR_INVALID): plans with ncat > 1, trees of 2^17 nodes or more or with more than 10240 internal
+ * nodes (their 2-bit states no longer fit the LDS), b >= 65536.
+ *
+ * Determinism: a column's bytes depend on seed, id, i, b, r, the locus' model, the tree and the column's mask only -- not on
+ * the other loci of the plan or on the launch shape.  Calls on one plan must not overlap. */
+typedef struct tphip_simulate_opts {
+    uint32_t struct_size;      /* sizeof(tphip_simulate_opts) of the caller */
+    int32_t replicate;         /* b, 0..65535 */
+    uint64_t seed;
+    const int64_t *locus_ids;  /* HOST [nloci] stream id per locus, NULL = the plan's locus index; handled as by
+                                  tphip_pi_bootstrap_dev: copied first, `stream` synchronised once */
+} tphip_simulate_opts;
+
+/* d_rates [ncols] raw rates; d_mask [ntaxa][ncols] or NULL; d_states_out [ntaxa][ncols].  Enqueues on `stream`. */
+int tphip_simulate_columns_dev(tphip_plan *plan, const double *d_rates, const uint8_t *d_mask,
+                               const tphip_simulate_opts *opts, uint8_t *d_states_out, void *stream);
+int tphip_simulate_columns(tphip_plan *plan, const double *rates, const uint8_t *mask, const tphip_simulate_opts *opts,
+                           uint8_t *states_out);
+
+/* The replicate loop.  Per replicate b = 0..B-1: simulate with the observed alignment as mask; run the plan's site-rate stage
+ * (de-duplication and start rule as the plan says) and its PI-table stage on the simulated states; copy net PI [0..T) and the
+ * n_i integrals of every locus into rows[l][b][0..Wb), Wb = T + n_i (the layout of tphip_pi_bootstrap); fold every column's
+ * final rate -- after the plan's rounding, correction and cull, what the PI stage sees -- into running moments (Welford, in
+ * replicate order).  Then d_summary [nloci][4][Wb] = mean, sd, lo, hi as for tphip_pi_bootstrap.  d_rate_mean / d_rate_sd
+ * [ncols] (B - 1 in the denominator) are NaN for a column whose final rate is NaN in any replicate; with the mask kept those
+ * are exactly the culled columns.  d_rows [nloci][B][Wb], d_rate_mean and d_rate_sd may be NULL.  d_rates are the raw rates
+ * the simulation runs at (NaN = a culled column: it comes out all missing and is culled again).
+ * A site whose rate is 0 simulates constant and is estimated at 0 again: its mean and sd are exactly 0.
+ * Errors are TPHIP_ERR_INVALID throughout, a workspace below tphip_parboot_workspace_bytes() included. */
+typedef struct tphip_parboot_opts {
+    uint32_t struct_size;      /* sizeof(tphip_parboot_opts) of the caller */
+    int32_t replicates;        /* B, 2..4096 */
+    double level;              /* coverage of [lo, hi], in (0, 1) */
+    uint64_t seed;
+    const int64_t *locus_ids;  /* as in tphip_simulate_opts */
+} tphip_parboot_opts;
+
+/* device workspace: one replicate of states, the per-column outputs of the site-rate stage, one table, the rows, the moments
+ * and the plan's own workspace */
+int tphip_parboot_workspace_bytes(const tphip_plan *plan, const tphip_parboot_opts *opts, size_t *bytes);
+int tphip_pi_parametric_bootstrap_dev(tphip_plan *plan, const double *d_rates, const uint8_t *d_states_observed,
+                                      const tphip_parboot_opts *opts, double *d_summary, double *d_rows,
+                                      double *d_rate_mean, double *d_rate_sd, void *d_workspace, size_t workspace_bytes,
+                                      void *stream);
+/* host-pointer twin: the library allocates its own workspace */
+int tphip_pi_parametric_bootstrap(tphip_plan *plan, const double *rates, const uint8_t *states_observed,
+                                  const tphip_parboot_opts *opts, double *summary, double *rows, double *rate_mean,
+                                  double *rate_sd);
+/* The summary of tphip_pi_bootstrap on any rows [nloci][B][Wb] -> d_summary [nloci][4][Wb]: mean, sd (B - 1), and the
+ * quantiles at (1 - level) / 2 and 1 - (1 - level) / 2 by numpy's default rule.  B in 2..4096.  Plan-less. */
+int tphip_summarize_rows_dev(int32_t device, const double *d_rows, int64_t nloci, int32_t B, int32_t Wb, double level,
+                             double *d_summary, void *stream);
+int tphip_summarize_rows(int32_t device, const double *rows, int64_t nloci, int32_t B, int32_t Wb, double level,
+                         double *summary);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ Same positionals, same required/optional flags and defaults, same output directo
 --integral-mode, --full-precision-rates, --gamma-categories / --gamma-alpha, --site-model, --rate-estimator,
 --bootstrap / --bootstrap-seed / --bootstrap-level (site-bootstrap bands in a second file,
 phylogenetic-informativeness-bootstrap.sqlite; the other outputs stay byte for byte the same), --quartets (quartet signal
-and noise in another file of its own, phylogenetic-informativeness-quartets.sqlite; again nothing else changes).
+and noise in another file of its own, phylogenetic-informativeness-quartets.sqlite; again nothing else changes),
+--parametric-bootstrap / --parametric-bootstrap-seed / --parametric-bootstrap-level (the rates re-estimated on simulated
+alignments: bands in phylogenetic-informativeness-parametric-bootstrap.sqlite, per-site moments in NAME.rates-bootstrap.json).
 
 Several GPUs: launch it with `python -m torch.distributed.run --nproc-per-node G bin/tapir_compute.py ...` (one process
 per GPU).  The files are dealt round-robin over the ranks (what `Pool.map(worker, params)` did over cores,
@@ -104,6 +106,17 @@ def get_args(argv=None):
     new.add_argument('--bootstrap-seed', type=int, default=None, help="seed of the resampling (default 1); needs --bootstrap")
     new.add_argument('--bootstrap-level', type=float, default=None,
                      help="coverage of the band [lo, hi], in (0, 1) (default 0.95); needs --bootstrap")
+    new.add_argument('--parametric-bootstrap', type=int, default=0, metavar='B',
+                     help="B in 2..4096: parametric bootstrap of the site rates: B times every column is simulated down the tree "
+                          "under its locus' fitted model at its own fitted rate (the observed missing cells kept), its rate "
+                          "re-estimated and the PI profile recomputed; mean, sd and a confidence band per entry go into "
+                          "phylogenetic-informativeness-parametric-bootstrap.sqlite, mean and sd of every site's rate into "
+                          "NAME.rates-bootstrap.json.  Not with --site-rates, --rate-estimator eb or --gamma-categories above 1.  "
+                          "0 = off")
+    new.add_argument('--parametric-bootstrap-seed', type=int, default=None,
+                     help="seed of the simulation (default 1); needs --parametric-bootstrap")
+    new.add_argument('--parametric-bootstrap-level', type=float, default=None,
+                     help="coverage of the band [lo, hi], in (0, 1) (default 0.95); needs --parametric-bootstrap")
     new.add_argument('--quartets', type=_quartets, default=None, metavar='T:to[,T:to...]',
                      help="signal and noise of four-taxon trees ((a:T,b:T),(c:T,d:T)) with an internode of length to, both in "
                           "the tree's time units (floats; to > 0, T >= 0, T + to <= tree depth): per locus the expected numbers "
@@ -130,6 +143,28 @@ def get_args(argv=None):
             args.bootstrap_level = 0.95
         if not 0.0 < args.bootstrap_level < 1.0:
             parser.error("--bootstrap-level must be in (0, 1)")
+    if args.parametric_bootstrap == 0:
+        for flag, value in (('--parametric-bootstrap-seed', args.parametric_bootstrap_seed),
+                            ('--parametric-bootstrap-level', args.parametric_bootstrap_level)):
+            if value is not None:
+                parser.error("{0} needs --parametric-bootstrap".format(flag))
+    else:
+        if not 2 <= args.parametric_bootstrap <= 4096:
+            parser.error("--parametric-bootstrap must be in 2..4096")
+        if args.site_rates:
+            parser.error("--parametric-bootstrap simulates alignments: it cannot be combined with --site-rates, which reads none")
+        if args.rate_estimator == 'eb':
+            parser.error("--parametric-bootstrap re-estimates maximum-likelihood rates: it cannot be combined with --rate-estimator eb")
+        if args.gamma_categories > 1:
+            parser.error("--parametric-bootstrap has no rate mixture: it cannot be combined with --gamma-categories above 1")
+        if args.parametric_bootstrap_seed is None:
+            args.parametric_bootstrap_seed = 1
+        if not 0 <= args.parametric_bootstrap_seed < 2 ** 64:
+            parser.error("--parametric-bootstrap-seed must be in 0..2^64-1")
+        if args.parametric_bootstrap_level is None:
+            args.parametric_bootstrap_level = 0.95
+        if not 0.0 < args.parametric_bootstrap_level < 1.0:
+            parser.error("--parametric-bootstrap-level must be in (0, 1)")
     if args.site_model != 'locus':
         for flag, given in (('--exchangeabilities', args.exchangeabilities is not None), ('--subs-model', bool(args.subs_model)),
                             ('--site-rates', args.site_rates and args.quartets is None)):   # (with --quartets: the model of that stage)
@@ -428,6 +463,26 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
             db.write_bootstrap_db(os.path.join(args.output, 'phylogenetic-informativeness-bootstrap.sqlite'), files,
                                   all_boot.reshape(len(files), 4, Wb), T, args.times, args.intervals, args.bootstrap,
                                   args.bootstrap_seed, args.bootstrap_level)
+    if args.parametric_bootstrap:
+        # (as the site bootstrap: after the main database, every rank on its own loci, stream ids = global file indices; the
+        # alignments are re-read: the main run does not keep them)
+        eng = engine_mod
+        if eng is None:
+            from . import engine as eng
+        Wb = T + len(args.intervals)
+        ids = list(tdist.shard_loci(len(files), rank, world))
+        pmodels = models if models is not None else dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)),
+                                                         model="gtr" if args.site_model == 'locus' else "f81")
+        pboot, _ = pipeline.parametric_bootstrap_tables(
+            eng, mine, [p[1] for p in pis], pmodels, leaf_names, parent, blen, leaf, T, args.intervals, correction, args.threshold,
+            -1 if args.full_precision_rates else 4, args.device, integ_mode, ids, args.parametric_bootstrap,
+            args.parametric_bootstrap_seed, args.parametric_bootstrap_level, subsets=subset_pi,
+            start_rule=1 if args.reference_start else 0, output_dir=args.output)
+        all_pboot = _gather_rows(pboot.reshape(len(ids), 4 * Wb), len(files), rank, world, on_gpu)
+        if rank == 0:
+            db.write_bootstrap_db(os.path.join(args.output, 'phylogenetic-informativeness-parametric-bootstrap.sqlite'), files,
+                                  all_pboot.reshape(len(files), 4, Wb), T, args.times, args.intervals, args.parametric_bootstrap,
+                                  args.parametric_bootstrap_seed, args.parametric_bootstrap_level, method="parametric")
     if args.quartets:
         # (as the bootstrap: an opt-in stage after the main database, from every rank's final rates; rows travel like the PI rows)
         eng = engine_mod

@@ -90,6 +90,19 @@ void bs_quantile_index(int32_t n, double q, int32_t* idx, double* frac) {
     *frac = vi - fl;
 }
 
+// what bootstrap_summary_kernel needs for B replicates of width Wb at coverage `level`; rows and summary are set per launch
+SummaryParams bs_summary_params(int32_t B, int32_t Wb, double level) {
+    SummaryParams S;
+    S.rows = nullptr; S.summary = nullptr;
+    S.B = B; S.Wb = Wb;
+    S.npow2 = 2;
+    while (S.npow2 < B) S.npow2 <<= 1;
+    const double q_lo = (1.0 - level) / 2.0, q_hi = 1.0 - (1.0 - level) / 2.0;
+    bs_quantile_index(B, q_lo, &S.idx_lo, &S.frac_lo);
+    bs_quantile_index(B, q_hi, &S.idx_hi, &S.frac_hi);
+    return S;
+}
+
 // integrals of the columns [c0, c1) into `integ`
 int bs_launch_integrals(const tphip_plan* p, const PiParams& Q, int64_t c0, int64_t c1, double* integ, hipStream_t st) {
     if (c1 > c0 && p->n_i > 0) {
@@ -219,13 +232,7 @@ int tphip_pi_bootstrap_dev(tphip_plan* p, const double* d_rates, const int32_t* 
     base += bs_ids_bytes(p);
     usable -= bs_ids_bytes(p);
     const PiParams Q = bs_pi_params(p, d_rates, d_nres);
-    SummaryParams S;
-    S.B = B; S.Wb = Wb;
-    S.npow2 = 2;
-    while (S.npow2 < B) S.npow2 <<= 1;
-    const double q_lo = (1.0 - o.level) / 2.0, q_hi = 1.0 - (1.0 - o.level) / 2.0;
-    bs_quantile_index(B, q_lo, &S.idx_lo, &S.frac_lo);
-    bs_quantile_index(B, q_hi, &S.idx_hi, &S.frac_hi);
+    SummaryParams S = bs_summary_params(B, Wb, o.level);
     int64_t l0 = 0;
     while (l0 < p->nloci) {
         // as many consecutive loci as fit with all B replicates' counts; a locus that does not fit alone goes in ranges
@@ -339,6 +346,43 @@ int tphip_bootstrap_counts(int32_t device, uint64_t seed, int64_t locus_id, int6
     if (rc) return rc;
     HIP_TRY(hipMemcpy2D(counts_out, sizeof(uint16_t) * (size_t)n, d_c, sizeof(uint16_t) * pitch, sizeof(uint16_t) * (size_t)n,
                         (size_t)nrep, hipMemcpyDeviceToHost));
+    return TPHIP_OK;
+}
+
+// The summary kernel on any [L][B][Wb] rows (it lives here because a __global__ definition must stay in one translation
+// unit; the parametric bootstrap of simulate_driver.hip ends in this call).
+int tphip_summarize_rows_dev(int32_t device, const double* d_rows, int64_t nloci, int32_t B, int32_t Wb, double level,
+                             double* d_summary, void* stream) {
+    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
+    if (B < 2 || B > kBsMaxReplicates) return fail(TPHIP_ERR_INVALID, "replicates must be in 2..4096");
+    if (!(level > 0.0 && level < 1.0)) return fail(TPHIP_ERR_INVALID, "level must be in (0, 1)");
+    if (nloci < 0 || Wb < 0) return fail(TPHIP_ERR_INVALID, "negative size");
+    if (nloci == 0 || Wb == 0) return TPHIP_OK;
+    if (!d_rows || !d_summary) return fail(TPHIP_ERR_INVALID, "null device pointer");
+    if (nloci * (int64_t)Wb > 0x7fffffffll) return fail(TPHIP_ERR_INVALID, "nloci * Wb beyond 2^31 - 1 entries");
+    HIP_TRY(hipSetDevice(device));
+    SummaryParams S = bs_summary_params(B, Wb, level);
+    S.rows = d_rows;
+    S.summary = d_summary;
+    bootstrap_summary_kernel<<<dim3((unsigned)(nloci * Wb)), dim3(256), 0, (hipStream_t)stream>>>(S);
+    HIP_TRY(hipGetLastError());
+    return TPHIP_OK;
+}
+
+int tphip_summarize_rows(int32_t device, const double* rows, int64_t nloci, int32_t B, int32_t Wb, double level, double* summary) {
+    if (nloci < 0 || Wb < 0 || B < 0) return fail(TPHIP_ERR_INVALID, "negative size");
+    const size_t nrows = (size_t)nloci * (size_t)B * (size_t)Wb, nsum = (size_t)nloci * 4 * (size_t)Wb;
+    if (nsum && (!rows || !summary)) return fail(TPHIP_ERR_INVALID, "null host pointer");
+    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
+    HIP_TRY(hipSetDevice(device));
+    Scratch S;
+    double* d_rows = S.get<double>(nrows);
+    double* d_sum = S.get<double>(nsum);
+    if (!d_rows || !d_sum) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
+    if (nrows) HIP_TRY(hipMemcpy(d_rows, rows, sizeof(double) * nrows, hipMemcpyHostToDevice));
+    int rc = tphip_summarize_rows_dev(device, d_rows, nloci, B, Wb, level, d_sum, nullptr);
+    if (rc) return rc;
+    if (nsum) HIP_TRY(hipMemcpy(summary, d_sum, sizeof(double) * nsum, hipMemcpyDeviceToHost));
     return TPHIP_OK;
 }
 

@@ -18,6 +18,7 @@
 
 #include "gtr_model.hpp"
 #include "pi_rate.hpp"
+#include "transition_row.hpp"
 
 namespace tphip {
 
@@ -47,31 +48,12 @@ struct QuartetParams {
     int64_t ncols;
 };
 
-// P(tau) = exp(Q r tau / kappa), row-major.  expm1 form: I + sum_k U[:,k] expm1(lam_k r tau / kappa) U^-1[k,:] keeps the
-// off-diagonal entries accurate relative to themselves when r tau << 1 ("accuracy at t s << 1").
-// F81: e I + (1 - e) Pi with 1 - e = -expm1(-r tau / kappa): no eigenvector enters, an absent base stays exactly absent.
+// P(tau) = exp(Q r tau / kappa), row-major: the four rows of transition_row.hpp (the expm1 form; F81 in closed form).
 __device__ __forceinline__ void quartet_transition(const LocusModel& m, bool f81, double r, double tau, double* __restrict__ P) {
-#pragma clang fp contract(off)
-    const double s = r * tau / m.kappa;
-    if (f81) {
-        const double ome = -expm1(-s);          // 1 - e
-        const double e = 1.0 - ome;
+    double e[3];
+    transition_exps(m, f81, transition_scale(m, r, tau), e);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) P[4 * i + j] = (i == j) ? fma(ome, m.pi[j], e) : ome * m.pi[j];
-        return;
-    }
-    const double e1 = expm1(m.lam[0] * s), e2 = expm1(m.lam[1] * s), e3 = expm1(m.lam[2] * s);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const double a1 = m.U[3 * i] * e1, a2 = m.U[3 * i + 1] * e2, a3 = m.U[3 * i + 2] * e3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double v = fma(a3, m.Ui[8 + j], fma(a2, m.Ui[4 + j], a1 * m.Ui[j]));
-            P[4 * i + j] = (i == j) ? 1.0 + v : v;
-        }
-    }
+    for (int i = 0; i < 4; ++i) transition_row(m, f81, e, i, P + 4 * i);
 }
 
 // (y, x) of one site from its two matrices.  With a_x[i] = M_xi^2 and R_y[i] = sum_{j != i} a_y[j] (three additions each),

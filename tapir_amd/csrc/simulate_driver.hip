@@ -1,0 +1,306 @@
+// simulate_driver.hip -- parametric bootstrap of site rates and PI rows: the C entry points
+// tphip_simulate_columns (+ _dev), tphip_pi_parametric_bootstrap (+ _dev) and tphip_parboot_workspace_bytes.  The kernels
+// are in simulate_kernels.hpp; the summary at the end is tphip_summarize_rows_dev (bootstrap_driver.hip).
+//
+// A replicate is three enqueues on the caller's stream: simulate every column at its fitted rate with the observed pattern of
+// missing cells, the plan's own site-rate and PI-table stages on the simulated states (tphip_run_dev: de-duplication and start
+// rule as the plan says), and the copy of the table into the replicate's row with the Welford update of the rate moments.
+// The locus' model and the tree are held fixed -- no stage-1 refit per replicate: the bands are conditional on the fitted
+// substitution model.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+#include <vector>
+
+#include "simulate_kernels.hpp"
+#include "tphip_internal.hpp"
+
+namespace {
+
+constexpr size_t kSimAlign = 256;
+constexpr int32_t kParbootMaxReplicates = 4096;   // the summary kernel's limit (bootstrap_kernels.hpp: kBsMaxReplicates)
+
+struct SimOpts {
+    int32_t replicate = 0;
+    uint64_t seed = 0;
+    const int64_t* locus_ids = nullptr;
+};
+
+struct ParbootOpts {
+    int32_t replicates = 0;
+    double level = 0.0;
+    uint64_t seed = 0;
+    const int64_t* locus_ids = nullptr;
+};
+
+int sim_read_opts(const tphip_simulate_opts* o, SimOpts* out) {
+    if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_simulate_opts");
+    if (o->struct_size < offsetof(tphip_simulate_opts, seed) + sizeof(uint64_t))
+        return fail(TPHIP_ERR_INVALID, "tphip_simulate_opts.struct_size is too small: set it to sizeof(tphip_simulate_opts)");
+    out->replicate = o->replicate;
+    out->seed = o->seed;
+    out->locus_ids = (o->struct_size >= offsetof(tphip_simulate_opts, locus_ids) + sizeof(const int64_t*)) ? o->locus_ids : nullptr;
+    if (out->replicate < 0 || out->replicate >= kSimMaxReplicate) return fail(TPHIP_ERR_INVALID, "replicate must be in 0..65535");
+    return TPHIP_OK;
+}
+
+int parboot_read_opts(const tphip_parboot_opts* o, ParbootOpts* out) {
+    if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_parboot_opts");
+    if (o->struct_size < offsetof(tphip_parboot_opts, seed) + sizeof(uint64_t))
+        return fail(TPHIP_ERR_INVALID, "tphip_parboot_opts.struct_size is too small: set it to sizeof(tphip_parboot_opts)");
+    out->replicates = o->replicates;
+    out->level = o->level;
+    out->seed = o->seed;
+    out->locus_ids = (o->struct_size >= offsetof(tphip_parboot_opts, locus_ids) + sizeof(const int64_t*)) ? o->locus_ids : nullptr;
+    if (out->replicates < 2 || out->replicates > kParbootMaxReplicates)
+        return fail(TPHIP_ERR_INVALID, "parametric bootstrap replicates must be in 2..4096");
+    if (!(out->level > 0.0 && out->level < 1.0)) return fail(TPHIP_ERR_INVALID, "parametric bootstrap level must be in (0, 1)");
+    return TPHIP_OK;
+}
+
+// what the plan must be for the simulation, and its tree as the kernel reads it (made once per plan)
+int sim_prepare(tphip_plan* p) {
+    if (p->ncat > 1)
+        return fail(TPHIP_ERR_INVALID, "the simulation has no rate mixture: a plan with ncat > 1 cannot be simulated from");
+    if (p->max_locus_cols >= ((int64_t)1 << 32)) return fail(TPHIP_ERR_INVALID, "a locus of 2^32 columns or more cannot be simulated");
+    if (p->d_sim_nodes) return TPHIP_OK;
+    const tphip_plan_desc* d = tphip_internal_saved_desc(p);
+    if (!d) return fail(TPHIP_ERR_INVALID, "plan without a saved descriptor");
+    const int32_t nn = d->nnodes;
+    if (nn >= kSimMaxNodes) return fail(TPHIP_ERR_INVALID, "trees of 2^17 nodes or more cannot be simulated");
+    std::vector<int32_t> slot((size_t)nn, -1);
+    int32_t nint = 0;
+    for (int32_t n = nn - 1; n >= 0; --n)
+        if (d->leaf_taxon[n] < 0) slot[(size_t)n] = nint++;
+    std::vector<SimNode> nodes((size_t)nn);
+    for (int32_t n = 0; n < nn; ++n) {
+        SimNode& s = nodes[(size_t)n];
+        s.pslot = d->parent[n] < 0 ? -1 : slot[(size_t)d->parent[n]];
+        s.self = d->leaf_taxon[n] >= 0 ? d->leaf_taxon[n] : ~slot[(size_t)n];
+        s.t = d->parent[n] < 0 ? 0.0 : d->branch_len[n];
+    }
+    const int32_t words = (nint + 15) / 16;
+    int32_t block = kSimMaxBlock;
+    while (block > kSimMinBlock && (size_t)words * (size_t)block * sizeof(uint32_t) > kSimLdsBytes) block >>= 1;
+    if ((size_t)words * (size_t)block * sizeof(uint32_t) > kSimLdsBytes)
+        return fail(TPHIP_ERR_INVALID, "tree has " + std::to_string(nint) + " internal nodes: the simulation kernel keeps the 2-bit states of at "
+                                       "most 10240 per column (64 columns in 160 KiB of LDS)");
+    HIP_TRY(hipSetDevice(p->device));
+    void* dn = nullptr;
+    HIP_TRY(hipMalloc(&dn, sizeof(SimNode) * (size_t)nn));
+    hipError_t e = hipMemcpy(dn, nodes.data(), sizeof(SimNode) * (size_t)nn, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dn);
+        return fail(TPHIP_ERR_HIP, std::string("hipMemcpy of the simulation tree: ") + hipGetErrorString(e));
+    }
+    p->d_sim_nodes = dn;
+    p->sim_block = block;
+    p->sim_words = words;
+    return TPHIP_OK;
+}
+
+// stream ids to the device (read now: the caller's array need not outlive the call); *d_ids = null without ids
+int sim_stage_ids(tphip_plan* p, const int64_t* locus_ids, hipStream_t st, const int64_t** d_ids) {
+    *d_ids = nullptr;
+    if (!locus_ids) return TPHIP_OK;
+    if (!p->d_sim_ids) HIP_TRY(hipMalloc((void**)&p->d_sim_ids, sizeof(int64_t) * (size_t)p->nloci));
+    HIP_TRY(hipMemcpyAsync(p->d_sim_ids, locus_ids, sizeof(int64_t) * (size_t)p->nloci, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *d_ids = p->d_sim_ids;
+    return TPHIP_OK;
+}
+
+int sim_launch(const tphip_plan* p, const double* d_rates, const uint8_t* d_mask, const int64_t* d_ids, uint32_t replicate,
+               uint64_t seed, uint8_t* d_out, hipStream_t st) {
+    if (p->n_pi_chunks == 0) return TPHIP_OK;
+    SimParams S;
+    S.rates = d_rates; S.mask = d_mask; S.out = d_out; S.ncols = p->ncols;
+    S.models = p->d_models.p; S.locus_offsets = p->d_offsets.p;
+    S.chunk_locus = p->d_pi_chunk_locus.p; S.chunk_index = p->d_pi_chunk_index.p;
+    S.locus_ids = d_ids;
+    S.nodes = (const SimNode*)p->d_sim_nodes;
+    S.nnodes = tphip_internal_saved_desc(p)->nnodes;
+    S.f81 = p->model == TPHIP_MODEL_F81 ? 1 : 0;
+    S.replicate = replicate;
+    S.key0 = (uint32_t)seed ^ kSimKeyTag;
+    S.key1 = (uint32_t)(seed >> 32);
+    const size_t lds = (size_t)p->sim_words * (size_t)p->sim_block * sizeof(uint32_t);
+    if (lds > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void*)simulate_columns_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    simulate_columns_kernel<<<dim3((unsigned)p->n_pi_chunks, (unsigned)(kSimChunk / p->sim_block)), dim3((unsigned)p->sim_block), lds, st>>>(S);
+    HIP_TRY(hipGetLastError());
+    return TPHIP_OK;
+}
+
+// workspace of tphip_pi_parametric_bootstrap_dev: one replicate of states, the per-column outputs of the site-rate stage, one
+// table, the rows, the moments and the plan's own workspace
+struct ParbootLayout {
+    size_t states, rate, subst, lnl, flag, nres, tables, rows, mean, m2, plan_ws, total;
+};
+
+ParbootLayout parboot_layout(const tphip_plan* p, int32_t B) {
+    ParbootLayout L;
+    const size_t n = (size_t)p->ncols, W = (size_t)(p->T + p->n_t + 2 * p->n_i), Wb = (size_t)(p->T + p->n_i);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off = align_up(off + bytes, kSimAlign); return at; };
+    L.states = take((size_t)p->ntaxa * n);
+    L.rate = take(sizeof(double) * n);
+    L.subst = take(sizeof(double) * n);
+    L.lnl = take(sizeof(double) * n);
+    L.flag = take(n);
+    L.nres = take(sizeof(int32_t) * n);
+    L.tables = take(sizeof(double) * (size_t)p->nloci * W);
+    L.rows = take(sizeof(double) * (size_t)p->nloci * (size_t)B * Wb);
+    L.mean = take(sizeof(double) * n);
+    L.m2 = take(sizeof(double) * n);
+    L.plan_ws = take(p->ws_total);
+    L.total = off + kSimAlign;   // the caller's pointer is aligned up
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tphip_simulate_columns_dev(tphip_plan* p, const double* d_rates, const uint8_t* d_mask, const tphip_simulate_opts* opts,
+                               uint8_t* d_states_out, void* stream) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    SimOpts o;
+    int rc = sim_read_opts(opts, &o);
+    if (rc) return rc;
+    rc = sim_prepare(p);
+    if (rc) return rc;
+    if (p->ncols == 0) return TPHIP_OK;
+    if (!d_rates || !d_states_out) return fail(TPHIP_ERR_INVALID, "null device pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t* d_ids = nullptr;
+    rc = sim_stage_ids(p, o.locus_ids, st, &d_ids);
+    if (rc) return rc;
+    return sim_launch(p, d_rates, d_mask, d_ids, (uint32_t)o.replicate, o.seed, d_states_out, st);
+}
+
+int tphip_simulate_columns(tphip_plan* p, const double* rates, const uint8_t* mask, const tphip_simulate_opts* opts, uint8_t* states_out) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    SimOpts o;
+    int rc = sim_read_opts(opts, &o);
+    if (rc) return rc;
+    const size_t n = (size_t)p->ncols, cells = (size_t)p->ntaxa * n;
+    if (n && (!rates || !states_out)) return fail(TPHIP_ERR_INVALID, "null host pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    Scratch S;
+    double* d_r = S.get<double>(n);
+    uint8_t* d_m = mask ? S.get<uint8_t>(cells) : nullptr;
+    uint8_t* d_o = S.get<uint8_t>(cells);
+    if (!d_r || (mask && !d_m) || !d_o) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
+    if (n) {
+        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
+        if (mask) HIP_TRY(hipMemcpy(d_m, mask, cells, hipMemcpyHostToDevice));
+    }
+    rc = tphip_simulate_columns_dev(p, d_r, d_m, opts, d_o, nullptr);
+    if (rc) return rc;
+    if (n) HIP_TRY(hipMemcpy(states_out, d_o, cells, hipMemcpyDeviceToHost));
+    return TPHIP_OK;
+}
+
+int tphip_parboot_workspace_bytes(const tphip_plan* p, const tphip_parboot_opts* opts, size_t* bytes) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    ParbootOpts o;
+    int rc = parboot_read_opts(opts, &o);
+    if (rc) return rc;
+    if (bytes) *bytes = parboot_layout(p, o.replicates).total;
+    return TPHIP_OK;
+}
+
+int tphip_pi_parametric_bootstrap_dev(tphip_plan* p, const double* d_rates, const uint8_t* d_states_observed,
+                                      const tphip_parboot_opts* opts, double* d_summary, double* d_rows, double* d_rate_mean,
+                                      double* d_rate_sd, void* ws, size_t ws_bytes, void* stream) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    ParbootOpts o;
+    int rc = parboot_read_opts(opts, &o);
+    if (rc) return rc;
+    rc = sim_prepare(p);
+    if (rc) return rc;
+    if (!d_states_observed && p->ncols) return fail(TPHIP_ERR_INVALID, "null observed alignment: its pattern of missing cells is part of the bootstrap");
+    if (!d_summary || !ws || (p->ncols && !d_rates)) return fail(TPHIP_ERR_INVALID, "null device pointer");
+    const int32_t B = o.replicates, Wb = p->T + p->n_i, W = p->T + p->n_t + 2 * p->n_i;
+    const ParbootLayout L = parboot_layout(p, B);
+    const uintptr_t a = (uintptr_t)ws, al = (a + kSimAlign - 1) / kSimAlign * kSimAlign;
+    if (ws_bytes < L.total - kSimAlign + (size_t)(al - a))
+        return fail(TPHIP_ERR_INVALID, "workspace smaller than tphip_parboot_workspace_bytes()");
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)al;
+    const int64_t* d_ids = nullptr;
+    rc = sim_stage_ids(p, o.locus_ids, st, &d_ids);
+    if (rc) return rc;
+    uint8_t* states = (uint8_t*)(base + L.states);
+    double* rate = (double*)(base + L.rate);
+    double* subst = (double*)(base + L.subst);
+    double* lnl = (double*)(base + L.lnl);
+    uint8_t* flag = (uint8_t*)(base + L.flag);
+    int32_t* nres = (int32_t*)(base + L.nres);
+    double* tables = (double*)(base + L.tables);
+    double* rows = d_rows ? d_rows : (double*)(base + L.rows);
+    MomentParams M;
+    M.pi.rates = rate; M.pi.nres = nres; M.pi.locus_offsets = p->d_offsets.p;
+    M.pi.chunk_locus = nullptr; M.pi.chunk_index = nullptr;
+    M.pi.T = p->T; M.pi.intervals = p->d_intervals.p; M.pi.n_i = p->n_i; M.pi.integ_mode = p->integ_mode;
+    M.pi.correction = p->correction; M.pi.threshold = p->threshold;
+    M.pi.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
+    M.pi.partial = nullptr;
+    M.ncols = p->ncols; M.B = B;
+    M.mean = (double*)(base + L.mean); M.m2 = (double*)(base + L.m2);
+    M.out_mean = d_rate_mean; M.out_sd = d_rate_sd;
+    for (int32_t b = 0; b < B; ++b) {
+        rc = sim_launch(p, d_rates, d_states_observed, d_ids, (uint32_t)b, o.seed, states, st);
+        if (rc) return rc;
+        rc = tphip_run_dev(p, states, rate, subst, lnl, flag, nres, tables, base + L.plan_ws, p->ws_total, stream);
+        if (rc) return rc;
+        if (Wb > 0) parboot_rows_kernel<<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(tables, W, p->T, p->n_t, p->n_i, b, B, rows);
+        if (p->ncols > 0) {
+            M.b = b;
+            rate_moments_kernel<<<dim3((unsigned)((p->ncols + 255) / 256)), dim3(256), 0, st>>>(M);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return tphip_summarize_rows_dev(p->device, rows, p->nloci, B, Wb, o.level, d_summary, stream);
+}
+
+int tphip_pi_parametric_bootstrap(tphip_plan* p, const double* rates, const uint8_t* states_observed, const tphip_parboot_opts* opts,
+                                  double* summary, double* rows, double* rate_mean, double* rate_sd) {
+    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
+    ParbootOpts o;
+    int rc = parboot_read_opts(opts, &o);
+    if (rc) return rc;
+    const size_t n = (size_t)p->ncols, cells = (size_t)p->ntaxa * n, Wb = (size_t)(p->T + p->n_i), L = (size_t)p->nloci,
+                 B = (size_t)o.replicates;
+    if (!states_observed && n) return fail(TPHIP_ERR_INVALID, "null observed alignment: its pattern of missing cells is part of the bootstrap");
+    if (!summary || (n && !rates)) return fail(TPHIP_ERR_INVALID, "null host pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t ws_bytes = parboot_layout(p, o.replicates).total;
+    Scratch S;
+    double* d_r = S.get<double>(n);
+    uint8_t* d_s = S.get<uint8_t>(cells);
+    double* d_sum = S.get<double>(L * 4 * Wb);
+    double* d_rows = rows ? S.get<double>(L * B * Wb) : nullptr;
+    double* d_mean = rate_mean ? S.get<double>(n) : nullptr;
+    double* d_sd = rate_sd ? S.get<double>(n) : nullptr;
+    char* ws = S.get<char>(ws_bytes);
+    if (!d_r || !d_s || !d_sum || (rows && !d_rows) || (rate_mean && !d_mean) || (rate_sd && !d_sd) || !ws)
+        return fail(TPHIP_ERR_HIP, "hipMalloc failed");
+    if (n) {
+        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_s, states_observed, cells, hipMemcpyHostToDevice));
+    }
+    rc = tphip_pi_parametric_bootstrap_dev(p, d_r, d_s, opts, d_sum, d_rows, d_mean, d_sd, ws, ws_bytes, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(summary, d_sum, sizeof(double) * L * 4 * Wb, hipMemcpyDeviceToHost));
+    if (rows) HIP_TRY(hipMemcpy(rows, d_rows, sizeof(double) * L * B * Wb, hipMemcpyDeviceToHost));
+    if (rate_mean && n) HIP_TRY(hipMemcpy(rate_mean, d_mean, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (rate_sd && n) HIP_TRY(hipMemcpy(rate_sd, d_sd, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return TPHIP_OK;
+}
+
+}  // extern "C"

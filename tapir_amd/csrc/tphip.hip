@@ -62,6 +62,8 @@ int tphip_plan_destroy(tphip_plan* plan) {
     if (plan->d_part) { (void)hipFree(plan->d_part); plan->d_part = nullptr; }
     if (plan->d_col_weight) { (void)hipFree(plan->d_col_weight); plan->d_col_weight = nullptr; }
     if (plan->d_eb_ws) { (void)hipFree(plan->d_eb_ws); plan->d_eb_ws = nullptr; }
+    if (plan->d_sim_nodes) { (void)hipFree(plan->d_sim_nodes); plan->d_sim_nodes = nullptr; }
+    if (plan->d_sim_ids) { (void)hipFree(plan->d_sim_ids); plan->d_sim_ids = nullptr; }
     if (plan->d_grad_params) { (void)hipFree(plan->d_grad_params); plan->d_grad_params = nullptr; }
     plan->d_grad2_fops.release(); plan->d_grad2_rops.release();
     if (plan->d_grad2_ws) { (void)hipFree(plan->d_grad2_ws); plan->d_grad2_ws = nullptr; }

@@ -134,6 +134,11 @@ struct tphip_plan {
     void* d_grad2_params = nullptr;
     void* d_eb_ws = nullptr;         // workspace of the empirical-Bayes calls (eb_driver.hip), grown on demand
     size_t eb_ws_bytes = 0;
+    // simulation kernel (simulate_driver.hip), made on first use: the tree as SimNode[nnodes], the workgroup size at which the
+    // packed states of its internal nodes fit the LDS and their words per column; the stream ids of a call with locus_ids
+    void* d_sim_nodes = nullptr;
+    int32_t sim_block = 0, sim_words = 0;
+    int64_t* d_sim_ids = nullptr;
     double* d_col_weight = nullptr;  // optional column multiplicities for the locus likelihood / gradient kernels
     double* d_part = nullptr;   // per-slice partial sums of the locus likelihood / gradient kernels, grown on demand
     size_t part_bytes = 0;

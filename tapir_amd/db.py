@@ -91,11 +91,12 @@ BOOTSTRAP_DDL = [
 ]
 
 
-def write_bootstrap_db(db_name, names, summary, T, times, intervals, replicates, seed, level):
+def write_bootstrap_db(db_name, names, summary, T, times, intervals, replicates, seed, level, method=None):
     """phylogenetic-informativeness-bootstrap.sqlite, a file of its own beside the main database (which stays byte for
     byte what it is without --bootstrap).  summary [L, 4, T + n_i] = mean, sd, lo, hi per locus (pipeline.bootstrap_tables);
     the --times rows are the net rows at those times.  Loci get the ids 1..L in file order, as in the main database.
-    Bulk inserts as in insert_tables."""
+    Bulk inserts as in insert_tables.  method: None for the site bootstrap; "parametric" writes the same tables for
+    phylogenetic-informativeness-parametric-bootstrap.sqlite (pipeline.parametric_bootstrap_tables) with a `method` row in meta."""
     import numpy as np
     if os.path.exists(db_name):
         os.remove(db_name)
@@ -124,6 +125,8 @@ def write_bootstrap_db(db_name, names, summary, T, times, intervals, replicates,
                       zip(np.repeat(keys, n_i).tolist(), labels * L, *stats(summary[:, :, T:])))
     c.executemany("INSERT INTO meta VALUES (?,?)", [("replicates", str(int(replicates))), ("seed", str(int(seed))),
                                                     ("level", repr(float(level)))])
+    if method is not None:
+        c.execute("INSERT INTO meta VALUES (?,?)", ("method", str(method)))
     conn.commit()
     c.close()
     conn.close()

@@ -58,6 +58,15 @@ class QuartetOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("tip", _vp), ("internode", _vp)]
 
 
+class SimulateOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("replicate", _i32), ("seed", ctypes.c_uint64), ("locus_ids", _vp)]
+
+
+class ParbootOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("replicates", _i32), ("level", _f64), ("seed", ctypes.c_uint64),
+                ("locus_ids", _vp)]
+
+
 # every symbol include/tphip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("tphip_version", ctypes.c_int, []),
@@ -125,6 +134,14 @@ SYMBOLS = [
     ("tphip_quartet_sites_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp, _vp]),
     ("tphip_quartet_tables", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp]),
     ("tphip_quartet_sites", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp]),
+    ("tphip_simulate_columns_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp, _vp]),
+    ("tphip_simulate_columns", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp]),
+    ("tphip_parboot_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ParbootOpts), ctypes.POINTER(ctypes.c_size_t)]),
+    ("tphip_pi_parametric_bootstrap_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ParbootOpts), _vp, _vp, _vp, _vp, _vp,
+                                                         ctypes.c_size_t, _vp]),
+    ("tphip_pi_parametric_bootstrap", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ParbootOpts), _vp, _vp, _vp, _vp]),
+    ("tphip_summarize_rows_dev", ctypes.c_int, [_i32, _vp, _i64, _i32, _i32, _f64, _vp, _vp]),
+    ("tphip_summarize_rows", ctypes.c_int, [_i32, _vp, _i64, _i32, _i32, _f64, _vp]),
 ]
 
 _lib = None
@@ -698,6 +715,89 @@ class Plan:
         opts, keep = self._quartet_opts(quartets)
         _check(self._lib.tphip_quartet_sites_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
 
+    # ---- parametric bootstrap of site rates and PI rows (csrc/simulate_driver.hip) ---------------
+    def _ids(self, locus_ids):
+        if locus_ids is None:
+            return None
+        ids = _np(locus_ids, np.int64).reshape(-1)
+        if ids.size != self.nloci:
+            raise TphipError("locus_ids must have one entry per locus of the plan")
+        return ids
+
+    def simulate_columns(self, rates, mask=None, replicate=0, seed=1, locus_ids=None):
+        """Alignment columns simulated down the plan's tree (tphip_simulate_columns): column c under its locus' model at the
+        raw rate rates[c] (kappa * s, the unit of site_rates()["rate"]; NaN, negative or infinite: a column of 15s).  mask:
+        uint8 [ntaxa, ncols] observed alignment whose cells that are not a single base (gaps, ambiguity codes) are copied
+        through.  Returns uint8 [ntaxa, ncols].  A column's bytes depend on seed, its locus' stream id (locus_ids, default the
+        locus index), its index in the locus, replicate, its rate, the model, the tree and its mask only."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        if mask is not None:
+            mask = _np(mask, np.uint8)
+            assert mask.shape == (self.ntaxa, self.ncols), (mask.shape, self.ntaxa, self.ncols)
+        ids = self._ids(locus_ids)
+        opts = SimulateOpts(struct_size=ctypes.sizeof(SimulateOpts), replicate=int(replicate), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            locus_ids=_ptr(ids))
+        out = np.empty((self.ntaxa, self.ncols), np.uint8)
+        _check(self._lib.tphip_simulate_columns(self._h, rates.ctypes.data, _ptr(mask), ctypes.byref(opts), out.ctypes.data))
+        return out
+
+    def simulate_columns_dev(self, d_rates, d_mask, d_states_out, replicate=0, seed=1, locus_ids=None, stream=0):
+        """tphip_simulate_columns_dev on device tensors (d_mask may be None); enqueues on `stream`."""
+        ids = self._ids(locus_ids)
+        opts = SimulateOpts(struct_size=ctypes.sizeof(SimulateOpts), replicate=int(replicate), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            locus_ids=_ptr(ids))
+        _check(self._lib.tphip_simulate_columns_dev(self._h, _ptr(d_rates), _ptr(d_mask), ctypes.byref(opts), _ptr(d_states_out),
+                                                    stream))
+
+    def _parboot_opts(self, replicates, seed, level, locus_ids):
+        ids = self._ids(locus_ids)
+        opts = ParbootOpts(struct_size=ctypes.sizeof(ParbootOpts), replicates=int(replicates), level=float(level),
+                           seed=int(seed) & 0xFFFFFFFFFFFFFFFF, locus_ids=_ptr(ids))
+        return opts, ids
+
+    def parboot_workspace_bytes(self, replicates, seed=1, level=0.95):
+        """bytes of device workspace for pi_parametric_bootstrap_dev."""
+        opts, _ = self._parboot_opts(replicates, seed, level, None)
+        n = ctypes.c_size_t()
+        _check(self._lib.tphip_parboot_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
+        return n.value
+
+    def pi_parametric_bootstrap(self, rates, states, replicates=100, seed=1, level=0.95, locus_ids=None, return_rows=False,
+                                return_rate_moments=False):
+        """Parametric bootstrap of the site rates and the PI rows (tphip_pi_parametric_bootstrap): `replicates` times every
+        column is simulated at its raw rate rates[c] with the missing cells of `states` (the observed alignment), its rate
+        re-estimated and the PI row recomputed; the locus' model and the tree are held fixed.  Returns summary [L, 4, Wb]
+        (mean, sd, lo, hi); with return_rows the replicate rows [L, B, Wb]; with return_rate_moments (rate_mean, rate_sd) of
+        every column's final rate over the replicates, NaN for culled columns -- in that order."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        if states is not None:
+            states = _np(states, np.uint8)
+            assert states.shape == (self.ntaxa, self.ncols), (states.shape, self.ntaxa, self.ncols)
+        opts, ids = self._parboot_opts(replicates, seed, level, locus_ids)
+        Wb = self.bootstrap_width
+        summary = np.zeros((self.nloci, 4, Wb))
+        rows = np.zeros((self.nloci, int(replicates), Wb)) if return_rows else None
+        mean = np.empty(self.ncols) if return_rate_moments else None
+        sd = np.empty(self.ncols) if return_rate_moments else None
+        _check(self._lib.tphip_pi_parametric_bootstrap(self._h, rates.ctypes.data, _ptr(states), ctypes.byref(opts),
+                                                       summary.ctypes.data, _ptr(rows), _ptr(mean), _ptr(sd)))
+        out = (summary,)
+        if return_rows:
+            out += (rows,)
+        if return_rate_moments:
+            out += (mean, sd)
+        return out if len(out) > 1 else summary
+
+    def pi_parametric_bootstrap_dev(self, d_rates, d_states, d_summary, d_rows, d_rate_mean, d_rate_sd, d_ws, replicates, seed=1,
+                                    level=0.95, locus_ids=None, stream=0, ws_bytes=None):
+        """tphip_pi_parametric_bootstrap_dev on device tensors (d_rows / d_rate_mean / d_rate_sd may be None)."""
+        opts, ids = self._parboot_opts(replicates, seed, level, locus_ids)
+        nbytes = d_ws.numel() * d_ws.element_size() if ws_bytes is None else int(ws_bytes)
+        _check(self._lib.tphip_pi_parametric_bootstrap_dev(self._h, _ptr(d_rates), _ptr(d_states), ctypes.byref(opts), _ptr(d_summary),
+                                                           _ptr(d_rows), _ptr(d_rate_mean), _ptr(d_rate_sd), _ptr(d_ws), nbytes, stream))
+
     def profile_enable(self, on=True):
         _check(self._lib.tphip_profile_enable(self._h, 1 if on else 0))
 
@@ -736,6 +836,18 @@ def bootstrap_counts(n, rep0=0, nrep=1, seed=1, locus_id=0, device=0):
     _check(load().tphip_bootstrap_counts(device, int(seed) & 0xFFFFFFFFFFFFFFFF, int(locus_id), int(n), int(rep0), int(nrep),
                                          out.ctypes.data))
     return out
+
+
+def summarize_rows(rows, level=0.95, device=0):
+    """The bootstrap's summary kernel on any replicate rows [L, B, Wb] (tphip_summarize_rows): [L, 4, Wb] = mean, sd (B - 1 in
+    the denominator), and the quantiles at (1 - level) / 2 and 1 - (1 - level) / 2 by numpy's default rule."""
+    rows = _np(rows, np.float64)
+    if rows.ndim != 3:
+        raise TphipError("rows must be [L, B, Wb]")
+    L, B, Wb = rows.shape
+    summary = np.zeros((L, 4, Wb))
+    _check(load().tphip_summarize_rows(device, rows.ctypes.data, L, B, Wb, float(level), summary.ctypes.data))
+    return summary
 
 
 def state_histogram(states, locus_offsets, device=0):

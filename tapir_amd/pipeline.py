@@ -805,6 +805,81 @@ def bootstrap_tables(eng, per_locus, leaf_names, parent, blen, leaf, T, interval
         plan.close()
 
 
+PARBOOT_BLOCK_COLS = 1 << 24   # columns per plan of parametric_bootstrap_tables
+
+
+def parametric_bootstrap_tables(eng, alignments, per_locus, models, leaf_names, parent, blen, leaf, T, intervals, correction,
+                                threshold, round_decimals, device, integ_mode, locus_ids, replicates, seed=1, level=0.95,
+                                subsets=None, start_rule=0, output_dir=None):
+    """Parametric bootstrap of the site rates and the PI rows: every column of every locus is
+    simulated `replicates` times down the tree under the locus' model at its own rate, with the observed pattern of missing
+    cells, its rate re-estimated and the PI row recomputed.  Returns the summaries [L, 4, T + n_i] (mean, sd, lo, hi) and,
+    per locus, the (mean, sd) of every site's final rate over the replicates (NaN for culled sites); with output_dir the
+    latter are also written as NAME.rates-bootstrap.json beside the `.rates` files.
+
+    alignments: the loci's NEXUS files, re-read here and sliced as run_alignments slices the rates for `subsets`
+    (--subset-pi-map-file).  per_locus: the run's final rates (rounded, / correction, NaN = culled); the raw rate of the
+    simulation is final rate x correction, so a culled column comes out all missing and is culled again.  models:
+    run_alignments' out["models"].  The plans carry the run's real correction, threshold and round_decimals.  The loci go
+    through in blocks of at most 2^24 columns; a column's bytes do not depend on the loci beside it, so the blocking changes
+    no bit.  locus_ids: the generator's stream ids -- the command line passes the global file indices.  The models and the
+    tree are held fixed (no stage-1 refit per replicate): the bands are conditional on the fitted substitution model."""
+    subsets = subsets or {}
+    L, Wb = len(alignments), T + len(intervals)
+    summary = np.zeros((L, 4, Wb))
+    moments = []
+    if L == 0:
+        return summary, moments
+    model = models["model"]
+    pi = np.asarray(models["pi"], dtype=np.float64).reshape(L, 4)
+    exch = None if model == "f81" else np.asarray(models["exch"], dtype=np.float64).reshape(L, 6)
+    ids = np.asarray(locus_ids, dtype=np.int64)
+    extra = dict(start_rule=int(start_rule)) if start_rule else {}
+    l0 = 0
+    while l0 < L:
+        l1, cols = l0, 0
+        while l1 < L and (l1 == l0 or cols + len(per_locus[l1]) <= PARBOOT_BLOCK_COLS):
+            cols += len(per_locus[l1])
+            l1 += 1
+        states, off = load_alignments(alignments[l0:l1], leaf_names)
+        blocks = []
+        for k, a in enumerate(alignments[l0:l1]):
+            blk = states[:, off[k]:off[k + 1]]
+            base = os.path.basename(a)
+            if base in subsets:
+                blk = blk[:, subsets[base][0]:subsets[base][1]]
+            if blk.shape[1] != len(per_locus[l0 + k]):
+                raise PipelineError("{0}: {1} columns, but {2} final rates".format(base, blk.shape[1], len(per_locus[l0 + k])))
+            blocks.append(blk)
+        states = np.ascontiguousarray(np.concatenate(blocks, axis=1))
+        offsets = np.concatenate([[0], np.cumsum([b.shape[1] for b in blocks])]).astype(np.int64)
+        raw = np.concatenate(per_locus[l0:l1]) * correction
+        plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi[l0:l1], None if exch is None else exch[l0:l1], T, [],
+                        intervals, correction=correction, threshold=threshold, round_decimals=round_decimals,
+                        integ_mode=integ_mode, device=device, model=model, **extra)
+        try:
+            s, mean, sd = plan.pi_parametric_bootstrap(raw, states, replicates=replicates, seed=seed, level=level,
+                                                       locus_ids=ids[l0:l1], return_rate_moments=True)
+        finally:
+            plan.close()
+        summary[l0:l1] = s
+        for k in range(l1 - l0):
+            moments.append((mean[offsets[k]:offsets[k + 1]], sd[offsets[k]:offsets[k + 1]]))
+        l0 = l1
+    if output_dir is not None:
+        for a, (mean, sd) in zip(alignments, moments):
+            _write_rate_moments_file(os.path.join(output_dir, os.path.basename(a) + ".rates-bootstrap.json"), mean, sd)
+    return summary, moments
+
+
+def _write_rate_moments_file(path, mean, sd):
+    """NAME.rates-bootstrap.json: mean and sd of every site's final rate over the parametric replicates, null for culled sites."""
+    import json
+    clean = lambda v: [None if x != x else x for x in np.asarray(v, dtype=np.float64).tolist()]   # noqa: E731
+    with open(path, "w") as fh:
+        json.dump({"mean": clean(mean), "sd": clean(sd)}, fh)
+
+
 def quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr"):
     """Quartet signal and noise rows [L, n_q, 8] (Y, X, Yy, Xx, XY, p_correct, p_incorrect, p_polytomy; DESIGN.md section
     3.6) for already-final rates (NaN = culled), on a no-rounding plan exactly as bootstrap_tables: every path that ends in
