@@ -540,6 +540,15 @@ static void build_model(const double pi[4], const double exch[6], orc_model *m) 
     for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) S[i][j] = sq[i] * Q[i][j] / sq[j];
     for (int i = 0; i < 4; ++i) for (int j = i + 1; j < 4; ++j) S[i][j] = S[j][i] = 0.5 * (S[i][j] + S[j][i]);
     jacobi4(S, V, m->lam);
+    /* The stationary eigenvalue is 0 exactly (rows of Q sum to 0; the other three are negative); Jacobi leaves ~1e-14 there,
+     * and transition() would multiply every row by exp(1e-14 t s): a relative error of 1e-14 t s per branch in every
+     * likelihood, 1e-8 and more in log L once t s reaches 1e6 on a long branch at a large rate.  The device makes it exact
+     * too (gtr_model.hpp). */
+    {
+        int k0 = 0;
+        for (int k = 1; k < 4; ++k) if (m->lam[k] > m->lam[k0]) k0 = k;
+        m->lam[k0] = 0.0;
+    }
     for (int i = 0; i < 4; ++i) for (int k = 0; k < 4; ++k) {
         m->U[i][k] = V[i][k] / sq[i];
         m->Ui[k][i] = V[i][k] * sq[i];

@@ -26,6 +26,9 @@ from scipy import integrate
 DPS = 40
 mp = mpmath.mp
 PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))   # exchangeability order AC, AG, AT, CG, CT, GT
+# A base composition far from uniform, shared by the deep-tree tests: a saturated rare base costs a partial 5.6 bits per tip.
+SKEW_PI = [0.02, 0.02, 0.02, 0.94]
+SKEW_EXCH = [1.0, 2.0, 0.5, 1.5, 3.0, 1.0]
 
 
 def floored_pi(pi, floor=1e-12):
@@ -110,10 +113,14 @@ def kappa(pi, exch=None, model="gtr"):
     return float(_Model(pi, exch, model).kappa)
 
 
-def column_curves(states, parent, blen, leaf_taxon, pi, exch, u, model="gtr"):
+def column_curves(states, parent, blen, leaf_taxon, pi, exch, u, model="gtr", small_nodes=False):
     """f, g, h of every column of `states` (uint8 masks [ntaxa, ncols]) at every u: float arrays [len(u), ncols].
     parent / blen / leaf_taxon: post-order tree arrays (root last), as the engine takes them.  pi is used as given
-    (normalised to sum 1): a GTR plan floors absent bases first, see floored_pi."""
+    (normalised to sum 1): a GTR plan floors absent bases first, see floored_pi.
+    small_nodes=True appends two int arrays [len(u), ncols]: the number of non-root nodes whose (unscaled) partial has its
+    largest component below 2^-256, and below 2^-512.  The kernels rescale a running partial below 2^-256 before it goes up
+    a branch, so a pair with a count of 0 is evaluated without rescaling and one with a node below 2^-512 rescales more
+    than once; the root's partial goes up no branch and is not counted."""
     states = np.asarray(states, np.uint8)
     ntaxa, ncols = states.shape
     parent = np.asarray(parent)
@@ -134,7 +141,9 @@ def column_curves(states, parent, blen, leaf_taxon, pi, exch, u, model="gtr"):
     F = np.empty((len(u), ncols))
     G = np.empty_like(F)
     H = np.empty_like(F)
+    below = np.zeros((2, len(u), ncols), np.int64)
     with mp.workdps(DPS):
+        limits = (mpmath.ldexp(one, -256), mpmath.ldexp(one, -512))
         for iu, uu in enumerate(u):
             s = mpmath.exp(mpmath.mpf(float(uu)))
             part = [None] * nn
@@ -152,6 +161,11 @@ def column_curves(states, parent, blen, leaf_taxon, pi, exch, u, model="gtr"):
                 if parent[n] < 0:
                     part[n] = (v, d1, d2)
                     continue
+                if small_nodes and d1 is not None:     # (a tip's largest component is 1)
+                    for c in range(ncols):
+                        top = max(v[:, c])
+                        below[0, iu, c] += top < limits[0]
+                        below[1, iu, c] += top < limits[1]
                 P, P1, P2 = M.matrices(mpmath.mpf(float(blen[n])) * s)
                 if d1 is None:           # a tip: its vector does not depend on u
                     part[n] = (P.dot(v), P1.dot(v), P2.dot(v))
@@ -165,6 +179,8 @@ def column_curves(states, parent, blen, leaf_taxon, pi, exch, u, model="gtr"):
                 F[iu, c] = float(mpmath.log(L[c]))
                 G[iu, c] = float(g)
                 H[iu, c] = float(L2[c] / L[c] - g * g)
+    if small_nodes:
+        return F, G, H, below[0], below[1]
     return F, G, H
 
 

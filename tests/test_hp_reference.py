@@ -9,6 +9,7 @@ import pytest
 
 import fast_exp_emulation as fexp
 import hp_reference as hp
+import test_gpu_numerics as num
 
 
 def test_column_curves_agree_with_the_oracle(oracle):
@@ -27,6 +28,43 @@ def test_column_curves_agree_with_the_oracle(oracle):
             assert np.all(np.abs(g - G[:, c]) <= 1e-10 * (1.0 + np.abs(H[:, c]))), (model, c)
             assert np.all(np.abs(h - H[:, c]) <= 1e-10 * (1.0 + np.abs(H[:, c]))), (model, c)
         assert abs(hp.kappa(d["pi"][0], ex) - oracle.gtr_eigen(d["pi"][0], ex)[3]) < 1e-15
+
+
+DEEP_MODELS = [  # (name, pi, exchangeabilities for the oracle, the reference's exch, the reference's model)
+    ("gtr", num.MODELS[0][2], num.MODELS[0][3], num.MODELS[0][3], "gtr"),
+    ("gtr_skewed", hp.SKEW_PI, hp.SKEW_EXCH, hp.SKEW_EXCH, "gtr"),
+    ("f81_skewed", hp.SKEW_PI, [1.0] * 6, None, "f81"),    # the oracle's stand-in for F81: exchangeabilities of 1
+]
+DEEP_U = [-3.0, 0.0, 3.0, num.U_MAX, 17.0, 25.0]
+# of test_gpu_numerics._columns: all A, all T, all different, one resolved cell, IUPAC masks 2, 6, 13 and 15 (gaps) on every other
+# taxon, two random columns
+DEEP_COLUMNS = [0, 3, 4, 5, 8, 12, 19, 21, 22, 24]
+
+
+@pytest.mark.parametrize("ntaxa", [16, 64, 130, 300])
+@pytest.mark.parametrize("mname,pi,exch,ref_exch,ref_model", DEEP_MODELS, ids=[m[0] for m in DEEP_MODELS])
+def test_oracle_curve_on_deep_trees_at_far_rates(oracle, mname, pi, exch, ref_exch, ref_model, ntaxa):
+    """The rule of test_column_curves_agree_with_the_oracle where the parity tests trust the oracle and nothing checked it:
+    balanced trees of 16 to 300 taxa (the oracle rescales from 64 on) with a 1e-9 branch and a branch of 3000, u from -3
+    through kUMax to 25 (300 taxa: kUMax and 25 only, the reference takes 2.8 s per u there).  With the stationary eigenvalue
+    left at Jacobi's ~1e-14 instead of 0, exp(lam_0 t s) on the branch of 3000 cost the oracle 1.4e-8 of f at kUMax and
+    1.0e-1 at u = 25 (gtr, 16 taxa); with it exact the largest misses seen are 3.0e-13 in f (f81_skewed, 16 taxa, u = -3) and
+    2.1e-11 in g, h (f81_skewed, 130 taxa, u = -3)."""
+    rng = np.random.default_rng(1000 + ntaxa)
+    parent, blen, leaf = num._tree(num._balanced(list(range(ntaxa))), rng, tiny=0, long=1)
+    st = np.ascontiguousarray(num._columns(ntaxa, rng)[:, DEEP_COLUMNS])
+    u = np.array(DEEP_U[3::2] if ntaxa == 300 else DEEP_U)
+    F, G, H = hp.column_curves(st, parent, blen, leaf, pi, ref_exch, u, model=ref_model)
+    ef, egh = np.zeros_like(F), np.zeros_like(F)
+    for c in range(st.shape[1]):
+        f, g, h = oracle.column_curve(st, parent, blen, leaf, pi, exch, c, u)
+        ef[:, c] = np.abs(f - F[:, c]) / np.maximum(1.0, np.abs(F[:, c]))
+        egh[:, c] = np.maximum(np.abs(g - G[:, c]), np.abs(h - H[:, c])) / (1.0 + np.abs(H[:, c]))
+    print("oracle vs reference, %s, %d taxa, per u: |df| %s ; |dg|,|dh| %s" % (
+        mname, ntaxa, " ".join("%.1e" % v for v in ef.max(axis=1)), " ".join("%.1e" % v for v in egh.max(axis=1))))
+    assert np.isfinite(ef).all() and np.isfinite(egh).all()
+    assert ef.max() <= 1e-12, (np.unravel_index(ef.argmax(), ef.shape), ef.max())
+    assert egh.max() <= 1e-10, (np.unravel_index(egh.argmax(), egh.shape), egh.max())
 
 
 def test_oracle_site_rates_are_maxima_of_the_reference_curve(oracle):
