@@ -836,13 +836,15 @@ __global__ __launch_bounds__(256) void sub_direction_kernel(SubState S) {
     if (p >= S.Q || S.phase[p] != PH_LIVE) return;
     const int id = S.id[p], k = S.kk[id % kSubModels];
     double g[4], d[4], x[4];
+    bool held[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         g[a] = a < k ? S.g[(size_t)a * S.Q + p] : 0.0;
         x[a] = S.x[(size_t)a * S.Q + p];
         // a rate AT a bound whose gradient points out of the box is fixed for this iteration (projected gradient): without
         // this a fit whose optimum is at the bound never meets the stopping test and runs to the iteration limit
-        if ((x[a] <= kLogRateMin && g[a] > 0.0) || (x[a] >= kLogRateMax && g[a] < 0.0)) g[a] = 0.0;
+        held[a] = (x[a] <= kLogRateMin && g[a] > 0.0) || (x[a] >= kLogRateMax && g[a] < 0.0);
+        if (held[a]) g[a] = 0.0;
     }
     double gd = 0, gg = 0, gmax = 0;
 #pragma unroll
@@ -850,7 +852,9 @@ __global__ __launch_bounds__(256) void sub_direction_kernel(SubState S) {
         double s = 0;
 #pragma unroll
         for (int b = 0; b < 4; ++b) s = fma(S.Hinv[(size_t)(a * 4 + b) * S.Q + p], g[b], s);
-        d[a] = a < k ? fmax(fmin(-s, kMaxLogStep), -kMaxLogStep) : 0.0;
+        // the step of a held rate is 0 as well: through the off-diagonal metric it would move, sub_trial_kernel would clamp it,
+        // and the Armijo test would judge a step that was not taken with the slope of one that was
+        d[a] = (a < k && !held[a]) ? fmax(fmin(-s, kMaxLogStep), -kMaxLogStep) : 0.0;
         gd = fma(g[a], d[a], gd); gg = fma(g[a], g[a], gg); gmax = fmax(gmax, fabs(g[a]));
     }
     if (!(gd < 0)) {

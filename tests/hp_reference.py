@@ -15,6 +15,9 @@ what the reference program calls).
   d2 lnL / d (log t_b)^2 of any branch, analytic (the same three matrices, carried from the branch to the root past the stored
   sibling messages), and d lnL / d r_q of the six exchangeabilities by central differences inside mpmath at 60 digits with a
   relative step of 1e-18 (truncation and rounding both below 1e-30).
+* One rate-class model of stage 1, phi(theta) = lnL(exch(theta), t = b / totalFactor(exch(theta))), with gradient and Hessian in the free
+  log class rates by central differences at 60 digits (class_model_reference), and the 203 partitions, totalFactor and the Akaike
+  weights written out from their definitions (rate_partitions, partition_classes, total_factor, akaike_weights).
 * PI(t) = 16 r^2 t exp(-4 r t) and its exact integral G(4rb) - G(4ra), G(x) = -(1+x) exp(-x).
 """
 import math
@@ -81,7 +84,8 @@ class _Model:
                 # P_ij(tau) = sqrt(pi_j / pi_i) sum_k V_ik V_jk exp(lam_k tau)
                 self.B = [[[V[i, k] * V[j, k] * sq[j] / sq[i] for j in range(4)] for i in range(4)] for k in range(4)]
 
-    def matrices(self, tau):
+    def matrices(self, tau, derivs=True):
+        """derivs=False: P alone (the other two are None), a third of the work."""
         with mp.workdps(self.dps):
             P = np.empty((4, 4), object)
             P1 = np.empty((4, 4), object)
@@ -104,9 +108,11 @@ class _Model:
             for i in range(4):
                 for j in range(4):
                     P[i, j] = mpmath.fsum(terms[k][0] * self.B[k][i][j] for k in range(4))
+                    if not derivs:
+                        continue
                     P1[i, j] = mpmath.fsum(terms[k][1] * self.B[k][i][j] for k in range(4))
                     P2[i, j] = mpmath.fsum(terms[k][2] * self.B[k][i][j] for k in range(4))
-            return P, P1, P2
+            return (P, P1, P2) if derivs else (P, None, None)
 
 
 def kappa(pi, exch=None, model="gtr"):
@@ -213,8 +219,15 @@ def _locus_sweep(M, states, parent, blen, leaf_taxon, branches, want_derivs):
                 v = msg[c] if v is None else v * msg[c]
         part[n] = v
         if parent[n] >= 0:
-            mats[n] = M.matrices(mpmath.mpf(float(blen[n])))
-            msg[n] = mats[n][0].dot(v)
+            # (a length that is already mpf is taken as it is: class_model_reference moves it by 1e-15 of itself)
+            mats[n] = M.matrices(blen[n] if isinstance(blen[n], mpmath.mpf) else mpmath.mpf(float(blen[n])), want_derivs)
+            if leaf_taxon[n] >= 0:       # P v for a 0/1 vector: the sum of the mask's columns of P, once per mask
+                tab = np.empty((4, 16), object)
+                for mask in set(int(x) for x in m):
+                    tab[:, mask] = np.sum([mats[n][0][:, i] for i in range(4) if (mask >> i) & 1], axis=0)
+                msg[n] = tab[:, m.astype(int)]
+            else:
+                msg[n] = mats[n][0].dot(v)
     roots = [n for n in range(nn) if parent[n] < 0]
     assert roots == [nn - 1]
     pi_r = np.array(M.pi, object)
@@ -255,7 +268,8 @@ def locus_reference_columns(states, parent, blen, leaf, pi, exch, branches=None,
     made of these columns with weights w has lnL = sum w_c log L_c and the same sums for its derivatives."""
     dps = dps or DPS
     with mp.workdps(dps):
-        return _locus_sweep(_Model(floored_pi(pi), exch, "gtr", dps), states, parent, blen, leaf, branches, True)
+        want = branches is None or len(branches) > 0      # branches=[]: the values alone, a third of the matrix work
+        return _locus_sweep(_Model(floored_pi(pi), exch, "gtr", dps), states, parent, blen, leaf, branches, want)
 
 
 def locus_reference(states, weights, parent, blen, leaf, pi, exch, branches=None, dps=None, as_float=True):
@@ -303,6 +317,117 @@ def locus_dexch_reference(states, weights, parent, blen, leaf, pi, exch, dps=60,
         cols = locus_dexch_reference_columns(states, parent, blen, leaf, pi, exch, dps, step)
         out = [_wsum(weights, cols[q]) for q in range(6)]
         return np.array([float(x) for x in out]) if as_float else out
+
+
+# ---- the rate-class models of stage 1 ------------------------------------------------------------------------------
+
+def rate_partitions():
+    """The 203 partitions of the six rates (AC, AG, AT, CG, CT, GT) into classes as restricted growth strings (the first rate
+    is in class 0, every later one in a class seen before or in the next new one): the general model "012345" first, the
+    other 202 in lexicographic order, which is the order the engine documents (include/tphip.h, stage1_driver.hip)."""
+    import itertools
+    out = []
+    for tail in itertools.product(range(6), repeat=5):       # (lexicographic already)
+        s = (0,) + tail
+        if all(s[i] <= max(s[:i]) + 1 for i in range(1, 6)):
+            out.append("".join(str(c) for c in s))
+    out.remove("012345")
+    return ["012345"] + out
+
+
+def partition_classes(partition):
+    """(class of each of the six rates, k): -1 on the class that contains AG (fixed at 1), the k free classes numbered
+    0..k-1 in order of first appearance."""
+    ag, free = partition[1], []
+    for c in partition:
+        if c != ag and c not in free:
+            free.append(c)
+    return [-1 if c == ag else free.index(c) for c in partition], len(free)
+
+
+def total_factor(pi, exch, dps=None):
+    """HyPhy's totalFactor = sum over the six pairs of r_ij 2 pi_i pi_j: the expected substitutions per unit of branch length
+    of the unnormalised generator, so that t = b / totalFactor turns a length b in expected substitutions into the
+    generator's time (mpf; pi is normalised to sum 1 first; mpf exchangeabilities are taken as they are)."""
+    with mp.workdps(dps or DPS):
+        p = [mpmath.mpf(float(x)) for x in pi]
+        tot = mpmath.fsum(p)
+        return mpmath.fsum((r if isinstance(r, mpmath.mpf) else mpmath.mpf(float(r))) * 2 * p[i] * p[j] / (tot * tot)
+                           for (i, j), r in zip(PAIRS, exch))
+
+
+def akaike_weights(lnl, nfree, dps=None):
+    """w_m = exp(lnL_m - k_m) / sum_n exp(lnL_n - k_n) (mpf list): mpmath's exponent range needs no shift by the maximum."""
+    with mp.workdps(dps or DPS):
+        e = [mpmath.exp(mpmath.mpf(float(a)) - int(k)) for a, k in zip(lnl, nfree)]
+        tot = mpmath.fsum(e)
+        return [x / tot for x in e]
+
+
+def class_model_reference(states, weights, parent, b, leaf, pi, partition, theta, order=2, dps=60, step=1e-15):
+    """One rate-class model of stage 1 on one locus: phi(theta) = lnL(exch(theta), t = b / totalFactor(exch(theta))), where
+    exch_q = 1 on the class of AG and exp(theta_c) on free class c (partition_classes), b are the stashed branch lengths in
+    expected substitutions and pi is floored as a GTR plan floors it.  Returns (phi, gradient [k], Hessian [k][k]) as mpf
+    (order = 0: phi only, 1: no Hessian; the entries not asked for are None); k = 0 has a value only.
+
+    Derivatives are central differences of phi in theta with an ABSOLUTE step h = `step` at `dps` digits, from one stencil:
+    g_a = (f(+a) - f(-a)) / 2h, H_aa = (f(+a) - 2 f(0) + f(-a)) / h^2, H_ab = (f(+a+b) + f(-a-b) - f(+a) - f(-a) - f(+b) - f(-b)
+    + 2 f(0)) / 2h^2: 1 + 2k + k(k-1) values.  Choice of h: the truncation terms are h^2 f'''/6, h^2 f''''/12 and, for H_ab, h^2 times
+    a sum of fourth derivatives of the same size; the rounding terms are u |f| c / h for g and 4 u |f| c / h^2 for H, where
+    u = 10^-dps and c is the number of roundings one evaluation accumulates (measured: c is about 3).  phi is a sum over a few hundred columns of
+    logarithms that move by less than one per unit of theta each, so |f| and its derivatives of every order stay below ~10^3
+    on the loci of the tests (80 to 100 columns).  With h = 1e-15 and 60 digits: truncation <= 1e-30 * 10^3 = 1e-27, rounding of
+    H <= 4e-60 * 10^3 * 10^3 / 1e-30 = 4e-24 at the pessimistic c and 4e-27 at c = 1; rounding of g <= 1e-39.  All below 1e-25 for
+    c < 25, and test_class_model_reference_does_not_depend_on_its_precision measures it against 120 digits and h = 1e-17
+    (which cuts truncation by 10^4 and rounding by 10^56): nothing moves at 1e-25."""
+    cls, k = partition_classes(partition)
+    assert len(theta) == k
+    pif = floored_pi(pi)
+    with mp.workdps(dps):
+        h = mpmath.mpf(step)
+        th0 = [x if isinstance(x, mpmath.mpf) else mpmath.mpf(float(x)) for x in theta]
+        bb = [x if isinstance(x, mpmath.mpf) else mpmath.mpf(float(x)) for x in b]
+
+        def phi(shift):
+            th = [x + s * h for x, s in zip(th0, shift)]
+            exch = [mpmath.mpf(1) if c < 0 else mpmath.exp(th[c]) for c in cls]
+            tf = total_factor(pif, exch, dps)
+            t = [x / tf for x in bb]
+            logl = _locus_sweep(_Model(pif, exch, "gtr", dps), states, parent, t, leaf, None, False)[0]
+            return _wsum(weights, logl)
+
+        def unit(*idx, sign=1):
+            return [sign if a in idx else 0 for a in range(k)]
+
+        f0 = phi([0] * k)
+        if order == 0 or k == 0:
+            return f0, None, None
+        fp = [phi(unit(a)) for a in range(k)]
+        fm = [phi(unit(a, sign=-1)) for a in range(k)]
+        g = [(fp[a] - fm[a]) / (2 * h) for a in range(k)]
+        if order == 1:
+            return f0, g, None
+        H = [[None] * k for _ in range(k)]
+        for a in range(k):
+            H[a][a] = (fp[a] - 2 * f0 + fm[a]) / (h * h)
+            for c in range(a + 1, k):
+                both = phi(unit(a, c)) + phi(unit(a, c, sign=-1))
+                H[a][c] = H[c][a] = (both - fp[a] - fm[a] - fp[c] - fm[c] + 2 * f0) / (2 * h * h)
+        return f0, g, H
+
+
+def newton_gain(g, H, coords=None, dps=None):
+    """(1/2 g' (-H)^-1 g, smallest eigenvalue of -H) on the coordinates `coords` (default: all) as floats: what a Newton step
+    would still gain in phi from a point with gradient g and Hessian H, and whether -H is positive definite there."""
+    coords = list(range(len(g))) if coords is None else list(coords)
+    if not coords:
+        return 0.0, math.inf
+    with mp.workdps(dps or 60):
+        A = mpmath.matrix([[-H[a][c] for c in coords] for a in coords])
+        gv = mpmath.matrix([g[a] for a in coords])
+        lam = mpmath.eigsy(A, eigvals_only=True)
+        x = mpmath.lu_solve(A, gv)
+        return float((gv.T * x)[0] / 2), float(min(lam))
 
 
 # ---- PI ------------------------------------------------------------------------------------------------------------

@@ -630,7 +630,7 @@ def test_stage1_optimiser_against_independent_restatement(tmp_path):
         assert np.max(np.abs(got["exch"][l] - ref["exch"]) / ref["exch"]) < 1e-3
         lnl = np.array([ref["lnl"][m] for m in got["models"]])
         w = np.array([ref["weights"][m] for m in got["models"]])
-        keep = w > 1e-9   # models abandoned early (weight < e^-30) are not polished to their optimum
+        keep = w > 1e-9   # models abandoned early (weight < e^-21) are not polished to their optimum
         assert np.max(np.abs(lnl - got["lnl"][l])[keep]) < 1e-3
         assert np.all(got["lnl"][l] <= lnl + 1e-3)
         assert np.max(np.abs(w - got["weights"][l])) < 1e-4

@@ -262,3 +262,130 @@ def test_locus_reference_does_not_depend_on_its_precision():
         r = mpmath.mpf(1) + mpmath.mpf("1e-18")
         Q = hp.rate_matrix([0.25] * 4, [r] + [1.0] * 5, dps=60)[0]
         assert Q[0, 1] != Q[0, 2] and abs(Q[0, 1] / Q[0, 2] - r) < mpmath.mpf("1e-50")
+
+
+# ---- the rate-class models of stage 1 --------------------------------------------------------------------------------
+
+_CLASS = {}
+
+
+def _class_case():
+    """Locus 0 of synth.simulate(2, 80, 5, 23, rate_mean=0.01) as site patterns with counts (47 patterns), its tree, its
+    empirical base frequencies, and the restatement's fit of all 203 models (about 8 s, once)."""
+    if not _CLASS:
+        from oracle import stage1_oracle
+        from tapir_amd import synth
+        d = synth.simulate(2, 80, 5, 23, rate_mean=0.01)
+        pin = synth.plan_inputs(d["root"], d["names"])
+        st = d["states"].numpy()[:, :80]
+        pat, cnt = np.unique(st, axis=1, return_counts=True)
+        hist = np.bincount(st.ravel(), minlength=16).astype(np.float64)
+        pi = np.array([sum(hist[m] / bin(m).count("1") for m in range(1, 16) if (m >> k) & 1) for k in range(4)])
+        pi /= pi.sum()
+        parent, leaf = np.asarray(pin["parent"]), np.asarray(pin["leaf"])
+        fit = stage1_oracle.model_averaged(st, parent, np.asarray(pin["blen"]) / pin["correction"], leaf, pi)
+        _CLASS.update(pat=np.ascontiguousarray(pat), cnt=cnt.astype(np.float64), parent=parent, leaf=leaf, pi=pi, fit=fit)
+    return _CLASS
+
+
+def test_partitions_and_akaike_weights_against_the_restatement():
+    """hp.rate_partitions (a filter over all digit strings) against the restatement's recursion and the engine's documented
+    order; hp.akaike_weights (mpmath, no shift by the maximum) against the restatement's weights at 1e-12."""
+    from oracle import stage1_oracle
+    ms = hp.rate_partitions()
+    assert len(ms) == 203 and len(set(ms)) == 203 and ms[:4] == ["012345", "000000", "000001", "000010"]
+    assert ms[1:] == sorted(ms[1:]) and set(ms) == set(stage1_oracle.partitions6())
+    assert hp.partition_classes("012345") == ([0, -1, 1, 2, 3, 4], 5) and hp.partition_classes("000000") == ([-1] * 6, 0)
+    assert hp.partition_classes("010010") == ([0, -1, 0, 0, -1, 0], 1) and hp.partition_classes("011201") == ([0, -1, -1, 1, 0, -1], 2)
+    assert sorted(k for _, k in map(hp.partition_classes, ms[1:])) == [0] + [1] * 31 + [2] * 90 + [3] * 65 + [4] * 15   # Stirling
+    pi = [0.1, 0.2, 0.3, 0.4]
+    assert abs(float(hp.total_factor(pi, np.ones(6))) - (1 - sum(x * x for x in pi))) < 1e-15
+    fit = _class_case()["fit"]
+    nfree = [5] + [hp.partition_classes(s)[1] for s in ms[1:]]
+    w = hp.akaike_weights([fit["lnl"][s] for s in ms], nfree)
+    assert max(abs(float(w[i]) - fit["weights"][s]) for i, s in enumerate(ms)) <= 1e-12
+    with mpmath.workdps(hp.DPS):      # hundreds of nats behind: tiny, positive, and the sum is still 1
+        far = hp.akaike_weights([-300.0, -1500.0, -301.0], [5, 0, 2])
+        assert 0 < far[1] < mpmath.mpf(10) ** -500 and abs(mpmath.fsum(far) - 1) < mpmath.mpf(10) ** -35
+
+
+def test_class_model_gradient_is_the_chain_rule():
+    """d phi / d theta_j = sum_{q in class j} r_q (d lnL / d r_q - (sum_b d lnL / d log t_b) 2 pi_i pi_j / totalFactor), the two
+    pieces from locus_dexch_reference and locus_reference at t = b / totalFactor: to 1e-25 for one to four free classes."""
+    c = _class_case()
+    rng = np.random.default_rng(6)
+    b = np.where(c["parent"] >= 0, np.exp(rng.uniform(np.log(0.02), np.log(0.5), len(c["parent"]))), 0.0)
+    pif = hp.floored_pi(c["pi"])
+    for part in ("010010", "011021", "010213", "012340"):
+        cls, k = hp.partition_classes(part)
+        exch = np.array([1.0 if x < 0 else math.exp(rng.normal(0, 0.7)) for x in range(k)])[cls]
+        exch[np.array(cls) < 0] = 1.0
+        with mpmath.workdps(60):
+            theta = [mpmath.log(mpmath.mpf(float(exch[cls.index(a)]))) for a in range(k)]
+            tf = hp.total_factor(pif, exch, 60)
+            t = [mpmath.mpf(float(x)) / tf for x in b]
+            phi, g, _ = hp.class_model_reference(c["pat"], c["cnt"], c["parent"], b, c["leaf"], c["pi"], part, theta, order=1)
+            lnl, d1, _ = hp.locus_reference(c["pat"], c["cnt"], c["parent"], t, c["leaf"], c["pi"], exch, dps=60, as_float=False)
+            dex = hp.locus_dexch_reference(c["pat"], c["cnt"], c["parent"], t, c["leaf"], c["pi"], exch, as_float=False)
+            slope = mpmath.fsum(d1.values())
+            tiny = mpmath.mpf(10) ** -25
+            assert abs(phi - lnl) <= tiny
+            for a in range(k):
+                want = mpmath.fsum(mpmath.mpf(float(exch[q])) * (dex[q] - slope * 2 * mpmath.mpf(float(pif[i])) * mpmath.mpf(float(pif[j])) / tf)
+                                   for q, (i, j) in enumerate(hp.PAIRS) if cls[q] == a)
+                assert abs(g[a] - want) <= tiny * max(1, abs(want)), (part, a, g[a], want)
+
+
+def test_class_model_reference_does_not_depend_on_its_precision():
+    """60 digits with h = 1e-15 against 120 digits with h = 1e-17 (truncation 10^4 times smaller, rounding 10^56 times): the
+    value, the gradient and the Hessian of a three-class model move by less than 1e-25."""
+    c = _class_case()
+    b = np.where(c["parent"] >= 0, 0.07, 0.0)
+    a = hp.class_model_reference(c["pat"], c["cnt"], c["parent"], b, c["leaf"], c["pi"], "010213", [0.2, -0.4, 0.1])
+    z = hp.class_model_reference(c["pat"], c["cnt"], c["parent"], b, c["leaf"], c["pi"], "010213", [0.2, -0.4, 0.1], dps=120, step=1e-17)
+    with mpmath.workdps(120):
+        tiny = mpmath.mpf(10) ** -25
+        assert abs(a[0] - z[0]) <= tiny and max(abs(a[1][i] - z[1][i]) for i in range(3)) <= tiny
+        assert max(abs(a[2][i][j] - z[2][i][j]) for i in range(3) for j in range(3)) <= tiny
+        assert all(a[2][i][j] == a[2][j][i] for i in range(3) for j in range(3)) and max(abs(x) for x in z[1]) > 0.1
+    assert hp.class_model_reference(c["pat"], c["cnt"], c["parent"], b, c["leaf"], c["pi"], "000000", [])[1:] == (None, None)
+
+
+def test_restatement_optima_against_the_class_model_reference():
+    """At the optima oracle.stage1_oracle.model_averaged finds on the same locus, for every class model whose rates are all
+    interior (all 202 here): the reference's phi is the restatement's lnL within 1e-10 (1 + |lnL|), -H is positive definite,
+    and the Newton gain 1/2 g'(-H)^-1 g still to be had is below what the restatement's stopping rule implies:
+    scipy's L-BFGS-B stops on max_i |g_i| <= gtol for ITS gradient, forward differences of step eps of an objective with
+    absolute noise d, so the true slope is within gtol + eps |H_ii| / 2 + 2 d / eps =: s, and the gain is at most
+    k s^2 / (2 lambda_min(-H)).  Of the restatement's two runs (gtol 1e-7 with eps 1e-6, then 1e-8 with 1e-7) either may be
+    the one returned, so each term takes its larger value: s = 1e-7 + 5e-7 max|H_ii| + 2 d / 1e-7, with d = 1e-13 |lnL| (what the
+    oracle's likelihood keeps on ordinary inputs: test_locus_reference_agrees_with_the_oracle).  The largest gain must also be
+    below 1e-4, a tenth of the 1e-3 in lnL at which the GPU tests use the restatement as a cross-check."""
+    c = _class_case()
+    fit = c["fit"]
+    with mpmath.workdps(60):
+        tf0 = hp.total_factor(hp.floored_pi(c["pi"]), fit["grm_exch"], 60)
+        b = [mpmath.mpf(float(x)) * tf0 for x in fit["grm_blen"]]
+    rows = []
+    for s in hp.rate_partitions()[1:]:
+        cls, k = hp.partition_classes(s)
+        theta = np.log([fit["rates"][s][cls.index(a)] for a in range(k)])
+        if k == 0 or np.any(theta < -7.0 + 1e-6) or np.any(theta > 9.2 - 1e-6):
+            continue
+        with mpmath.workdps(60):
+            th = [mpmath.log(mpmath.mpf(float(fit["rates"][s][cls.index(a)]))) for a in range(k)]
+        phi, g, H = hp.class_model_reference(c["pat"], c["cnt"], c["parent"], b, c["leaf"], c["pi"], s, th)
+        gain, lam = hp.newton_gain(g, H)
+        lnl = float(phi)
+        slope = 1e-7 + 5e-7 * max(abs(float(H[a][a])) for a in range(k)) + 2 * 1e-13 * abs(lnl) / 1e-7
+        rows.append((s, abs(lnl - fit["lnl"][s]) / (1e-10 * (1 + abs(lnl))), gain, k * slope ** 2 / (2 * lam) if lam > 0 else 0.0, lam))
+    worst = max(rows, key=lambda r: r[2] / r[3] if r[3] > 0 else math.inf)
+    print("restatement optima: %d models; largest |d lnL| / bound %.3g; largest Newton gain %.3g; largest gain / implied bound %.3g "
+          "(model %s: gain %.3g, bound %.3g, smallest eigenvalue of -H %.3g)"
+          % (len(rows), max(r[1] for r in rows), max(r[2] for r in rows), worst[2] / worst[3] if worst[3] > 0 else math.inf, worst[0],
+             worst[2], worst[3], worst[4]))
+    assert len(rows) == 201      # every class model but "000000", which has no free rate
+    assert max(r[1] for r in rows) <= 1.0
+    bad = [r for r in rows if not (r[4] > 0 and r[2] <= r[3])]
+    assert not bad, bad
+    assert max(r[2] for r in rows) <= 1e-4
