@@ -466,6 +466,147 @@ __global__ __launch_bounds__(kCompactBlock) void compact_classes_kernel(const ui
     }
 }
 
+// ---- The same lists for long loci, chunk-parallel.  One workgroup per locus is a chain of barriers as long as the locus
+// (C3: 100 workgroups on 256 CUs, 49 rounds of three barriers each, then the append pass).  Three steps instead, ordered
+// by the stream alone (no workgroup waits for another):
+//   compact_count_kernel    per 1024-column chunk: its wanted columns and its easy ones            -> chunk_cnt[chunk]
+//   compact_scan_kernel     per locus: exclusive scan of its chunks' counts (in place); work_count, work_class
+//   compact_scatter_kernel  per chunk: every entry of work_cols straight to its final place -- main part
+//                           lo + before - reserved_before(easy rank), reserved tail lo + n_main + reserved_before(easy rank),
+//                           n_main from the locus totals: no scratch list, no append pass.
+// kClasses = false is compact_kernel's plain list (no marks read, reserve 0).  The lists, counts and class counts are the
+// one-workgroup kernels' entry for entry.
+constexpr int kCompactChunkBlock = 256;
+
+// A chunk's columns in kPiColsPerThread rounds of 256: which of them are wanted / easy, as one ballot per round and wave.
+template <bool kClasses>
+__device__ __forceinline__ void compact_chunk_ballots(const uint8_t* __restrict__ flag, const double* __restrict__ lnl,
+                                                      int64_t base, int64_t hi, unsigned long long* bal,
+                                                      unsigned long long* bal_easy) {
+#pragma unroll
+    for (int it = 0; it < kPiColsPerThread; ++it) {
+        const int64_t col = base + it * kCompactChunkBlock + threadIdx.x;
+        const bool want = (col < hi) && (flag[col] == TPHIP_FLAG_OK);
+        bool easy = false;
+        if (kClasses) easy = want && lnl[col] == 0.0;
+        bal[it] = __ballot(want);
+        bal_easy[it] = kClasses ? __ballot(easy) : 0ull;
+    }
+}
+
+template <bool kClasses>
+__global__ __launch_bounds__(kCompactChunkBlock) void compact_count_kernel(const uint8_t* __restrict__ flag, const double* __restrict__ lnl,
+                                                                          const int64_t* __restrict__ locus_offsets,
+                                                                          const int32_t* __restrict__ chunk_locus,
+                                                                          const int32_t* __restrict__ chunk_index,
+                                                                          int2* __restrict__ chunk_cnt) {
+    constexpr int kWaves = kCompactChunkBlock / 64;
+    __shared__ int wave_tot[kWaves], wave_easy[kWaves];
+    const int chunk = blockIdx.x, locus = chunk_locus[chunk];
+    const int64_t base = locus_offsets[locus] + (int64_t)chunk_index[chunk] * kPiChunk, hi = locus_offsets[locus + 1];
+    unsigned long long bal[kPiColsPerThread], bal_easy[kPiColsPerThread];
+    compact_chunk_ballots<kClasses>(flag, lnl, base, hi, bal, bal_easy);
+    int tot = 0, etot = 0;
+#pragma unroll
+    for (int it = 0; it < kPiColsPerThread; ++it) { tot += __popcll(bal[it]); etot += __popcll(bal_easy[it]); }
+    if ((threadIdx.x & 63) == 0) { wave_tot[threadIdx.x >> 6] = tot; wave_easy[threadIdx.x >> 6] = etot; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0, b = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) { a += wave_tot[w]; b += wave_easy[w]; }
+        chunk_cnt[chunk] = make_int2(a, b);
+    }
+}
+
+template <bool kClasses>
+__global__ __launch_bounds__(kCompactChunkBlock) void compact_scan_kernel(const int64_t* __restrict__ locus_chunk_offsets, int2* __restrict__ chunk_cnt,
+                                                                         int32_t* __restrict__ work_count, int32_t* __restrict__ work_class) {
+    constexpr int kWaves = kCompactChunkBlock / 64;
+    __shared__ int wave_tot[kWaves], wave_easy[kWaves];
+    const int locus = blockIdx.x;
+    const int64_t c0 = locus_chunk_offsets[locus], c1 = locus_chunk_offsets[locus + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int running = 0, running_easy = 0;   // the same in every thread
+    for (int64_t cb = c0; cb < c1; cb += kCompactChunkBlock) {
+        const int64_t c = cb + threadIdx.x;
+        const int2 mine = (c < c1) ? chunk_cnt[c] : make_int2(0, 0);
+        int inc = mine.x, einc = mine.y;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(inc, o), eup = __shfl_up(einc, o);
+            if (lane >= o) { inc += up; einc += eup; }
+        }
+        if (lane == 63) { wave_tot[wave] = inc; wave_easy[wave] = einc; }
+        __syncthreads();
+        int off = running, eoff = running_easy;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            off += (w < wave) ? wave_tot[w] : 0; running += wave_tot[w];
+            eoff += (w < wave) ? wave_easy[w] : 0; running_easy += wave_easy[w];
+        }
+        if (c < c1) chunk_cnt[c] = make_int2(off + inc - mine.x, eoff + einc - mine.y);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        work_count[locus] = running;
+        if (kClasses) { work_class[2 * locus] = running - running_easy; work_class[2 * locus + 1] = running_easy; }
+    }
+}
+
+template <bool kClasses>
+__global__ __launch_bounds__(kCompactChunkBlock) void compact_scatter_kernel(const uint8_t* __restrict__ flag, const double* __restrict__ lnl,
+                                                                            const int64_t* __restrict__ locus_offsets,
+                                                                            const int32_t* __restrict__ chunk_locus,
+                                                                            const int32_t* __restrict__ chunk_index,
+                                                                            const int2* __restrict__ chunk_off,
+                                                                            const int32_t* __restrict__ work_count,
+                                                                            const int32_t* __restrict__ work_class, int32_t reserve_q,
+                                                                            int32_t* __restrict__ work_cols) {
+    constexpr int kWaves = kCompactChunkBlock / 64;
+    __shared__ int wave_tot[kPiColsPerThread][kWaves], wave_easy[kPiColsPerThread][kWaves];
+    const int chunk = blockIdx.x, locus = chunk_locus[chunk];
+    const int64_t lo = locus_offsets[locus], hi = locus_offsets[locus + 1];
+    const int64_t base = lo + (int64_t)chunk_index[chunk] * kPiChunk;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long bal[kPiColsPerThread], bal_easy[kPiColsPerThread];
+    compact_chunk_ballots<kClasses>(flag, lnl, base, hi, bal, bal_easy);
+    if (lane == 0) {
+#pragma unroll
+        for (int it = 0; it < kPiColsPerThread; ++it) { wave_tot[it][wave] = __popcll(bal[it]); wave_easy[it][wave] = __popcll(bal_easy[it]); }
+    }
+    __syncthreads();
+    const int2 start = chunk_off[chunk];   // the locus' wanted / easy columns before this chunk
+    int n_main = 0;
+    if (kClasses) n_main = work_count[locus] - reserved_before(work_class[2 * locus + 1], reserve_q);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int off = start.x, eoff = start.y;     // ... before this round's first column
+#pragma unroll
+    for (int it = 0; it < kPiColsPerThread; ++it) {
+        int woff = off, weoff = eoff;      // ... before this wave's first column of the round
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            woff += (w < wave) ? wave_tot[it][w] : 0; off += wave_tot[it][w];
+            weoff += (w < wave) ? wave_easy[it][w] : 0; eoff += wave_easy[it][w];
+        }
+        if ((bal[it] >> lane) & 1ull) {
+            const int32_t col = (int32_t)(base + it * kCompactChunkBlock + threadIdx.x);
+            const int before = woff + __popcll(bal[it] & below);
+            if (kClasses) {
+                // erank: the easy columns of the locus before this one; that many of them were reserved, the others are
+                // ahead of this column in the main part
+                const int erank = weoff + __popcll(bal_easy[it] & below);
+                const int res = reserved_before(erank, reserve_q);
+                const bool easy = (bal_easy[it] >> lane) & 1ull;
+                if (easy && reserved_before((int64_t)erank + 1, reserve_q) != res) work_cols[lo + n_main + res] = col;
+                else work_cols[lo + before - res] = col;
+            } else {
+                work_cols[lo + before] = col;
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -574,6 +574,11 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     p->ws_work_wprefix = off; off = align_up(off + sizeof(int64_t) * ((size_t)d->nloci + 1), 256);
     p->ws_part_prefix = off; off = align_up(off + sizeof(int64_t) * 2 * ((size_t)d->nloci + 1), 256);
     p->ws_part_start = off; off = align_up(off + sizeof(int64_t) * 2 * ((size_t)d->nloci + 1), 256);
+    // Long loci build the work list chunk-parallel (compact_count / scan / scatter kernels); TPHIP_COMPACT_CHUNKED=0/1 is the
+    // A/B and test switch that forces either path on any shape.
+    p->compact_chunked = p->max_locus_cols > 2048 ? 1 : 0;
+    if (const char* ec = getenv("TPHIP_COMPACT_CHUNKED")) p->compact_chunked = (ec[0] != '0');
+    p->ws_chunk_cnt = off; off = align_up(off + sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(1, p->n_pi_chunks), 256);
     p->ws_partial = off; off = align_up(off + sizeof(double) * (size_t)p->n_pi_chunks * (size_t)(d->T + 2 * d->n_i), 256);
     p->ws_packed = off; off = align_up(off + sizeof(uint32_t) * (size_t)p->nwords * (size_t)ncols, 256);
     if (const char* e9 = getenv("TPHIP_DEDUP")) {   // test/tuning knob: 0 = never, 1 = always, anything else = automatic
@@ -716,6 +721,25 @@ int tphip_last_round_count(tphip_plan* p, int64_t* rounds) {
 
 static PiParams pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres, void* ws);
 
+// The work list of long loci by the chunk-parallel kernels (pi_kernels.hpp).  work_class != null: with the class counts and
+// the reserved tails of the hand-out by predicted work (compact_classes_kernel's list), else compact_kernel's plain list.
+static void launch_compact_chunked(tphip_plan* p, const uint8_t* d_flag, const double* d_lnl, int32_t* work_cols, int32_t* work_count,
+                                  int32_t* work_class, void* ws, hipStream_t st) {
+    int2* cnt = (int2*)((char*)ws + p->ws_chunk_cnt);
+    const dim3 chunks((unsigned)p->n_pi_chunks), loci((unsigned)p->nloci), block(kCompactChunkBlock);
+    if (work_class) {
+        compact_count_kernel<true><<<chunks, block, 0, st>>>(d_flag, d_lnl, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt);
+        compact_scan_kernel<true><<<loci, block, 0, st>>>(p->d_locus_pichunk_offsets.p, cnt, work_count, work_class);
+        compact_scatter_kernel<true><<<chunks, block, 0, st>>>(d_flag, d_lnl, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt,
+                                                               work_count, work_class, p->site_reserve_q, work_cols);
+    } else {
+        compact_count_kernel<false><<<chunks, block, 0, st>>>(d_flag, nullptr, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt);
+        compact_scan_kernel<false><<<loci, block, 0, st>>>(p->d_locus_pichunk_offsets.p, cnt, work_count, nullptr);
+        compact_scatter_kernel<false><<<chunks, block, 0, st>>>(d_flag, nullptr, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt,
+                                                                work_count, nullptr, 0, work_cols);
+    }
+}
+
 static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_rate, double* d_subst, double* d_lnl,
                              uint8_t* d_flag, int32_t* d_nres, void* ws, hipStream_t st, int slot) {
     p->last_run_in_parts = false;
@@ -750,11 +774,16 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
         }
         if (p->site_share_work) {
             // shares by predicted work: the list with class counts and reserved tails, and their scans (compact_classes_kernel
-            // reads the marks, 8 more bytes per work column in its chain of barriers, and appends the tails: C3 47 -> 100 us)
+            // reads the marks, 8 more bytes per work column in its chain of barriers, and appends the tails: C3 47 -> 100 us;
+            // long loci take the chunk-parallel kernels instead: 40 us)
             int32_t* work_class = (int32_t*)((char*)ws + p->ws_work_class);
-            int32_t* scratch = p->site_reserve_q > 0 ? (int32_t*)((char*)ws + p->ws_work_cols2) : nullptr;
-            if (p->max_locus_cols > 2048) compact_classes_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
-            else compact_classes_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
+            if (p->compact_chunked) {
+                launch_compact_chunked(p, d_flag, d_lnl, work_cols, work_count, work_class, ws, st);
+            } else {
+                int32_t* scratch = p->site_reserve_q > 0 ? (int32_t*)((char*)ws + p->ws_work_cols2) : nullptr;
+                if (p->max_locus_cols > 2048) compact_classes_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
+                else compact_classes_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
+            }
             ScanClasses SC;
             SC.cls = work_class; SC.reserve_q = p->site_reserve_q; SC.w_slow = p->site_w_slow; SC.w_easy = p->site_w_easy;
             SC.locus_offsets = p->d_offsets.p;
@@ -763,7 +792,8 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
             HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site_chunk_cols, (int64_t*)((char*)ws + p->ws_work_prefix),
                                               (int64_t*)((char*)ws + p->ws_slice_prefix), &SC));
         } else {
-            if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
+            if (p->compact_chunked) launch_compact_chunked(p, d_flag, nullptr, work_cols, work_count, nullptr, ws, st);
+            else if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
             else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
             HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site_chunk_cols, (int64_t*)((char*)ws + p->ws_work_prefix),
                                               (int64_t*)((char*)ws + p->ws_slice_prefix), nullptr));
@@ -872,6 +902,8 @@ int tphip_internal_eb_prepare(tphip_plan* p, const uint8_t* d_states, const EbPr
         else dedup_estimate_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(D);
         dedup_insert_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
         dedup_resolve_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
+        // (this front end keeps the one-workgroup-per-locus list for long loci too: it runs once per empirical-Bayes call,
+        //  not per step, and EbPrep carries no buffer for the chunk counts of launch_compact_chunked)
         if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(B->flag, p->d_offsets.p, B->work_cols, B->work_count);
         else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(B->flag, p->d_offsets.p, B->work_cols, B->work_count);
     }

@@ -168,6 +168,8 @@ struct tphip_plan {
     // cut the rest into equal predicted work, a slow column weighing w_slow / 2^10 evaluations and an easy one w_easy / 2^10
     int32_t site_share_work = 0, site_reserve_q = 0, site_w_slow = 0, site_w_easy = 0;
     size_t ws_work_class = 0, ws_work_wprefix = 0, ws_part_prefix = 0, ws_part_start = 0;
+    int32_t compact_chunked = 0;   // long loci: the work list by the chunk-parallel count / scan / scatter kernels (pi_kernels.hpp)
+    size_t ws_chunk_cnt = 0;
     // profiling
     bool profile = false;
     std::vector<hipEvent_t> ev;  // 4 events per slot: site start/stop, pi start/stop
