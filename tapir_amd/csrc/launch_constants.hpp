@@ -1,0 +1,35 @@
+// launch_constants.hpp -- the constants that the kernels and the host's launch decisions (site_launch_plan.hpp) share.
+// No HIP header: site_launch_plan.hpp and its test program compile with a plain C++ compiler.
+#pragma once
+#include <cstdint>
+
+namespace tphip {
+
+// ---- site-rate kernels (site_rate_params.hpp, site_rate_kernel.hpp) ----
+constexpr int kFirstStepMinTaxa = 32;   // trees from this size on use the parsimony length in the optimiser's first step (pi_kernels.hpp)
+constexpr int kSiteBlock = 64;      // one wavefront per workgroup
+constexpr int kReserveShift = 16;     // the reserved fraction of a locus' easy columns is reserve_q / 2^16 (reserved_before)
+constexpr int kShareWeightShift = 10; // predicted evaluations per column of a class, in units of 2^-10 (the weighted scan stays exact)
+constexpr double kDefaultReserve = 0.15;  // shares by predicted work (SiteParams::share_work): this fraction of every locus' easy columns
+                                          //   forms its reserved tail; TPHIP_SITE_RESERVE
+constexpr int kMixedLoci = 8;        // loci whose columns a wave of the mixed-loci mode carries at a time (site_rate_kernel.hpp)
+constexpr int kMixedLdsHeader = kMixedLoci * 64 + 64 + 32;   // doubles: tip tables, 2^(j/64), segment table
+constexpr int kMixedColBits = 28;    // a work entry of that mode = column | locus-in-group << 28: batches below 2^28 columns
+constexpr int kSiteLdsHeader = 160;  // doubles of LDS before the stack: tip table [16][4] + model [32] + 2^(j/64) [64]
+constexpr int kStreamWords = -1;   // NW value of the streamed-words path
+constexpr int kStreamWordsSpill = -2;   // launcher variant: streamed words + SPILL
+constexpr int kMixedVariant = 100;   // launcher variants 102 / 108: packed words in registers, mixed-loci mode
+
+// ---- classification and PI kernels (pi_kernels.hpp) ----
+constexpr int kPiBlock = 256;
+constexpr int kPiColsPerThread = 4;
+constexpr int kPiChunk = kPiBlock * kPiColsPerThread;  // 1024 columns per workgroup
+
+// ---- site-pattern de-duplication (pattern_kernels.hpp) ----
+enum : int32_t { DEDUP_AUTO = 0, DEDUP_OFF = 1, DEDUP_ON = 2 };
+// Batches below this many columns are not de-duplicated in automatic mode: they run in the latency-bound small-batch
+// modes of site_rate_kernel (a launch lasts as long as its slowest wave), where fewer columns hardly shorten the kernel and the four extra
+// launches cost more than they save (C2, 5e5 columns: 0.50 -> 0.53 ms per step with the machinery idling).
+constexpr int64_t kDedupAutoMinColumns = 1 << 20;
+
+}  // namespace tphip

@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "launch_constants.hpp"
 #include "tphip.h"
 
 namespace tphip {
@@ -154,7 +155,7 @@ constexpr unsigned long long kDedupEmpty = ~0ull;
 constexpr int kDedupBitmapBits = 1 << 16;
 constexpr double kDedupWorthIt = 0.85;
 constexpr int kDedupMinColumns = 32;
-enum : int32_t { DEDUP_AUTO = 0, DEDUP_OFF = 1, DEDUP_ON = 2 };
+// (DEDUP_AUTO / DEDUP_OFF / DEDUP_ON and kDedupAutoMinColumns: launch_constants.hpp)
 
 struct DedupParams {
     const int64_t* locus_offsets;   // [nloci+1]
@@ -176,10 +177,6 @@ struct DedupParams {
 __device__ __forceinline__ unsigned long long dedup_key(uint64_t h) { return h == kDedupEmpty ? 0ull : h; }
 
 constexpr int64_t kDedupEstimatePrefix = 16384;   // columns of a locus the estimate looks at (0.17 -> 0.02 ms on C3)
-// Batches below this many columns are not de-duplicated in automatic mode: they run in the latency-bound small-batch
-// modes of site_rate_kernel (a launch lasts as long as its slowest wave), where fewer columns hardly shorten the kernel and the four extra
-// launches cost more than they save (C2, 5e5 columns: 0.50 -> 0.53 ms per step with the machinery idling).
-constexpr int64_t kDedupAutoMinColumns = 1 << 20;
 
 // kBlock: 1024 threads for long loci, 256 for short ones (1000 workgroups of 1024 threads in front of the one-wave
 // workgroups of site_rate_kernel made THAT kernel 24 % slower on C2 -- the effect round 1 saw with compact_kernel)

@@ -22,9 +22,7 @@
 
 namespace tphip {
 
-constexpr int kPiBlock = 256;
-constexpr int kPiColsPerThread = 4;
-constexpr int kPiChunk = kPiBlock * kPiColsPerThread;  // 1024 columns per workgroup
+// (kPiBlock, kPiColsPerThread, kPiChunk: launch_constants.hpp)
 constexpr int kTimeTile = 16;
 constexpr int kIvTile = 8;      // intervals per register tile of pi_partial_kernel (2 * kIvTile <= kTimeTile rows of `red`)
 

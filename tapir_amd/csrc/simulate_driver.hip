@@ -154,7 +154,7 @@ ParbootLayout parboot_layout(const tphip_plan* p, int32_t B) {
     L.rows = take(sizeof(double) * (size_t)p->nloci * (size_t)B * Wb);
     L.mean = take(sizeof(double) * n);
     L.m2 = take(sizeof(double) * n);
-    L.plan_ws = take(p->ws_total);
+    L.plan_ws = take(p->ws.total);
     L.total = off + kSimAlign;   // the caller's pointer is aligned up
     return L;
 }
@@ -256,7 +256,7 @@ int tphip_pi_parametric_bootstrap_dev(tphip_plan* p, const double* d_rates, cons
     for (int32_t b = 0; b < B; ++b) {
         rc = sim_launch(p, d_rates, d_states_observed, d_ids, (uint32_t)b, o.seed, states, st);
         if (rc) return rc;
-        rc = tphip_run_dev(p, states, rate, subst, lnl, flag, nres, tables, base + L.plan_ws, p->ws_total, stream);
+        rc = tphip_run_dev(p, states, rate, subst, lnl, flag, nres, tables, base + L.plan_ws, p->ws.total, stream);
         if (rc) return rc;
         if (Wb > 0) parboot_rows_kernel<<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(tables, W, p->T, p->n_t, p->n_i, b, B, rows);
         if (p->ncols > 0) {

@@ -5,11 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gtr_model.hpp"
+#include "launch_constants.hpp"   // kSiteBlock, the LDS headers, the launcher variants, ...
 #include "tree_program.hpp"
 
 namespace tphip {
 
-constexpr int kFirstStepMinTaxa = 32;   // trees from this size on use the parsimony length in the optimiser's first step (pi_kernels.hpp)
 constexpr double kUMin = -23.025850929940457;  // log(1e-10)
 constexpr double kUMax = 9.210340371976184;    // log(1e4)
 constexpr double kStepMax = 2.0;
@@ -31,16 +31,7 @@ constexpr double kFlatEps = 1e-10;  // |g| and |h| below this: log L flat to fp6
 constexpr double kUCheck = 2.995732273553991;   // log(20)
 constexpr double kSatTol = 1e-10;
 constexpr double kPlateauStride = 0.5;
-constexpr int kSiteBlock = 64;      // one wavefront per workgroup
 constexpr int kTailWindow = 2 * kSiteBlock;   // persistent mode: entries at the end of a segment that are put in slow-first order (SiteParams::tail_order)
-constexpr int kReserveShift = 16;     // the reserved fraction of a locus' easy columns is reserve_q / 2^16 (reserved_before)
-constexpr int kShareWeightShift = 10; // predicted evaluations per column of a class, in units of 2^-10 (the weighted scan stays exact)
-constexpr double kDefaultReserve = 0.15;  // shares by predicted work (SiteParams::share_work): this fraction of every locus' easy columns
-                                          //   forms its reserved tail; TPHIP_SITE_RESERVE
-constexpr int kMixedLoci = 8;        // loci whose columns a wave of the mixed-loci mode carries at a time (site_rate_kernel.hpp)
-constexpr int kMixedLdsHeader = kMixedLoci * 64 + 64 + 32;   // doubles: tip tables, 2^(j/64), segment table
-constexpr int kMixedColBits = 28;    // a work entry of that mode = column | locus-in-group << 28: batches below 2^28 columns
-constexpr int kSiteLdsHeader = 160;  // doubles of LDS before the stack: tip table [16][4] + model [32] + 2^(j/64) [64]
 #ifndef TPHIP_EXP_TABLE
 #define TPHIP_EXP_TABLE 1
 #endif
@@ -109,9 +100,6 @@ __host__ __device__ __forceinline__ int32_t reserved_before(int64_t r, int32_t r
     return (int32_t)((r * (int64_t)reserve_q) >> kReserveShift);
 }
 
-constexpr int kStreamWords = -1;   // NW value of the streamed-words path
-constexpr int kStreamWordsSpill = -2;   // launcher variant: streamed words + SPILL
-constexpr int kMixedVariant = 100;   // launcher variants 102 / 108: packed words in registers, mixed-loci mode
 
 // Diagnostic launch: evaluate f = log L, g = df/du, h = d2f/du2 at a caller-chosen u for EVERY column.
 struct EvalParams {

@@ -185,139 +185,55 @@ static int make_parts(tphip_plan* p) {
     return TPHIP_OK;
 }
 
-int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
-    if (!d_in || !out) return fail(TPHIP_ERR_INVALID, "null plan descriptor");
-    *out = nullptr;
-    // the caller's struct may be shorter (built against an older header): its missing trailing fields are zero
-    if (d_in->struct_size < offsetof(tphip_plan_desc, round_decimals) + sizeof(int32_t) || d_in->struct_size > 4096)
-        return fail(TPHIP_ERR_INVALID, "tphip_plan_desc.struct_size not set (zero-initialise the struct, then set it to sizeof)");
-    tphip_plan_desc d_copy;
-    memset(&d_copy, 0, sizeof(d_copy));
-    memcpy(&d_copy, d_in, std::min<size_t>(d_in->struct_size, sizeof(d_copy)));
-    d_copy.struct_size = (uint32_t)sizeof(d_copy);
-    const tphip_plan_desc* d = &d_copy;
-    int ndev = tphip_device_count();
-    if (ndev <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (d->device < 0 || d->device >= ndev) return fail(TPHIP_ERR_INVALID, "device ordinal out of range");
-    if (d->ntaxa < 2) return fail(TPHIP_ERR_INVALID, "ntaxa must be >= 2");
-    if (!d->parent || !d->branch_len || !d->leaf_taxon) return fail(TPHIP_ERR_INVALID, "null tree arrays");
-    if (d->model != TPHIP_MODEL_GTR && d->model != TPHIP_MODEL_F81) return fail(TPHIP_ERR_INVALID, "unknown model");
-    if (d->model == TPHIP_MODEL_F81 && d->exch)
-        return fail(TPHIP_ERR_INVALID, "exch must be NULL with TPHIP_MODEL_F81 (its exchangeabilities are all 1)");
-    if (d->nloci < 1 || !d->locus_offsets || !d->pi || (d->model == TPHIP_MODEL_GTR && !d->exch))
-        return fail(TPHIP_ERR_INVALID, "null or empty locus arrays");
-    if (d->T < 0 || d->n_t < 0 || d->n_i < 0) return fail(TPHIP_ERR_INVALID, "negative schedule size");
-    if ((d->n_t && !d->times) || (d->n_i && !d->intervals)) return fail(TPHIP_ERR_INVALID, "null times/intervals");
-    if (!(d->correction > 0.0)) return fail(TPHIP_ERR_INVALID, "correction must be > 0");
-    if (d->integ_mode != TPHIP_INTEG_QUADPACK && d->integ_mode != TPHIP_INTEG_CLOSED)
-        return fail(TPHIP_ERR_INVALID, "unknown integ_mode");
-    if (d->start_rule != TPHIP_START_AUTO && d->start_rule != TPHIP_START_PARSIMONY && d->start_rule != TPHIP_START_REFERENCE)
-        return fail(TPHIP_ERR_INVALID, "unknown start_rule");
-    if (d->pattern_dedup != TPHIP_DEDUP_AUTO && d->pattern_dedup != TPHIP_DEDUP_OFF && d->pattern_dedup != TPHIP_DEDUP_ON)
-        return fail(TPHIP_ERR_INVALID, "unknown pattern_dedup");
-    for (int i = 0; i < d->n_t; ++i)
-        if (d->times[i] < 0 || d->times[i] >= d->T)  // numpy would raise IndexError (tapir/compute.py:78)
-            return fail(TPHIP_ERR_INVALID, "a --times value is outside 0..T-1 (index out of bounds for the net PI vector)");
-    for (int i = 0; i < d->n_i; ++i)
-        if (!(d->intervals[2 * i] < d->intervals[2 * i + 1]))  // assert at tapir/compute.py:90-91
-            return fail(TPHIP_ERR_INVALID, "Start time is sooner than end time in an interval");
-    if (d->locus_offsets[0] != 0) return fail(TPHIP_ERR_INVALID, "locus_offsets[0] must be 0");
-    for (int64_t l = 0; l < d->nloci; ++l) {
-        if (d->locus_offsets[l + 1] < d->locus_offsets[l]) return fail(TPHIP_ERR_INVALID, "locus_offsets not monotone");
+// Base frequencies and exchangeabilities of locus l as a caller gave them (either array may be null: not checked).
+static int check_locus_model(const double* pi, const double* exch, int64_t l) {
+    if (pi) {
         int npos = 0;
         for (int k = 0; k < 4; ++k) {
-            if (!(d->pi[l * 4 + k] >= 0.0) || !std::isfinite(d->pi[l * 4 + k]))
+            if (!(pi[l * 4 + k] >= 0.0) || !std::isfinite(pi[l * 4 + k]))
                 return fail(TPHIP_ERR_INVALID, "base frequencies of locus " + std::to_string(l) + " must be finite and >= 0");
-            npos += d->pi[l * 4 + k] > 0.0;
+            npos += pi[l * 4 + k] > 0.0;
         }
         if (npos < 2) return fail(TPHIP_ERR_INVALID, "locus " + std::to_string(l) + " has fewer than two bases with a positive frequency");
-        for (int k = 0; k < 6 && d->exch; ++k)
-            if (!(d->exch[l * 6 + k] >= 0.0)) return fail(TPHIP_ERR_INVALID, "exchangeabilities must be >= 0");
     }
-    const int64_t ncols = d->locus_offsets[d->nloci];
-    if (ncols >= (int64_t)1 << 31) return fail(TPHIP_ERR_INVALID, "more than 2^31-1 columns in one batch");
-    std::vector<double> cat;
-    if (d->ncat > 1) {
-        if (d->ncat > 16) return fail(TPHIP_ERR_INVALID, "at most 16 rate categories");
-        if (!d->cat_rate || !d->cat_weight) return fail(TPHIP_ERR_INVALID, "rate categories need cat_rate and cat_weight");
-        double wsum = 0;
-        for (int k = 0; k < d->ncat; ++k) {
-            if (!(d->cat_rate[k] > 0.0) || !(d->cat_weight[k] > 0.0) || !std::isfinite(d->cat_rate[k]) || !std::isfinite(d->cat_weight[k]))
-                return fail(TPHIP_ERR_INVALID, "category rates and weights must be positive and finite");
-            wsum += d->cat_weight[k];
-        }
-        cat.resize(2 * (size_t)d->ncat);
-        for (int k = 0; k < d->ncat; ++k) { cat[k] = d->cat_rate[k]; cat[d->ncat + k] = std::log(d->cat_weight[k] / wsum); }
-    }
+    for (int k = 0; k < 6 && exch; ++k)
+        if (!(exch[l * 6 + k] >= 0.0)) return fail(TPHIP_ERR_INVALID, "exchangeabilities must be >= 0");
+    return TPHIP_OK;
+}
 
-    tphip_plan* p = new tphip_plan();
-    p->device = d->device; p->ntaxa = d->ntaxa; p->nloci = d->nloci; p->ncols = ncols;
-    p->T = d->T; p->n_t = d->n_t; p->n_i = d->n_i; p->integ_mode = d->integ_mode;
-    p->threshold = d->threshold; p->round_decimals = d->round_decimals; p->correction = d->correction;
-    // TPHIP_START_AUTO: HyPhy's own start where the parsimony start was ever seen to end on another local optimum (small trees)
-    // (the rate mixture is an extension without a HyPhy counterpart to start like: it keeps the parsimony start)
-    p->start_rule = d->start_rule == TPHIP_START_AUTO
-                        ? ((d->ntaxa >= kFirstStepMinTaxa || d->ncat > 1) ? TPHIP_START_PARSIMONY : TPHIP_START_REFERENCE)
-                        : d->start_rule;
-    p->dedup_mode = d->pattern_dedup;
-    p->model = d->model;
-    p->ncat = cat.empty() ? 0 : d->ncat;
-    std::string terr = build_tree_program(d->ntaxa, d->nnodes, d->parent, d->branch_len, d->leaf_taxon, &p->prog);
-    if (!terr.empty()) { delete p; return fail(TPHIP_ERR_INVALID, "tree: " + terr); }
-    if (p->prog.nleaves != d->ntaxa) {  // HyPhy refuses a tree / alignment mismatch as well
-        delete p;
-        return fail(TPHIP_ERR_INVALID, "tree: the number of leaves differs from the number of alignment rows");
+// A base that never occurs in a (short) locus has empirical frequency 0 (HarvestFrequencies, bf:968); HyPhy takes
+// that as it is: the state is unreachable and no tip carries it, so the likelihood is that of the three-state
+// model.  The eigen-form used here needs D^-1/2, so the zero is floored at kPiFloor before the renormalisation in
+// gtr_setup_kernel: the dead state then enters every likelihood with weight O(1e-12), below the 1e-9 the parity
+// tests resolve.
+static void floor_pi(std::vector<double>* hpi) {
+    for (size_t l = 0; 4 * l < hpi->size(); ++l) {
+        double sum = 0;
+        for (int k = 0; k < 4; ++k) sum += (*hpi)[4 * l + k];
+        for (int k = 0; k < 4; ++k) (*hpi)[4 * l + k] = std::max((*hpi)[4 * l + k], kPiFloor * sum);
     }
-    const size_t lds_bytes = (kSiteLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
-    if (lds_bytes > 160 * 1024) { delete p; return fail(TPHIP_ERR_INVALID, "tree needs a deeper LDS stack than 160 KiB allows"); }
-    p->h_offsets.assign(d->locus_offsets, d->locus_offsets + d->nloci + 1);
-    for (int64_t l = 0; l < d->nloci; ++l)
-        p->max_locus_cols = std::max<int64_t>(p->max_locus_cols, d->locus_offsets[l + 1] - d->locus_offsets[l]);
+}
 
-    // chunk tables: work slices for the optimiser, 1024-column chunks for classification and PI.
-    // A slice is what one wave works through with lane refill: long enough to amortise the drain at its end,
-    // short enough that the batch still makes >= ~8192 waves (32 per CU).
-    {
-        // Target slice length of the non-persistent mode (small batches) and of the eval diagnostic.
-        int64_t cc = 512;
-        if (const char* e = getenv("TPHIP_SITE_CHUNK")) {  // tuning knob for experiments
-            long v = atol(e);
-            if (v >= kSiteBlock) cc = v;
-        }
-        p->site_chunk_cols = (int32_t)cc;
-    }
-    std::vector<int32_t> scl, sci, pcl, pci;
-    std::vector<int64_t> lpo(d->nloci + 1, 0);
-    for (int64_t l = 0; l < d->nloci; ++l) {
-        const int64_t S = p->h_offsets[l + 1] - p->h_offsets[l];
-        const int64_t ns_max = std::max<int64_t>(1, (S + p->site_chunk_cols / 2) / p->site_chunk_cols);
-        for (int64_t c = 0; c < ns_max && S > 0; ++c) { scl.push_back((int32_t)l); sci.push_back((int32_t)c); }
-        for (int64_t c = 0; c * kPiChunk < S; ++c) { pcl.push_back((int32_t)l); pci.push_back((int32_t)c); }
-        lpo[l + 1] = (int64_t)pcl.size();
-    }
-    p->n_site_chunks = (int64_t)scl.size();
-    p->n_pi_chunks = (int64_t)pcl.size();
+// The tuning knobs of plan creation (site_launch_plan.hpp), read from the environment once per plan.
+static PlanKnobs knobs_from_env() {
+    PlanKnobs k;
+    for (const char* name : kPlanKnobNames)
+        if (const char* text = getenv(name)) set_plan_knob(&k, name, text);
+    return k;
+}
 
-    hipError_t e = hipSetDevice(d->device);
+// The tree programs, the locus and chunk tables, the schedule and the per-locus models, onto the plan's device.
+static hipError_t upload_plan(tphip_plan* p, const tphip_plan_desc* d, const std::vector<double>& cat, const ChunkTables& chunks) {
+    hipError_t e = hipSuccess;
     std::vector<int32_t> times(d->times, d->times + d->n_t), iv(d->intervals, d->intervals + 2 * (size_t)d->n_i);
     DevBuf<double> d_pi, d_exch;
     std::vector<double> hpi(d->pi, d->pi + 4 * (size_t)d->nloci), hex(6 * (size_t)d->nloci, 1.0);
     if (d->exch) hex.assign(d->exch, d->exch + 6 * (size_t)d->nloci);
     std::vector<LocusModel> f81;
     if (d->model == TPHIP_MODEL_F81) f81_models(d->pi, d->nloci, &f81);
-    // A base that never occurs in a (short) locus has empirical frequency 0 (HarvestFrequencies, bf:968); HyPhy takes
-    // that as it is: the state is unreachable and no tip carries it, so the likelihood is that of the three-state
-    // model.  The eigen-form used here needs D^-1/2, so the zero is floored at kPiFloor before the renormalisation in
-    // gtr_setup_kernel: the dead state then enters every likelihood with weight O(1e-12), below the 1e-9 the parity
-    // tests resolve.
-    for (int64_t l = 0; l < d->nloci; ++l) {
-        double sum = 0;
-        for (int k = 0; k < 4; ++k) sum += hpi[4 * l + k];
-        for (int k = 0; k < 4; ++k) hpi[4 * l + k] = std::max(hpi[4 * l + k], kPiFloor * sum);
-    }
+    floor_pi(&hpi);
     std::vector<int32_t> tip_taxon;
     for (const TreeOp& op : p->prog.ops) if (op.code <= OP_TIP_MUL) tip_taxon.push_back(op.taxon);
-    p->nwords = (int32_t)((tip_taxon.size() + 7) / 8);
     while (tip_taxon.size() % 8) tip_taxon.push_back(tip_taxon.back());   // read eight at a time
     if (e == hipSuccess) e = p->d_tip_taxon.upload(tip_taxon);
     if (e == hipSuccess) e = p->d_cls_steps.upload(p->prog.cls_steps);
@@ -364,15 +280,14 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
             }
         }
     }
-    p->nnodes = d->nnodes;
     if (e == hipSuccess) e = p->d_ops.upload(p->prog.ops);
     if (e == hipSuccess) e = p->d_fused_ops.upload(p->prog.fused_ops);
     if (e == hipSuccess) e = p->d_offsets.upload(p->h_offsets);
-    if (e == hipSuccess) e = p->d_locus_pichunk_offsets.upload(lpo);
-    if (e == hipSuccess) e = p->d_site_chunk_locus.upload(scl);
-    if (e == hipSuccess) e = p->d_site_chunk_index.upload(sci);
-    if (e == hipSuccess) e = p->d_pi_chunk_locus.upload(pcl);
-    if (e == hipSuccess) e = p->d_pi_chunk_index.upload(pci);
+    if (e == hipSuccess) e = p->d_locus_pichunk_offsets.upload(chunks.locus_pichunk_offsets);
+    if (e == hipSuccess) e = p->d_site_chunk_locus.upload(chunks.site_chunk_locus);
+    if (e == hipSuccess) e = p->d_site_chunk_index.upload(chunks.site_chunk_index);
+    if (e == hipSuccess) e = p->d_pi_chunk_locus.upload(chunks.pi_chunk_locus);
+    if (e == hipSuccess) e = p->d_pi_chunk_index.upload(chunks.pi_chunk_index);
     if (e == hipSuccess) e = p->d_times.upload(times);
     if (e == hipSuccess) e = p->d_intervals.upload(iv);
     if (e == hipSuccess) e = p->d_models.alloc((size_t)d->nloci);
@@ -390,223 +305,190 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     if (e == hipSuccess) e = hipDeviceSynchronize();
     d_pi.release();
     d_exch.release();
-    if (e != hipSuccess) {
-        std::string m = std::string("plan setup: ") + hipGetErrorString(e);
-        tphip_plan_destroy(p);
-        return fail(TPHIP_ERR_HIP, m);
+    return e;
+}
+
+// Launch configuration of the stage-1 kernels (locus likelihood, value, gradient): LDS sizes, whether they may run at all on
+// this tree, resident blocks per CU.
+static void configure_stage1_kernels(tphip_plan* p) {
+    // locus likelihood (value) kernel: no staging of the state masks in LDS, which cost it more than it saved (measured
+    // 13.6 ms vs 10.0 ms per 1616 candidates x 20000 columns x 64 taxa)
+    p->lik_lds = ((size_t)p->nnodes * 4 + (size_t)p->prog.stack_depth * 4 * kLikBlock) * sizeof(double);
+    p->lik_ok = p->lik_lds <= 150 * 1024;
+    if (p->lik_ok && p->lik_lds > 64 * 1024)
+        p->lik_ok = locus_loglik_kernel_allow_lds(150 * 1024) == hipSuccess;
+    // value kernel on transition matrices (locus_value_kernel.hpp): C columns per thread share the op decode and the
+    // scalar loads of a branch's matrix; parked siblings live in registers (template depth), LDS holds the tip matrices
+    // and the packed state masks
+    {
+        int cols = p->max_locus_cols >= 512 ? 2 : 1;
+        if (const char* env = getenv("TPHIP_VALUE_COLS")) cols = atoi(env) >= 2 ? 2 : 1;
+        p->value_cols = 0;
+        if (p->value_nops > 0 && p->prog.stack_depth <= kValueMaxDepth && !getenv("TPHIP_VALUE_EIGENBASIS")) {
+            const size_t need = (size_t)p->ntaxa * kValueTipRow * sizeof(double) + (size_t)p->nwords * cols * kLikBlock * sizeof(uint32_t);
+            if (need <= 96 * 1024 &&
+                (need <= 64 * 1024 || locus_value_kernel_allow_lds(cols, p->prog.stack_depth, 96 * 1024) == hipSuccess)) {
+                p->value_cols = cols;
+                p->value_lds = need;
+            }
+        }
     }
-    {   // persistent grid: exactly the waves the device keeps resident for this LDS footprint
-        hipDeviceProp_t prop;
-        int per_cu = 0;
-        if (hipGetDeviceProperties(&prop, d->device) != hipSuccess) { tphip_plan_destroy(p); return fail(TPHIP_ERR_HIP, "hipGetDeviceProperties failed"); }
-        const hipError_t oe = site_rate_kernel_occupancy(p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : kStreamWords, p->model, lds_bytes, &per_cu);
-        if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-        p->site_waves = per_cu * prop.multiProcessorCount;
-        p->num_cus = prop.multiProcessorCount;
-        // Deep trees (256 taxa: 4 parked partials = 24 KB per wave) are capped at 6 waves per CU by the LDS stack, not by
-        // the registers.  The deepest slots are the least used (C5 tree: 9 of 80 pushes per evaluation reach the fourth),
-        // so the streamed-words kernel has a variant that parks them in a global scratch row of the wave instead: with
-        // three slots in LDS (19.7 KB) eight waves fit.  Only worth it for the persistent grid (one scratch row per wave).
-        p->site_lds_depth = p->prog.stack_depth;
-        {
-            const int keep = (int)((160 * 1024 / 8 - kSiteLdsHeader * sizeof(double)) / (12 * kSiteBlock * sizeof(double)));   // = 3
-            bool want = p->nwords > 8 && p->prog.stack_depth > keep && per_cu < 8;
-            if (const char* es = getenv("TPHIP_SITE_SPILL")) want = (es[0] == '1') && p->nwords > 8 && p->prog.stack_depth > 1;
-            if (want) {
-                const int depth = std::max(1, std::min(keep, p->prog.stack_depth - 1));
-                const size_t lds2 = (kSiteLdsHeader + (size_t)depth * 12 * kSiteBlock) * sizeof(double);
-                int per2 = 0;
-                if (site_rate_kernel_occupancy(kStreamWordsSpill, p->model, lds2, &per2) == hipSuccess && per2 > per_cu &&
-                    ncols / ((int64_t)per2 * prop.multiProcessorCount) >= 1000) {   // persistent mode will be chosen below
-                    p->site_lds_depth = depth;
-                    p->site_waves = per2 * prop.multiProcessorCount;
-                }
-            }
-        }
-        // locus likelihood (value) kernel: no staging of the state masks in LDS, which cost it more than it saved (measured
-        // 13.6 ms vs 10.0 ms per 1616 candidates x 20000 columns x 64 taxa)
-        p->lik_lds = ((size_t)p->nnodes * 4 + (size_t)p->prog.stack_depth * 4 * kLikBlock) * sizeof(double);
-        p->lik_ok = p->lik_lds <= 150 * 1024;
-        if (p->lik_ok && p->lik_lds > 64 * 1024)
-            p->lik_ok = locus_loglik_kernel_allow_lds(150 * 1024) == hipSuccess;
-        // value kernel on transition matrices (locus_value_kernel.hpp): C columns per thread share the op decode and the
-        // scalar loads of a branch's matrix; parked siblings live in registers (template depth), LDS holds the tip matrices
-        // and the packed state masks
-        {
-            int cols = p->max_locus_cols >= 512 ? 2 : 1;
-            if (const char* env = getenv("TPHIP_VALUE_COLS")) cols = atoi(env) >= 2 ? 2 : 1;
-            p->value_cols = 0;
-            if (p->value_nops > 0 && p->prog.stack_depth <= kValueMaxDepth && !getenv("TPHIP_VALUE_EIGENBASIS")) {
-                const size_t need = (size_t)p->ntaxa * kValueTipRow * sizeof(double) + (size_t)p->nwords * cols * kLikBlock * sizeof(uint32_t);
-                if (need <= 96 * 1024 &&
-                    (need <= 64 * 1024 || locus_value_kernel_allow_lds(cols, p->prog.stack_depth, 96 * 1024) == hipSuccess)) {
-                    p->value_cols = cols;
-                    p->value_lds = need;
-                }
-            }
-        }
-        // gradient kernel: staging helps it (95.6 -> 91.7 ms)
-        p->grad_slots = kGradSlots;   // fewer accumulator addresses per branch when the tree would not fit otherwise
-        while (p->grad_slots > 1 && (size_t)p->nnodes * (kGradEF + 2 * kGradWaves * p->grad_slots) * sizeof(double) > 100 * 1024)
-            p->grad_slots >>= 1;
-        p->grad_lds = (size_t)p->nnodes * (kGradEF + 2 * kGradWaves * p->grad_slots) * sizeof(double);
-        const size_t grad_stage_bytes = (size_t)p->ntaxa * kGradBlock;
-        p->grad_stage = (grad_stage_bytes <= 48 * 1024 && p->grad_lds + grad_stage_bytes <= 150 * 1024) ? 1 : 0;
-        if (p->grad_stage) p->grad_lds += grad_stage_bytes;
-        p->grad_ok = p->grad_lds <= 150 * 1024;
-        if (p->grad_ok && p->grad_lds > 64 * 1024)
-            p->grad_ok = locus_grad_kernel_allow_lds(150 * 1024) == hipSuccess;
-        if (p->grad_ok) {
-            int bpc = 1;
-            if (locus_grad_kernel_occupancy(p->grad_lds, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-            // the tape of the resident blocks should stay within reach of the 256 MB memory-side cache: with 64 taxa, 4
-            // blocks per CU (390 MB of tape) ran slower than 3 (91 vs 85 ms); fewer than 3 loses more to latency
-            const size_t tape_per_block = (size_t)std::max(1, p->prog.ntape + p->prog.stack_depth) * 4 * kGradBlock * sizeof(double);
-            if (tape_per_block * (size_t)p->num_cus * (size_t)bpc > ((size_t)300 << 20)) bpc = std::min(bpc, 3);
-            p->grad_blocks_per_cu = bpc;
-        }
-        // transition-matrix gradient kernel: LDS = tip table + tipY + parked adjoints + per-branch accumulators + state codes
+    // gradient kernel: staging helps it (95.6 -> 91.7 ms)
+    p->grad_slots = kGradSlots;   // fewer accumulator addresses per branch when the tree would not fit otherwise
+    while (p->grad_slots > 1 && (size_t)p->nnodes * (kGradEF + 2 * kGradWaves * p->grad_slots) * sizeof(double) > 100 * 1024)
+        p->grad_slots >>= 1;
+    p->grad_lds = (size_t)p->nnodes * (kGradEF + 2 * kGradWaves * p->grad_slots) * sizeof(double);
+    const size_t grad_stage_bytes = (size_t)p->ntaxa * kGradBlock;
+    p->grad_stage = (grad_stage_bytes <= 48 * 1024 && p->grad_lds + grad_stage_bytes <= 150 * 1024) ? 1 : 0;
+    if (p->grad_stage) p->grad_lds += grad_stage_bytes;
+    p->grad_ok = p->grad_lds <= 150 * 1024;
+    if (p->grad_ok && p->grad_lds > 64 * 1024)
+        p->grad_ok = locus_grad_kernel_allow_lds(150 * 1024) == hipSuccess;
+    if (p->grad_ok) {
+        int bpc = 1;
+        if (locus_grad_kernel_occupancy(p->grad_lds, &bpc) != hipSuccess || bpc < 1) bpc = 1;
+        // the tape of the resident blocks should stay within reach of the 256 MB memory-side cache: with 64 taxa, 4
+        // blocks per CU (390 MB of tape) ran slower than 3 (91 vs 85 ms); fewer than 3 loses more to latency
+        const size_t tape_per_block = (size_t)std::max(1, p->prog.ntape + p->prog.stack_depth) * 4 * kGradBlock * sizeof(double);
+        if (tape_per_block * (size_t)p->num_cus * (size_t)bpc > ((size_t)300 << 20)) bpc = std::min(bpc, 3);
+        p->grad_blocks_per_cu = bpc;
+    }
+    // transition-matrix gradient kernel: LDS = tip table + tipY + parked adjoints + per-branch accumulators + state codes
+    if (p->grad2_ok) {
+        p->grad2_lds = ((size_t)p->ntaxa * kValueTipRow + 64 + (size_t)p->grad2_rdepth * 4 * kGrad2Block +
+                        2 * (size_t)kGrad2Waves * p->nnodes) * sizeof(double) + (size_t)p->nwords * kGrad2Block * sizeof(uint32_t);
+        p->grad2_ok = p->value_cols > 0 && p->grad2_lds <= 96 * 1024 &&
+                      (p->grad2_lds <= 64 * 1024 || locus_grad2_kernel_allow_lds(p->prog.stack_depth, 96 * 1024) == hipSuccess);
         if (p->grad2_ok) {
-            p->grad2_lds = ((size_t)p->ntaxa * kValueTipRow + 64 + (size_t)p->grad2_rdepth * 4 * kGrad2Block +
-                            2 * (size_t)kGrad2Waves * p->nnodes) * sizeof(double) + (size_t)p->nwords * kGrad2Block * sizeof(uint32_t);
-            p->grad2_ok = p->value_cols > 0 && p->grad2_lds <= 96 * 1024 &&
-                          (p->grad2_lds <= 64 * 1024 || locus_grad2_kernel_allow_lds(p->prog.stack_depth, 96 * 1024) == hipSuccess);
-            if (p->grad2_ok) {
-                int bpc = 1;
-                if (locus_grad2_kernel_occupancy(p->prog.stack_depth, p->grad2_lds, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-                p->grad2_blocks_per_cu = bpc;
-            }
-        }
-        // Small batches (an equal share would be under ~1000 columns) leave the persistent grid: the mixed-loci mode below,
-        // or one workgroup per locus-aligned slice (cutting a small locus in two doubles its prologue and drain: measured on C2).
-        p->site_persistent = (ncols / p->site_waves >= 1000) ? 1 : 0;
-        if (const char* e3 = getenv("TPHIP_SITE_PERSISTENT")) p->site_persistent = (e3[0] == '1');
-        if (!p->site_persistent && p->site_lds_depth < p->prog.stack_depth) {   // the scratch rows are per persistent wave
-            p->site_lds_depth = p->prog.stack_depth;
-            p->site_waves = per_cu * prop.multiProcessorCount;
-        }
-        // Small batches of trees up to 64 taxa: equal shares of the work list, a wave carrying columns of several loci at
-        // once (site_rate_kernel<NW, false, true>); the slice mode remains for the streamed words.
-        p->site_mixed = (!p->site_persistent && p->nwords <= 8 && ncols < ((int64_t)1 << kMixedColBits)) ? 1 : 0;
-        if (const char* em = getenv("TPHIP_SITE_MIXED")) p->site_mixed = (em[0] == '1') && p->nwords <= 8 && ncols < ((int64_t)1 << kMixedColBits);
-        if (p->site_mixed) {
-            int per3 = 0;
-            const size_t lds3 = (kMixedLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
-            const int64_t simds = 4 * (int64_t)prop.multiProcessorCount;
-            const double est_rounds = (double)ncols * (p->start_rule == TPHIP_START_REFERENCE ? 2.2 : 1.4) / (double)(kSiteBlock * simds);
-            if (lds3 > 160 * 1024 || site_rate_kernel_occupancy(kMixedVariant + (p->nwords <= 2 ? 2 : 8), p->model, lds3, &per3) != hipSuccess || per3 < 1) p->site_mixed = 0;
-            // a batch that wants two waves per SIMD on a tree whose tables leave room for six per CU (64 taxa: 23.3 KB of LDS
-            // per wave) stays with the slices: 1900 loci x 1000 x 64, 3.36 ms in slices, 4.10 with 1024 mixed waves
-            else if (est_rounds >= 28.0 && per3 < 8 && !getenv("TPHIP_SITE_MIXED")) p->site_mixed = 0;
-            else {
-                p->site_persistent = 0;
-                // One wave per SIMD or two?  A second wave on a SIMD adds half again to its throughput (C2: 15.2 us per round of
-                // evaluations alone, 19.8 us each for two) but lengthens every round of the wave that carries the slowest column
-                // (22 evaluations on C2 when the average column takes 3.7), and the launch ends with that wave.  Measured, one
-                // per SIMD / two: C2 (17 rounds of evaluations per SIMD) 0.348 / 0.391 ms, two C2s (34 rounds) 0.789 / 0.508,
-                // 300 loci x 1000 x 64 (8 rounds) 0.757 / 0.932, the resampled 5-taxon locus of bench.py --workload R1 (18 rounds;
-                // 1.5 after de-duplication) 0.150 / 0.165 and 0.099 / 0.138; 1152 waves on C2 0.422 (SIMDs shared unevenly).
-                // The grid is two per SIMD where eight waves fit a CU (64-taxon trees hold six: one per SIMD, and the batches
-                // that want two stay with the slices, above); the kernel uses half of it when the work list -- known on the
-                // device only, after classification and de-duplication -- is shorter than ~24 rounds per SIMD at 3.7
-                // evaluations per column from HyPhy's start value, 2.4 from the parsimony start.
-                const int64_t want = (per3 < 8) ? std::min<int64_t>(simds, (int64_t)per3 * prop.multiProcessorCount)
-                                                : 8 * (int64_t)prop.multiProcessorCount;
-                p->mixed_few_waves = (int32_t)std::min<int64_t>(simds, want);
-                p->mixed_switch_cols = (int64_t)(24.0 * (double)(kSiteBlock * simds) / (p->start_rule == TPHIP_START_REFERENCE ? 3.7 : 2.4));
-                p->site_waves = (int32_t)std::max<int64_t>(1, std::min<int64_t>(want, (ncols + kSiteBlock - 1) / kSiteBlock));
-            }
-        }
-        if (const char* e2 = getenv("TPHIP_SITE_WAVES")) { long v = atol(e2); if (v >= 1) { p->site_waves = (int32_t)v; p->mixed_switch_cols = 0; } }  // tuning knob
-        // Share sizes of the persistent grid.  Equal shares (one per resident wave) are equal column counts, not equal
-        // work: loci differ in evaluations per column, and with 5-7 resident waves per CU (deep LDS stacks) a wave that
-        // shares its SIMD runs slower than one that does not.  So the resident waves' first shares take 80-90 % of the
-        // batch and the rest is cut into twice as many small shares that the dispatcher hands to whichever waves
-        // finish first: site_rate_kernel C3 8.4 -> 7.0 ms, C4 share 9.8 -> 9.2, C5 share 20.9 -> 17.1.  Batches whose
-        // shares are short anyway only gain drains (2.2 M columns in 2200 loci: +3.5 %): they keep equal shares.
-        {
-            const int64_t share = ncols / std::max(1, p->site_waves);
-            const bool uneven = p->site_persistent && share >= 1500;
-            p->site_grid_mult = uneven ? 3 : 1;
-            // a share that spans several short loci pays a drain at every locus boundary, so its tail shares should be
-            // fewer columns: 90 % up front there (C4: 9.0 vs 9.2-9.3 ms), 80 % when shares lie inside long loci (C3: 6.9 vs 7.0)
-            const int64_t avg_locus = ncols / std::max<int64_t>(1, d->nloci);
-            p->site_first_fraction = !uneven ? 0.0 : (share >= 2 * avg_locus ? 0.9 : 0.8);
-            // whole C5 with the spilled stack slot (8 waves per CU): (3, 0.8) 109.6 ms, (3, 0.9) 113.3, (4, 0.85) 109.1, (2, 0.8) 117.1
-            if (uneven && p->site_lds_depth < p->prog.stack_depth) p->site_first_fraction = 0.8;
-            if (const char* e8 = getenv("TPHIP_SITE_FIRST_FRACTION")) p->site_first_fraction = atof(e8);
-            if (const char* e7 = getenv("TPHIP_SITE_GRID_MULT")) { long v = atol(e7); if (v >= 1 && v <= 16) p->site_grid_mult = (int32_t)v; }
-            // A/B and test switch: 0 = the persistent shares hand their segments out in list order, as the other modes do
-            if (const char* e6 = getenv("TPHIP_SITE_TAIL_ORDER")) p->site_tail_order = (e6[0] != '0');
-            // Shares by predicted work (site_rate_kernel.hpp; persistent mode with one locus at a time only): the weights are the
-            // mean evaluations of a marked and of an unmarked column.  TPHIP_SITE_SHARE_WORK=0 is the A/B
-            // and test switch back to shares of equal column counts and a list without reserved tails.
-            // On where the first-round shares lie inside long loci (C3: a locus holds ~20 of them, its reserved tail thousands
-            // of columns); where a share spans several short loci the tail of a locus is a segment of a lane-fill or two with
-            // a drain of its own, and the old hand-out is faster (whole C4 +6.5 %, whole C5 +2-5 %: DESIGN section 8, r10).
-            double reserve = kDefaultReserve, w_slow = 2.9, w_easy = 2.04;
-            p->site_share_work = (uneven && share < 2 * avg_locus) ? 1 : 0;
-            if (const char* e5 = getenv("TPHIP_SITE_SHARE_WORK")) p->site_share_work = (e5[0] != '0');
-            if (const char* e4 = getenv("TPHIP_SITE_RESERVE")) reserve = atof(e4);
-            if (const char* e1 = getenv("TPHIP_SITE_CLASS_WEIGHTS")) {
-                double a = 0, b = 0;
-                if (sscanf(e1, "%lf,%lf", &a, &b) == 2 && a > 0 && b > 0 && a <= 16 && b <= 16) { w_slow = a; w_easy = b; }
-            }
-            // the interpolation inside a locus multiplies its predicted work by its column count in 64 bits
-            if (!p->site_persistent || p->site_mixed || p->max_locus_cols > ((int64_t)1 << 24)) p->site_share_work = 0;
-            p->site_w_slow = std::max<int32_t>(1, (int32_t)lround(w_slow * (1 << kShareWeightShift)));
-            p->site_w_easy = std::max<int32_t>(1, (int32_t)lround(w_easy * (1 << kShareWeightShift)));
-            // without later shares there is nobody to take a reserved tail
-            reserve = (p->site_share_work && p->site_grid_mult > 1) ? std::min(std::max(reserve, 0.0), 1.0) : 0.0;
-            p->site_reserve_q = (int32_t)lround(reserve * (1 << kReserveShift));
+            int bpc = 1;
+            if (locus_grad2_kernel_occupancy(p->prog.stack_depth, p->grad2_lds, &bpc) != hipSuccess || bpc < 1) bpc = 1;
+            p->grad2_blocks_per_cu = bpc;
         }
     }
-    // workspace layout
-    size_t off = 0;
-    p->ws_work_cols = off; off = align_up(off + sizeof(int32_t) * (size_t)ncols, 256);
-    if (!p->site_persistent || p->site_reserve_q > 0) {   // small batches: slow-columns-first copy of the work list; reserved tails: compact_kernel's scratch
-        p->ws_work_cols2 = off; off = align_up(off + sizeof(int32_t) * (size_t)ncols, 256);
+}
+
+static int plan_setup_failed(tphip_plan* p, hipError_t e) {
+    std::string m = std::string("plan setup: ") + hipGetErrorString(e);
+    tphip_plan_destroy(p);
+    return fail(TPHIP_ERR_HIP, m);
+}
+
+int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
+    // 1. validate
+    if (!d_in || !out) return fail(TPHIP_ERR_INVALID, "null plan descriptor");
+    *out = nullptr;
+    // the caller's struct may be shorter (built against an older header): its missing trailing fields are zero
+    if (d_in->struct_size < offsetof(tphip_plan_desc, round_decimals) + sizeof(int32_t) || d_in->struct_size > 4096)
+        return fail(TPHIP_ERR_INVALID, "tphip_plan_desc.struct_size not set (zero-initialise the struct, then set it to sizeof)");
+    tphip_plan_desc d_copy;
+    memset(&d_copy, 0, sizeof(d_copy));
+    memcpy(&d_copy, d_in, std::min<size_t>(d_in->struct_size, sizeof(d_copy)));
+    d_copy.struct_size = (uint32_t)sizeof(d_copy);
+    const tphip_plan_desc* d = &d_copy;
+    int ndev = tphip_device_count();
+    if (ndev <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
+    if (d->device < 0 || d->device >= ndev) return fail(TPHIP_ERR_INVALID, "device ordinal out of range");
+    if (d->ntaxa < 2) return fail(TPHIP_ERR_INVALID, "ntaxa must be >= 2");
+    if (!d->parent || !d->branch_len || !d->leaf_taxon) return fail(TPHIP_ERR_INVALID, "null tree arrays");
+    if (d->model != TPHIP_MODEL_GTR && d->model != TPHIP_MODEL_F81) return fail(TPHIP_ERR_INVALID, "unknown model");
+    if (d->model == TPHIP_MODEL_F81 && d->exch)
+        return fail(TPHIP_ERR_INVALID, "exch must be NULL with TPHIP_MODEL_F81 (its exchangeabilities are all 1)");
+    if (d->nloci < 1 || !d->locus_offsets || !d->pi || (d->model == TPHIP_MODEL_GTR && !d->exch))
+        return fail(TPHIP_ERR_INVALID, "null or empty locus arrays");
+    if (d->T < 0 || d->n_t < 0 || d->n_i < 0) return fail(TPHIP_ERR_INVALID, "negative schedule size");
+    if ((d->n_t && !d->times) || (d->n_i && !d->intervals)) return fail(TPHIP_ERR_INVALID, "null times/intervals");
+    if (!(d->correction > 0.0)) return fail(TPHIP_ERR_INVALID, "correction must be > 0");
+    if (d->integ_mode != TPHIP_INTEG_QUADPACK && d->integ_mode != TPHIP_INTEG_CLOSED)
+        return fail(TPHIP_ERR_INVALID, "unknown integ_mode");
+    if (d->start_rule != TPHIP_START_AUTO && d->start_rule != TPHIP_START_PARSIMONY && d->start_rule != TPHIP_START_REFERENCE)
+        return fail(TPHIP_ERR_INVALID, "unknown start_rule");
+    if (d->pattern_dedup != TPHIP_DEDUP_AUTO && d->pattern_dedup != TPHIP_DEDUP_OFF && d->pattern_dedup != TPHIP_DEDUP_ON)
+        return fail(TPHIP_ERR_INVALID, "unknown pattern_dedup");
+    for (int i = 0; i < d->n_t; ++i)
+        if (d->times[i] < 0 || d->times[i] >= d->T)  // numpy would raise IndexError (tapir/compute.py:78)
+            return fail(TPHIP_ERR_INVALID, "a --times value is outside 0..T-1 (index out of bounds for the net PI vector)");
+    for (int i = 0; i < d->n_i; ++i)
+        if (!(d->intervals[2 * i] < d->intervals[2 * i + 1]))  // assert at tapir/compute.py:90-91
+            return fail(TPHIP_ERR_INVALID, "Start time is sooner than end time in an interval");
+    if (d->locus_offsets[0] != 0) return fail(TPHIP_ERR_INVALID, "locus_offsets[0] must be 0");
+    for (int64_t l = 0; l < d->nloci; ++l) {
+        if (d->locus_offsets[l + 1] < d->locus_offsets[l]) return fail(TPHIP_ERR_INVALID, "locus_offsets not monotone");
+        if (const int rc = check_locus_model(d->pi, d->exch, l)) return rc;
     }
-    p->ws_work_count = off; off = align_up(off + sizeof(int32_t) * (size_t)d->nloci, 256);
-    p->ws_work_prefix = off; off = align_up(off + sizeof(int64_t) * ((size_t)d->nloci + 1), 256);
-    p->ws_slice_prefix = off; off = align_up(off + sizeof(int64_t) * ((size_t)d->nloci + 1), 256);
-    p->ws_work_class = off; off = align_up(off + sizeof(int32_t) * 2 * (size_t)d->nloci, 256);
-    p->ws_work_wprefix = off; off = align_up(off + sizeof(int64_t) * ((size_t)d->nloci + 1), 256);
-    p->ws_part_prefix = off; off = align_up(off + sizeof(int64_t) * 2 * ((size_t)d->nloci + 1), 256);
-    p->ws_part_start = off; off = align_up(off + sizeof(int64_t) * 2 * ((size_t)d->nloci + 1), 256);
-    // Long loci build the work list chunk-parallel (compact_count / scan / scatter kernels); TPHIP_COMPACT_CHUNKED=0/1 is the
-    // A/B and test switch that forces either path on any shape.
-    p->compact_chunked = p->max_locus_cols > 2048 ? 1 : 0;
-    if (const char* ec = getenv("TPHIP_COMPACT_CHUNKED")) p->compact_chunked = (ec[0] != '0');
-    p->ws_chunk_cnt = off; off = align_up(off + sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(1, p->n_pi_chunks), 256);
-    p->ws_partial = off; off = align_up(off + sizeof(double) * (size_t)p->n_pi_chunks * (size_t)(d->T + 2 * d->n_i), 256);
-    p->ws_packed = off; off = align_up(off + sizeof(uint32_t) * (size_t)p->nwords * (size_t)ncols, 256);
-    if (const char* e9 = getenv("TPHIP_DEDUP")) {   // test/tuning knob: 0 = never, 1 = always, anything else = automatic
-        p->dedup_mode = (e9[0] == '0') ? DEDUP_OFF : (e9[0] == '1') ? DEDUP_ON : DEDUP_AUTO;
+    const int64_t ncols = d->locus_offsets[d->nloci];
+    if (ncols >= (int64_t)1 << 31) return fail(TPHIP_ERR_INVALID, "more than 2^31-1 columns in one batch");
+    std::vector<double> cat;
+    if (d->ncat > 1) {
+        if (d->ncat > 16) return fail(TPHIP_ERR_INVALID, "at most 16 rate categories");
+        if (!d->cat_rate || !d->cat_weight) return fail(TPHIP_ERR_INVALID, "rate categories need cat_rate and cat_weight");
+        double wsum = 0;
+        for (int k = 0; k < d->ncat; ++k) {
+            if (!(d->cat_rate[k] > 0.0) || !(d->cat_weight[k] > 0.0) || !std::isfinite(d->cat_rate[k]) || !std::isfinite(d->cat_weight[k]))
+                return fail(TPHIP_ERR_INVALID, "category rates and weights must be positive and finite");
+            wsum += d->cat_weight[k];
+        }
+        cat.resize(2 * (size_t)d->ncat);
+        for (int k = 0; k < d->ncat; ++k) { cat[k] = d->cat_rate[k]; cat[d->ncat + k] = std::log(d->cat_weight[k] / wsum); }
     }
-    if (p->dedup_mode == DEDUP_AUTO && ncols < kDedupAutoMinColumns) p->dedup_mode = DEDUP_OFF;   // small batch: see pattern_kernels.hpp
-    if (p->dedup_mode != DEDUP_OFF) {
-        p->ws_hash = off; off = align_up(off + sizeof(uint64_t) * (size_t)ncols, 256);
-        p->ws_dup_of = off; off = align_up(off + sizeof(int32_t) * (size_t)ncols, 256);
-        p->ws_tab_key = off; off = align_up(off + sizeof(unsigned long long) * 2 * (size_t)ncols, 256);
-        p->ws_tab_val = off; off = align_up(off + sizeof(int32_t) * 2 * (size_t)ncols, 256);
-        p->ws_dedup_on = off; off = align_up(off + sizeof(int32_t) * (size_t)d->nloci, 256);
+    const PlanKnobs knobs = knobs_from_env();
+
+    // 2. the tree programs
+    tphip_plan* p = new tphip_plan();
+    p->device = d->device; p->ntaxa = d->ntaxa; p->nnodes = d->nnodes; p->nloci = d->nloci; p->ncols = ncols;
+    p->T = d->T; p->n_t = d->n_t; p->n_i = d->n_i; p->integ_mode = d->integ_mode;
+    p->threshold = d->threshold; p->round_decimals = d->round_decimals; p->correction = d->correction;
+    p->model = d->model;
+    p->ncat = cat.empty() ? 0 : d->ncat;
+    std::string terr = build_tree_program(d->ntaxa, d->nnodes, d->parent, d->branch_len, d->leaf_taxon, &p->prog);
+    if (!terr.empty()) { delete p; return fail(TPHIP_ERR_INVALID, "tree: " + terr); }
+    if (p->prog.nleaves != d->ntaxa) {  // HyPhy refuses a tree / alignment mismatch as well
+        delete p;
+        return fail(TPHIP_ERR_INVALID, "tree: the number of leaves differs from the number of alignment rows");
     }
-    if (p->site_lds_depth < p->prog.stack_depth) {
-        const size_t rows = (size_t)p->site_waves * (size_t)p->site_grid_mult * (size_t)(p->prog.stack_depth - p->site_lds_depth);
-        p->ws_spill = off; off = align_up(off + rows * 12 * kSiteBlock * sizeof(double), 256);
-    }
-    p->ws_total = off + 256;
+    if (site_lds_bytes(p->prog.stack_depth) > 160 * 1024) { delete p; return fail(TPHIP_ERR_INVALID, "tree needs a deeper LDS stack than 160 KiB allows"); }
+    int64_t ntips = 0;
+    for (const TreeOp& op : p->prog.ops) ntips += op.code <= OP_TIP_MUL;
+    p->nwords = (int32_t)((ntips + 7) / 8);
+    p->h_offsets.assign(d->locus_offsets, d->locus_offsets + d->nloci + 1);
+    for (int64_t l = 0; l < d->nloci; ++l)
+        p->max_locus_cols = std::max<int64_t>(p->max_locus_cols, d->locus_offsets[l + 1] - d->locus_offsets[l]);
+
+    // 3. how the site-rate stage will run (site_launch_plan.hpp)
+    hipError_t e = hipSetDevice(d->device);
+    if (e != hipSuccess) return plan_setup_failed(p, e);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, d->device) != hipSuccess) { tphip_plan_destroy(p); return fail(TPHIP_ERR_HIP, "hipGetDeviceProperties failed"); }
+    p->num_cus = prop.multiProcessorCount;
+    SiteShape shape;
+    shape.ncols = ncols; shape.nloci = d->nloci; shape.max_locus_cols = p->max_locus_cols; shape.ntaxa = d->ntaxa;
+    shape.nwords = p->nwords; shape.stack_depth = p->prog.stack_depth; shape.model = d->model; shape.ncat = d->ncat;
+    shape.start_rule = d->start_rule; shape.pattern_dedup = d->pattern_dedup; shape.T = d->T; shape.n_i = d->n_i;
+    p->site = decide_site_launch(shape, p->num_cus, knobs, [&](int variant, size_t lds_bytes) {
+        int per_cu = 0;
+        return site_rate_kernel_occupancy(variant, shape.model, lds_bytes, &per_cu) == hipSuccess ? per_cu : 0;
+    });
+    p->host_split = host_split_groups(knobs);
+
+    // 4. the chunk tables and the workspace layout
+    const ChunkTables chunks = build_chunk_tables(p->h_offsets.data(), d->nloci, p->site.chunk_cols);
+    p->n_site_chunks = (int64_t)chunks.site_chunk_locus.size();
+    p->n_pi_chunks = (int64_t)chunks.pi_chunk_locus.size();
+    p->ws = layout_workspace(shape, p->site, p->n_pi_chunks);
+
+    // 5. upload
+    e = upload_plan(p, d, cat, chunks);
+    if (e != hipSuccess) return plan_setup_failed(p, e);
+
+    // 6. the stage-1 kernels
+    configure_stage1_kernels(p);
     p->saved = save_desc(d);
-    p->host_split = 2;   // measured (C3 / C4, pinned buffers): 1 group 16.5 / 151 ms, 2: 12.8 / 127, 3: 17.3 / 154, 4: 14.9 / 140, 6: 15.2 / 135
-    if (const char* hs = getenv("TPHIP_HOST_SPLIT")) p->host_split = std::max(1, std::min(64, atoi(hs)));
     *out = p;
     return TPHIP_OK;
 }
 
 int32_t tphip_plan_table_width(const tphip_plan* p) { return p ? p->T + p->n_t + 2 * p->n_i : 0; }
 int64_t tphip_plan_ncols(const tphip_plan* p) { return p ? p->ncols : 0; }
-size_t tphip_plan_workspace_bytes(const tphip_plan* p) { return p ? p->ws_total : 0; }
+size_t tphip_plan_workspace_bytes(const tphip_plan* p) { return p ? p->ws.total : 0; }
 double tphip_plan_chrono_length(const tphip_plan* p) { return p ? p->prog.chrono_length : 0.0; }
 int32_t tphip_plan_stack_depth(const tphip_plan* p) { return p ? p->prog.stack_depth : 0; }
 
@@ -725,13 +607,13 @@ static PiParams pi_params(const tphip_plan* p, const double* d_rates, const int3
 // the reserved tails of the hand-out by predicted work (compact_classes_kernel's list), else compact_kernel's plain list.
 static void launch_compact_chunked(tphip_plan* p, const uint8_t* d_flag, const double* d_lnl, int32_t* work_cols, int32_t* work_count,
                                   int32_t* work_class, void* ws, hipStream_t st) {
-    int2* cnt = (int2*)((char*)ws + p->ws_chunk_cnt);
+    int2* cnt = (int2*)((char*)ws + p->ws.chunk_cnt);
     const dim3 chunks((unsigned)p->n_pi_chunks), loci((unsigned)p->nloci), block(kCompactChunkBlock);
     if (work_class) {
         compact_count_kernel<true><<<chunks, block, 0, st>>>(d_flag, d_lnl, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt);
         compact_scan_kernel<true><<<loci, block, 0, st>>>(p->d_locus_pichunk_offsets.p, cnt, work_count, work_class);
         compact_scatter_kernel<true><<<chunks, block, 0, st>>>(d_flag, d_lnl, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt,
-                                                               work_count, work_class, p->site_reserve_q, work_cols);
+                                                               work_count, work_class, p->site.reserve_q, work_cols);
     } else {
         compact_count_kernel<false><<<chunks, block, 0, st>>>(d_flag, nullptr, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt);
         compact_scan_kernel<false><<<loci, block, 0, st>>>(p->d_locus_pichunk_offsets.p, cnt, work_count, nullptr);
@@ -743,25 +625,25 @@ static void launch_compact_chunked(tphip_plan* p, const uint8_t* d_flag, const d
 static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_rate, double* d_subst, double* d_lnl,
                              uint8_t* d_flag, int32_t* d_nres, void* ws, hipStream_t st, int slot) {
     p->last_run_in_parts = false;
-    int32_t* work_cols = (int32_t*)((char*)ws + p->ws_work_cols);
-    int32_t* work_count = (int32_t*)((char*)ws + p->ws_work_count);
+    int32_t* work_cols = (int32_t*)((char*)ws + p->ws.work_cols);
+    int32_t* work_count = (int32_t*)((char*)ws + p->ws.work_count);
     ClassifyParams C;
     C.states = d_states; C.ncols_total = p->ncols; C.ntaxa = p->ntaxa; C.models = p->d_models.p;
     C.locus_offsets = p->d_offsets.p; C.chunk_locus = p->d_pi_chunk_locus.p; C.chunk_index = p->d_pi_chunk_index.p;
     C.rate = d_rate; C.subst = d_subst; C.lnl = d_lnl; C.flag = d_flag; C.nres = d_nres;
     C.chrono_length = p->prog.chrono_length;
     C.steps = (const int2*)p->d_cls_steps.p; C.tail_pops = p->prog.cls_tail_pops; C.max_pops = p->prog.cls_max_pops;
-    C.packed = (uint32_t*)((char*)ws + p->ws_packed);
-    C.start_scale = (p->start_rule == TPHIP_START_REFERENCE) ? 0.0 : 1.0;
-    const bool dedup = p->dedup_mode != DEDUP_OFF && p->n_pi_chunks > 0;
-    C.hash = dedup ? (uint64_t*)((char*)ws + p->ws_hash) : nullptr;
+    C.packed = (uint32_t*)((char*)ws + p->ws.packed);
+    C.start_scale = (p->site.start_rule == TPHIP_START_REFERENCE) ? 0.0 : 1.0;
+    const bool dedup = p->site.dedup_mode != DEDUP_OFF && p->n_pi_chunks > 0;
+    C.hash = dedup ? (uint64_t*)((char*)ws + p->ws.hash) : nullptr;
     DedupParams D;
     if (dedup) {
         D.locus_offsets = p->d_offsets.p; D.chunk_locus = p->d_pi_chunk_locus.p; D.chunk_index = p->d_pi_chunk_index.p;
         D.hash = C.hash; D.packed = C.packed; D.nwords = p->nwords; D.ncols_total = p->ncols; D.flag = d_flag;
-        D.dup_of = (int32_t*)((char*)ws + p->ws_dup_of);
-        D.tab_key = (unsigned long long*)((char*)ws + p->ws_tab_key); D.tab_val = (int32_t*)((char*)ws + p->ws_tab_val);
-        D.on = (int32_t*)((char*)ws + p->ws_dedup_on); D.mode = p->dedup_mode;
+        D.dup_of = (int32_t*)((char*)ws + p->ws.dup_of);
+        D.tab_key = (unsigned long long*)((char*)ws + p->ws.tab_key); D.tab_val = (int32_t*)((char*)ws + p->ws.tab_val);
+        D.on = (int32_t*)((char*)ws + p->ws.dedup_on); D.mode = p->site.dedup_mode;
         D.rate = d_rate; D.subst = d_subst; D.lnl = d_lnl;
     }
     if (p->n_pi_chunks > 0) {
@@ -772,31 +654,31 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
             dedup_insert_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
             dedup_resolve_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
         }
-        if (p->site_share_work) {
+        if (p->site.share_work) {
             // shares by predicted work: the list with class counts and reserved tails, and their scans (compact_classes_kernel
             // reads the marks, 8 more bytes per work column in its chain of barriers, and appends the tails: C3 47 -> 100 us;
             // long loci take the chunk-parallel kernels instead: 40 us)
-            int32_t* work_class = (int32_t*)((char*)ws + p->ws_work_class);
-            if (p->compact_chunked) {
+            int32_t* work_class = (int32_t*)((char*)ws + p->ws.work_class);
+            if (p->site.compact_chunked) {
                 launch_compact_chunked(p, d_flag, d_lnl, work_cols, work_count, work_class, ws, st);
             } else {
-                int32_t* scratch = p->site_reserve_q > 0 ? (int32_t*)((char*)ws + p->ws_work_cols2) : nullptr;
-                if (p->max_locus_cols > 2048) compact_classes_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
-                else compact_classes_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site_reserve_q, scratch, work_class);
+                int32_t* scratch = p->site.reserve_q > 0 ? (int32_t*)((char*)ws + p->ws.work_cols2) : nullptr;
+                if (p->max_locus_cols > 2048) compact_classes_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site.reserve_q, scratch, work_class);
+                else compact_classes_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site.reserve_q, scratch, work_class);
             }
             ScanClasses SC;
-            SC.cls = work_class; SC.reserve_q = p->site_reserve_q; SC.w_slow = p->site_w_slow; SC.w_easy = p->site_w_easy;
+            SC.cls = work_class; SC.reserve_q = p->site.reserve_q; SC.w_slow = p->site.w_slow; SC.w_easy = p->site.w_easy;
             SC.locus_offsets = p->d_offsets.p;
-            SC.wprefix = (int64_t*)((char*)ws + p->ws_work_wprefix); SC.part_prefix = (int64_t*)((char*)ws + p->ws_part_prefix);
-            SC.part_start = (int64_t*)((char*)ws + p->ws_part_start);
-            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site_chunk_cols, (int64_t*)((char*)ws + p->ws_work_prefix),
-                                              (int64_t*)((char*)ws + p->ws_slice_prefix), &SC));
+            SC.wprefix = (int64_t*)((char*)ws + p->ws.work_wprefix); SC.part_prefix = (int64_t*)((char*)ws + p->ws.part_prefix);
+            SC.part_start = (int64_t*)((char*)ws + p->ws.part_start);
+            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site.chunk_cols, (int64_t*)((char*)ws + p->ws.work_prefix),
+                                              (int64_t*)((char*)ws + p->ws.slice_prefix), &SC));
         } else {
-            if (p->compact_chunked) launch_compact_chunked(p, d_flag, nullptr, work_cols, work_count, nullptr, ws, st);
+            if (p->site.compact_chunked) launch_compact_chunked(p, d_flag, nullptr, work_cols, work_count, nullptr, ws, st);
             else if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
             else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
-            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site_chunk_cols, (int64_t*)((char*)ws + p->ws_work_prefix),
-                                              (int64_t*)((char*)ws + p->ws_slice_prefix), nullptr));
+            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site.chunk_cols, (int64_t*)((char*)ws + p->ws.work_prefix),
+                                              (int64_t*)((char*)ws + p->ws.slice_prefix), nullptr));
         }
     }
     HIP_TRY(hipMemsetAsync(p->d_evals.p, 0, 8 * sizeof(unsigned long long), st));
@@ -804,44 +686,41 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
     S.states = d_states; S.ncols_total = p->ncols; S.models = p->d_models.p; S.ops = p->d_ops.p;
     S.nops = (int32_t)p->prog.ops.size(); S.stack_depth = p->prog.stack_depth; S.chrono_length = p->prog.chrono_length;
     S.locus_offsets = p->d_offsets.p; S.chunk_locus = p->d_site_chunk_locus.p; S.chunk_index = p->d_site_chunk_index.p;
-    S.chunk_cols = p->site_chunk_cols;
-    S.packed = (const uint32_t*)((char*)ws + p->ws_packed); S.nwords = p->nwords;
+    S.chunk_cols = p->site.chunk_cols;
+    S.packed = (const uint32_t*)((char*)ws + p->ws.packed); S.nwords = p->nwords;
     S.work_cols = work_cols; S.work_count = work_count;
-    S.work_cols2 = (!p->site_persistent && p->ws_work_cols2) ? (int32_t*)((char*)ws + p->ws_work_cols2) : nullptr;
-    S.work_prefix = (const int64_t*)((char*)ws + p->ws_work_prefix); S.nloci = p->nloci;
-    S.slice_prefix = (const int64_t*)((char*)ws + p->ws_slice_prefix);
+    S.work_cols2 = (!p->site.persistent && p->ws.work_cols2) ? (int32_t*)((char*)ws + p->ws.work_cols2) : nullptr;
+    S.work_prefix = (const int64_t*)((char*)ws + p->ws.work_prefix); S.nloci = p->nloci;
+    S.slice_prefix = (const int64_t*)((char*)ws + p->ws.slice_prefix);
     S.rate = d_rate; S.subst = d_subst; S.lnl = d_lnl; S.flag = d_flag; S.eval_counter = p->d_evals.p;
-    const bool spill = p->site_lds_depth < p->prog.stack_depth;
-    const size_t lds = (kSiteLdsHeader + (size_t)p->site_lds_depth * 12 * kSiteBlock) * sizeof(double);
-    S.lds_depth = p->site_lds_depth;
-    S.spill = spill ? (double*)((char*)ws + p->ws_spill) : nullptr;
-    S.persistent = (p->site_persistent || p->site_mixed) ? 1 : 0;
-    S.first_round = p->site_waves;
-    S.mixed_few_waves = p->mixed_few_waves; S.mixed_switch_cols = p->mixed_switch_cols;
-    S.tail_order = (p->site_persistent && !p->site_mixed && p->site_tail_order) ? 1 : 0;
-    S.first_fraction = (p->site_first_fraction > 0.0) ? p->site_first_fraction : 1.0 / (double)p->site_grid_mult;
-    S.share_work = p->site_share_work;
-    S.main_shares = (p->site_reserve_q > 0) ? p->site_waves : p->site_waves * p->site_grid_mult;
-    S.work_wprefix = (const int64_t*)((char*)ws + p->ws_work_wprefix); S.part_prefix = (const int64_t*)((char*)ws + p->ws_part_prefix);
-    S.part_start = (const int64_t*)((char*)ws + p->ws_part_start);
+    const bool spill = p->site.lds_depth < p->prog.stack_depth;
+    S.lds_depth = p->site.lds_depth;
+    S.spill = spill ? (double*)((char*)ws + p->ws.spill) : nullptr;
+    S.persistent = (p->site.persistent || p->site.mixed) ? 1 : 0;
+    S.first_round = p->site.waves;
+    S.mixed_few_waves = p->site.mixed_few_waves; S.mixed_switch_cols = p->site.mixed_switch_cols;
+    S.tail_order = (p->site.persistent && !p->site.mixed && p->site.tail_order) ? 1 : 0;
+    S.first_fraction = (p->site.first_fraction > 0.0) ? p->site.first_fraction : 1.0 / (double)p->site.grid_mult;
+    S.share_work = p->site.share_work;
+    S.main_shares = (p->site.reserve_q > 0) ? p->site.waves : p->site.waves * p->site.grid_mult;
+    S.work_wprefix = (const int64_t*)((char*)ws + p->ws.work_wprefix); S.part_prefix = (const int64_t*)((char*)ws + p->ws.part_prefix);
+    S.part_start = (const int64_t*)((char*)ws + p->ws.part_start);
     S.ncat = p->ncat; S.cat = p->d_cat.p;
     // profiling brackets exactly the dominant kernel, so the figure matches rocprofv3's per-kernel average
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 0], st));
     if (p->n_site_chunks > 0) {
-        const bool mixed = p->site_mixed;
-        const dim3 grid((unsigned)(mixed ? p->site_waves : p->site_persistent ? p->site_waves * p->site_grid_mult : p->n_site_chunks));
+        const bool mixed = p->site.mixed;
+        const dim3 grid((unsigned)site_grid(p->site, p->n_site_chunks));
         // the packed tip states are read with the fused-cherry stream (tree_program.hpp)
         S.ops = p->d_fused_ops.p;
         S.nops = (int32_t)p->prog.fused_ops.size();
         // variants: packed words in registers (<= 16 / <= 64 tips); streamed one word ahead (more than 64 tips)
-        const size_t lds_full = (kSiteLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
         const int variant = p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : (spill ? kStreamWordsSpill : kStreamWords);
         if (mixed) {   // equal shares: first_round = grid
-            const size_t lds_mixed = (kMixedLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
             S.first_fraction = 1.0;
-            HIP_TRY(launch_site_rate_kernel(kMixedVariant + variant, p->model, grid, lds_mixed, st, S));
-        } else
-        HIP_TRY(launch_site_rate_kernel(variant, p->model, grid, spill ? lds : lds_full, st, S));
+            HIP_TRY(launch_site_rate_kernel(kMixedVariant + variant, p->model, grid, mixed_lds_bytes(p->prog.stack_depth), st, S));
+        } else   // (lds_depth = the stack depth unless the SPILL variant runs)
+            HIP_TRY(launch_site_rate_kernel(variant, p->model, grid, site_lds_bytes(p->site.lds_depth), st, S));
     }
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 1], st));
     if (dedup) dedup_scatter_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
@@ -936,7 +815,7 @@ int tphip_run_dev(tphip_plan* p, const uint8_t* d_states, double* d_rate, double
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
     if (!d_states || !d_rate || !d_subst || !d_lnl || !d_flag || !d_nres || !d_tables || !ws)
         return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ws_bytes < p->ws_total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
+    if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     int slot = take_slot(p);
@@ -950,7 +829,7 @@ int tphip_site_rates_dev(tphip_plan* p, const uint8_t* d_states, double* d_rate,
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
     if (!d_states || !d_rate || !d_subst || !d_lnl || !d_flag || !d_nres || !ws)
         return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ws_bytes < p->ws_total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
+    if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
     HIP_TRY(hipSetDevice(p->device));
     int slot = take_slot(p);
     int rc = launch_site_rates(p, d_states, d_rate, d_subst, d_lnl, d_flag, d_nres, ws, (hipStream_t)stream, slot);
@@ -965,7 +844,7 @@ int tphip_pi_tables_dev(tphip_plan* p, const double* d_rates, const int32_t* d_n
                         size_t ws_bytes, void* stream) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
     if (!d_rates || !d_tables || !ws) return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ws_bytes < p->ws_total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
+    if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
     HIP_TRY(hipSetDevice(p->device));
     int slot = take_slot(p);
     if (slot >= 0) {
@@ -982,7 +861,7 @@ static PiParams pi_params(const tphip_plan* p, const double* d_rates, const int3
     Q.T = p->T; Q.intervals = p->d_intervals.p; Q.n_i = p->n_i; Q.integ_mode = p->integ_mode;
     Q.correction = p->correction; Q.threshold = p->threshold;
     Q.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
-    Q.partial = ws ? (double*)((char*)ws + p->ws_partial) : nullptr;
+    Q.partial = ws ? (double*)((char*)ws + p->ws.partial) : nullptr;
     return Q;
 }
 
@@ -1342,7 +1221,7 @@ static int host_enqueue(tphip_plan* p, const uint8_t* states, size_t spitch, hip
                  o_nres = o_lnl + align_up(8 * n, 256), o_flag = o_nres + align_up(4 * n, 256);
     int rc = grow((void**)&B.percol, B.percol_bytes, o_flag + align_up(n, 256));
     if (rc) return rc;
-    rc = grow(&B.ws, B.ws_bytes, p->ws_total);
+    rc = grow(&B.ws, B.ws_bytes, p->ws.total);
     if (rc) return rc;
     double* d_rate = (double*)(B.percol + o_rate);
     double* d_subst = (double*)(B.percol + o_subst);
@@ -1522,13 +1401,13 @@ int tphip_eval_columns_dev(tphip_plan* p, const uint8_t* d_s, const double* d_u,
     E.S.states = d_s; E.S.ncols_total = p->ncols; E.S.models = p->d_models.p; E.S.ops = p->d_ops.p;
     E.S.nops = (int32_t)p->prog.ops.size(); E.S.stack_depth = p->prog.stack_depth; E.S.chrono_length = p->prog.chrono_length;
     E.S.locus_offsets = p->d_offsets.p; E.S.chunk_locus = p->d_site_chunk_locus.p; E.S.chunk_index = p->d_site_chunk_index.p;
-    E.S.chunk_cols = p->site_chunk_cols;
+    E.S.chunk_cols = p->site.chunk_cols;
     E.S.packed = nullptr; E.S.nwords = 0;
     E.S.work_cols = nullptr; E.S.work_cols2 = nullptr; E.S.work_count = nullptr; E.S.work_prefix = nullptr; E.S.nloci = p->nloci; E.S.persistent = 0; E.S.first_round = 0; E.S.mixed_few_waves = 0; E.S.mixed_switch_cols = 0; E.S.first_fraction = 1.0; E.S.ncat = p->ncat; E.S.cat = p->d_cat.p; E.S.rate = nullptr; E.S.subst = nullptr; E.S.lnl = nullptr;
     E.S.flag = nullptr; E.S.eval_counter = nullptr; E.S.spill = nullptr; E.S.lds_depth = p->prog.stack_depth;
     E.u = d_u; E.f = d_f; E.g = d_g; E.h = d_h;
-    const size_t lds = (kSiteLdsHeader + (size_t)p->prog.stack_depth * 12 * kSiteBlock) * sizeof(double);
-    if (p->n_site_chunks > 0) HIP_TRY(launch_eval_columns_kernel(p->model, dim3((unsigned)p->n_site_chunks), lds, (hipStream_t)stream, E));
+    if (p->n_site_chunks > 0)
+        HIP_TRY(launch_eval_columns_kernel(p->model, dim3((unsigned)p->n_site_chunks), site_lds_bytes(p->prog.stack_depth), (hipStream_t)stream, E));
     return TPHIP_OK;
 }
 
@@ -1591,20 +1470,13 @@ int tphip_plan_set_models(tphip_plan* p, const double* pi, const double* exch) {
     if (p->model == TPHIP_MODEL_F81 && exch)
         return fail(TPHIP_ERR_INVALID, "exch must be NULL on a TPHIP_MODEL_F81 plan (its exchangeabilities are all 1)");
     if (pi) {
-        for (size_t l = 0; l < L; ++l) {
-            int npos = 0;
-            for (int k = 0; k < 4; ++k) {
-                if (!(pi[l * 4 + k] >= 0.0) || !std::isfinite(pi[l * 4 + k]))
-                    return fail(TPHIP_ERR_INVALID, "base frequencies of locus " + std::to_string(l) + " must be finite and >= 0");
-                npos += pi[l * 4 + k] > 0.0;
-            }
-            if (npos < 2) return fail(TPHIP_ERR_INVALID, "locus " + std::to_string(l) + " has fewer than two bases with a positive frequency");
-        }
+        for (int64_t l = 0; l < p->nloci; ++l)
+            if (const int rc = check_locus_model(pi, nullptr, l)) return rc;
         p->saved->pi.assign(pi, pi + 4 * L);
     }
     if (exch) {
-        for (size_t i = 0; i < 6 * L; ++i)
-            if (!(exch[i] >= 0.0)) return fail(TPHIP_ERR_INVALID, "exchangeabilities must be >= 0");
+        for (int64_t l = 0; l < p->nloci; ++l)
+            if (const int rc = check_locus_model(nullptr, exch, l)) return rc;
         p->saved->exch.assign(exch, exch + 6 * L);
     }
     p->saved->d.pi = p->saved->pi.data();
@@ -1619,11 +1491,7 @@ int tphip_plan_set_models(tphip_plan* p, const double* pi, const double* exch) {
     }
     p->saved->d.exch = p->saved->exch.data();
     std::vector<double> hpi(p->saved->pi);
-    for (size_t l = 0; l < L; ++l) {   // same floor as at plan creation
-        double sum = 0;
-        for (int k = 0; k < 4; ++k) sum += hpi[4 * l + k];
-        for (int k = 0; k < 4; ++k) hpi[4 * l + k] = std::max(hpi[4 * l + k], kPiFloor * sum);
-    }
+    floor_pi(&hpi);   // as at plan creation
     Scratch S;
     double* d_pi = S.get<double>(4 * L);
     double* d_ex = S.get<double>(6 * L);

@@ -12,6 +12,7 @@
 #include "locus_lik_params.hpp"
 #include "locus_value_params.hpp"
 #include "locus_grad2_params.hpp"
+#include "site_launch_plan.hpp"
 #include "site_rate_params.hpp"
 #include "tphip.h"
 #include "tree_program.hpp"
@@ -86,12 +87,11 @@ struct tphip_plan {
     int32_t device = 0;
     int32_t ntaxa = 0;
     int64_t nloci = 0, ncols = 0;
-    int32_t T = 0, n_t = 0, n_i = 0, integ_mode = 0, threshold = 0, round_decimals = -1, start_rule = 0;
+    int32_t T = 0, n_t = 0, n_i = 0, integ_mode = 0, threshold = 0, round_decimals = -1;
     double correction = 1.0;
     TreeProgram prog;
     std::vector<int64_t> h_offsets;
     int64_t n_site_chunks = 0, n_pi_chunks = 0;
-    int32_t site_chunk_cols = kSiteBlock;  // columns per site_rate_kernel work slice (multiple of 64)
     DevBuf<TreeOp> d_ops, d_fused_ops;
     DevBuf<LocusModel> d_models;
     DevBuf<int64_t> d_offsets, d_locus_pichunk_offsets;
@@ -147,29 +147,12 @@ struct tphip_plan {
     int32_t nwords = 0;
     DevBuf<int32_t> d_site_chunk_locus, d_site_chunk_index, d_pi_chunk_locus, d_pi_chunk_index, d_times, d_intervals;
     DevBuf<unsigned long long> d_evals;
-    // workspace layout (bytes)
-    size_t ws_work_cols2 = 0, ws_work_cols = 0, ws_work_count = 0, ws_work_prefix = 0, ws_slice_prefix = 0, ws_partial = 0, ws_packed = 0, ws_total = 0;
-    size_t ws_hash = 0, ws_dup_of = 0, ws_tab_key = 0, ws_tab_val = 0, ws_dedup_on = 0;   // site-pattern de-duplication
-    int32_t dedup_mode = 0;   // DEDUP_AUTO (pattern_kernels.hpp)
+    // how the site-rate stage runs and where its regions lie in the caller's workspace: decided once, at plan creation
+    // (site_launch_plan.hpp: decide_site_launch, layout_workspace)
+    SiteLaunch site;
+    WorkspaceLayout ws;
     int32_t model = 0;        // TPHIP_MODEL_GTR / TPHIP_MODEL_F81 (tphip_plan_desc.model): the site-rate kernels' messages
     int32_t num_cus = 256;
-    int32_t site_waves = 0;  // persistent grid of site_rate_kernel = resident waves on the device
-    int32_t site_persistent = 1;
-    int32_t mixed_few_waves = 0;   // mixed-loci mode: workgroups that take shares when the work list is short (SiteParams)
-    int64_t mixed_switch_cols = 0;
-    int32_t site_mixed = 0;        // small batches: waves carry columns of several loci (site_rate_kernel<NW, false, true>)
-    int32_t site_grid_mult = 1;   // persistent grid = resident waves x this (see plan creation)
-    int32_t site_lds_depth = 0;   // parked partials kept in LDS by site_rate_kernel (< stack depth: SPILL variant)
-    size_t ws_spill = 0;
-    double site_first_fraction = 0.0;   // share of the work the first round of shares takes (0 = equal shares)
-    int32_t site_tail_order = 1;  // persistent mode: slow columns first in the last 128 entries of every segment (SiteParams::tail_order)
-    // persistent mode, one locus at a time: shares by predicted work (SiteParams::share_work).  reserve_q / 2^16 of every locus'
-    // easy columns go to a reserved tail that the later, small shares cut into equal column counts; the first round's shares
-    // cut the rest into equal predicted work, a slow column weighing w_slow / 2^10 evaluations and an easy one w_easy / 2^10
-    int32_t site_share_work = 0, site_reserve_q = 0, site_w_slow = 0, site_w_easy = 0;
-    size_t ws_work_class = 0, ws_work_wprefix = 0, ws_part_prefix = 0, ws_part_start = 0;
-    int32_t compact_chunked = 0;   // long loci: the work list by the chunk-parallel count / scan / scatter kernels (pi_kernels.hpp)
-    size_t ws_chunk_cnt = 0;
     // profiling
     bool profile = false;
     std::vector<hipEvent_t> ev;  // 4 events per slot: site start/stop, pi start/stop

@@ -133,7 +133,7 @@ def test_fullsize_properties(workload, oracle):
 
 def test_deep_tree_spilled_stack_is_bit_identical(monkeypatch):
     """256 taxa: the persistent site-rate kernel keeps three parked partials in LDS and the fourth in a global scratch
-    row per wave (8 resident waves per CU instead of 6; tphip.hip plan creation).  Same bits as with the whole stack in
+    row per wave (8 resident waves per CU instead of 6; decide_site_launch, site_launch_plan.hpp).  Same bits as with the whole stack in
     LDS, on an eighth of C5 (2.5 M columns: the persistent grid, so the spill variant is the one that runs)."""
     import torch
     from tapir_amd import engine, synth
