@@ -10,6 +10,8 @@
 //     [net PI(t=0..T-1) | PI at --times | sum(integral) per interval | sum(error) per interval].
 //     Summation order is fixed (1024-column blocks, lane-strided, then block order) so a locus gives the
 //     same bits no matter how many GPUs the batch is sharded over.
+// pi_net_kernel + pi_interval_kernel
+//     pi_partial_kernel's two jobs as two kernels, for plans with long loci (SiteLaunch::pi_split); the same sums, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -748,6 +750,201 @@ __global__ __launch_bounds__(kPiBlock) void pi_partial_kernel(PiParams P) {
         }
         __syncthreads();
         if (threadIdx.x < 2 * kIvTile && k0 + (int)(threadIdx.x >> 1) < P.n_i) {
+            const int kk = threadIdx.x >> 1, which = threadIdx.x & 1;
+            out[P.T + which * P.n_i + k0 + kk] =
+                ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+        }
+        __syncthreads();
+    }
+}
+
+// ---- pi_partial_kernel as two kernels, for long loci (SiteLaunch::pi_split).  Its two jobs want opposite things: the time
+// tiles ~100 VGPRs and many waves, the interval integrals every register they can get.  Fused, the integrals pin the whole
+// kernel at 255 VGPRs and 2 waves per SIMD.  pi_net_kernel writes out[0 .. T), pi_interval_kernel out[T .. T + 2 n_i); each
+// packs the chunk as pi_partial_kernel does and adds in pi_partial_kernel's order, so `partial` holds the same bits.
+
+// The chunk's rates as the PI sums see them, the contributing ones packed to the front in thread-major order (see
+// pi_partial_kernel): r[j] / ok[j] is the thread's packed slot j * kPiBlock + threadIdx.x.  `packed_rate`: kPiChunk doubles
+// of LDS, the caller's, read here after the last barrier: a caller that writes them again puts a barrier in front.
+__device__ __forceinline__ void pi_pack_chunk(const PiParams& P, int64_t base, int64_t hi, double* packed_rate, double* r, bool* ok) {
+    __shared__ int wave_count[kPiBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < kPiColsPerThread; ++j) {
+        const int64_t col = base + j * kPiBlock + threadIdx.x;
+        r[j] = (col < hi) ? finalize_rate(P, col) : __longlong_as_double(0x7ff8000000000000ll);
+        ok[j] = isfinite(r[j]) && r[j] != 0.0;
+    }
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < kPiColsPerThread; ++j) c += ok[j] ? 1 : 0;
+    int inc = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) wave_count[wave] = inc;
+    __syncthreads();
+    int pos = inc - c, total = 0;
+#pragma unroll
+    for (int w = 0; w < kPiBlock / 64; ++w) { pos += (w < wave) ? wave_count[w] : 0; total += wave_count[w]; }
+#pragma unroll
+    for (int j = 0; j < kPiColsPerThread; ++j) if (ok[j]) packed_rate[pos++] = r[j];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kPiColsPerThread; ++j) {
+        const int idx = j * kPiBlock + (int)threadIdx.x;
+        ok[j] = idx < total;
+        r[j] = ok[j] ? packed_rate[idx] : __longlong_as_double(0x7ff8000000000000ll);
+    }
+}
+
+// The net-PI time tiles of pi_partial_kernel.  The tile's sixteen times are converted to double once per tile, not once per
+// column (the same conversion: the same bits).  The rates are packed through the transpose buffer: 34 KB of LDS and 128
+// VGPRs, four workgroups per CU, one wave of each per SIMD.
+__global__ __launch_bounds__(kPiBlock, 4) void pi_net_kernel(PiParams P) {
+    __shared__ double tile[kTimeTile][16 * 17];
+    static_assert(kTimeTile * 16 * 17 >= kPiChunk, "the transpose buffer holds a chunk's packed rates");
+    const int chunk = blockIdx.x;
+    const int locus = P.chunk_locus[chunk];
+    const int64_t lo = P.locus_offsets[locus], hi = P.locus_offsets[locus + 1];
+    const int64_t base = lo + (int64_t)P.chunk_index[chunk] * kPiChunk;
+    double r[kPiColsPerThread];
+    bool ok[kPiColsPerThread];
+    pi_pack_chunk(P, base, hi, &tile[0][0], r, ok);
+    __syncthreads();
+    double* out = P.partial + (size_t)chunk * (P.T + 2 * P.n_i);
+    for (int t0 = 0; t0 < P.T; t0 += kTimeTile) {
+        double acc[kTimeTile], t[kTimeTile];
+#pragma unroll
+        for (int i = 0; i < kTimeTile; ++i) { acc[i] = 0.0; t[i] = (double)(t0 + i); }
+#pragma unroll
+        for (int j = 0; j < kPiColsPerThread; ++j) {
+            if (!ok[j]) continue;
+            const double c = 16.0 * (r[j] * r[j]);
+            const double q = exp(-(4.0 * r[j]));
+            double p = exp(-(4.0 * r[j] * (double)t0));
+#pragma unroll
+            for (int i = 0; i < kTimeTile; ++i) {
+                acc[i] = fma(c * t[i], p, acc[i]);
+                p *= q;
+            }
+        }
+        // (the transpose-and-add of pi_partial_kernel)
+        {
+            const int slot = (threadIdx.x >> 4) * 17 + (threadIdx.x & 15);
+#pragma unroll
+            for (int i = 0; i < kTimeTile; ++i) tile[i][slot] = acc[i];
+        }
+        __syncthreads();
+        {
+            const int i = threadIdx.x >> 4, seg = threadIdx.x & 15;
+            const double* src = &tile[i][seg * 17];
+            double sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) sum += src[k];
+            sum += __shfl_xor(sum, 8);
+            sum += __shfl_xor(sum, 4);
+            sum += __shfl_xor(sum, 2);
+            sum += __shfl_xor(sum, 1);
+            if (seg == 0 && t0 + i < P.T) out[t0 + i] = sum;
+        }
+        __syncthreads();
+    }
+}
+
+// The generic first panel (4 r hl >= 30: a few hundred columns in millions) out of line, so that its 21 exponentials and
+// the call into dqagse_adaptive cost the factored path no registers.
+struct QuadResult { double result, abserr; };
+__device__ __noinline__ QuadResult quad_townsend_generic(double a, double b, double rate) {
+    QuadResult o;
+    o.abserr = 0.0;
+    quad_townsend<false>(a, b, rate, nullptr, o.result, o.abserr);
+    return o;
+}
+
+// The interval integrals of pi_partial_kernel in register tiles of kIvSplitTile intervals:
+//   * only the factored panel is inline: the generic panel and the adaptive bisection are calls behind branches that almost
+//     no wave takes;
+//   * a column's rate is read from the packed list when its turn comes, its slots are the thread's first n_ok;
+//   * what a panel derives from the interval's bounds alone is derived per column, where it is used (below).
+// 234 VGPRs, two waves per SIMD.  A build for three (168 VGPRs: the twenty factors of a column in LDS instead of registers) was
+// measured and is slower by what the LDS traffic costs: the kernel's time is its vector instructions.
+// Per (thread, interval) the columns are added in the order j = 0..3, then lanes, then waves, as in pi_partial_kernel.
+constexpr int kIvSplitTile = 4;
+__global__ __launch_bounds__(kPiBlock, 2) void pi_interval_kernel(PiParams P) {
+    __shared__ double red[2 * kIvSplitTile][4];
+    __shared__ double packed_rate[kPiChunk];
+    const int chunk = blockIdx.x;
+    const int locus = P.chunk_locus[chunk];
+    const int64_t lo = P.locus_offsets[locus], hi = P.locus_offsets[locus + 1];
+    const int64_t base = lo + (int64_t)P.chunk_index[chunk] * kPiChunk;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int n_ok = 0;   // the thread's contributing slots are its first n_ok: slot j is the packed index j * kPiBlock + threadIdx.x
+    {
+        double r[kPiColsPerThread];
+        bool ok[kPiColsPerThread];
+        pi_pack_chunk(P, base, hi, packed_rate, r, ok);
+#pragma unroll
+        for (int j = 0; j < kPiColsPerThread; ++j) n_ok += ok[j] ? 1 : 0;
+    }
+    double* out = P.partial + (size_t)chunk * (P.T + 2 * P.n_i);
+    for (int k0 = 0; k0 < P.n_i; k0 += kIvSplitTile) {
+        int a[kIvSplitTile], b[kIvSplitTile];   // wave-uniform; entries past n_i repeat the last interval and are not used
+#pragma unroll
+        for (int kk = 0; kk < kIvSplitTile; ++kk) {
+            const int k = (k0 + kk < P.n_i) ? k0 + kk : P.n_i - 1;
+            a[kk] = __builtin_amdgcn_readfirstlane(P.intervals[2 * k]);
+            b[kk] = __builtin_amdgcn_readfirstlane(P.intervals[2 * k + 1]);
+        }
+        double si[kIvSplitTile], se[kIvSplitTile];
+#pragma unroll
+        for (int kk = 0; kk < kIvSplitTile; ++kk) { si[kk] = 0.0; se[kk] = 0.0; }
+#pragma unroll 1
+        for (int j = 0; j < n_ok; ++j) {
+            const double rj = packed_rate[j * kPiBlock + (int)threadIdx.x];
+            GkFactors F;
+            double have_h = -1.0;        // half-length the factors in F were built for
+#pragma unroll
+            for (int kk = 0; kk < kIvSplitTile; ++kk) {
+                if (k0 + kk < P.n_i) {   // wave-uniform
+                    // The bounds are the same for every column, and so is all that a panel derives from them alone: the
+                    // bounds as doubles, centre, half-length, the 21 abscissae.  Hoisted out of the column loop those are
+                    // 44 live doubles per interval of the tile, next to the column's own values.  The empty asm makes the
+                    // bounds (two SGPRs) this column's own, so that all of it is derived again where it is used (the
+                    // arithmetic the panel is written with).
+                    int ai = a[kk], bi = b[kk];
+                    asm volatile("" : "+s"(ai), "+s"(bi));
+                    const double aj = (double)ai, bj = (double)bi;
+                    double res, err = 0.0;
+                    if (P.integ_mode == TPHIP_INTEG_QUADPACK) {
+                        const double hl = 0.5 * (bj - aj);
+                        if (4.0 * rj * hl < 30.0) {          // per lane: a huge rate takes the generic panel
+                            if (hl != have_h) { gk_factors(rj, hl, F); have_h = hl; }
+                            quad_townsend_factored(aj, bj, rj, F, res, err);
+                        } else {
+                            const QuadResult g = quad_townsend_generic(aj, bj, rj);
+                            res = g.result;
+                            err = g.abserr;
+                        }
+                    } else {
+                        res = integral_closed(aj, bj, rj);
+                    }
+                    si[kk] += res;
+                    se[kk] += err;
+                }
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < kIvSplitTile; ++kk) {
+            if (k0 + kk < P.n_i) {
+                const double s1 = wave_sum(si[kk]), s2 = wave_sum(se[kk]);
+                if (lane == 0) { red[2 * kk][wave] = s1; red[2 * kk + 1][wave] = s2; }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < 2 * kIvSplitTile && k0 + (int)(threadIdx.x >> 1) < P.n_i) {
             const int kk = threadIdx.x >> 1, which = threadIdx.x & 1;
             out[P.T + which * P.n_i + k0 + kk] =
                 ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];

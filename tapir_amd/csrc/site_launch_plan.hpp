@@ -28,7 +28,7 @@ inline size_t mixed_lds_bytes(int depth) { return (kMixedLdsHeader + (size_t)dep
 // their text (each has its own reading of it, below), numbers what atol / atof / atoi made of it.
 struct PlanKnobs {
     std::optional<long> site_chunk, site_waves, site_grid_mult;
-    std::optional<char> site_spill, site_persistent, site_mixed, site_tail_order, site_share_work, compact_chunked, dedup;
+    std::optional<char> site_spill, site_persistent, site_mixed, site_tail_order, site_share_work, compact_chunked, pi_split, dedup;
     std::optional<double> site_first_fraction, site_reserve;
     std::optional<std::pair<double, double>> site_class_weights;   // "slow,easy"; text that does not parse = not set
     std::optional<int> host_split;
@@ -37,7 +37,7 @@ struct PlanKnobs {
 constexpr const char* kPlanKnobNames[] = {
     "TPHIP_SITE_CHUNK", "TPHIP_SITE_SPILL", "TPHIP_SITE_PERSISTENT", "TPHIP_SITE_MIXED", "TPHIP_SITE_WAVES",
     "TPHIP_SITE_FIRST_FRACTION", "TPHIP_SITE_GRID_MULT", "TPHIP_SITE_TAIL_ORDER", "TPHIP_SITE_SHARE_WORK", "TPHIP_SITE_RESERVE",
-    "TPHIP_SITE_CLASS_WEIGHTS", "TPHIP_COMPACT_CHUNKED", "TPHIP_DEDUP", "TPHIP_HOST_SPLIT"};
+    "TPHIP_SITE_CLASS_WEIGHTS", "TPHIP_COMPACT_CHUNKED", "TPHIP_PI_SPLIT", "TPHIP_DEDUP", "TPHIP_HOST_SPLIT"};
 
 // One knob from its text (an environment variable's value).  False: no knob of that name.
 inline bool set_plan_knob(PlanKnobs* k, const char* name, const char* text) {
@@ -57,6 +57,7 @@ inline bool set_plan_knob(PlanKnobs* k, const char* name, const char* text) {
         if (sscanf(text, "%lf,%lf", &a, &b) == 2) k->site_class_weights = std::make_pair(a, b);
     }
     else if (is("TPHIP_COMPACT_CHUNKED")) k->compact_chunked = text[0];
+    else if (is("TPHIP_PI_SPLIT")) k->pi_split = text[0];
     else if (is("TPHIP_DEDUP")) k->dedup = text[0];
     else if (is("TPHIP_HOST_SPLIT")) k->host_split = atoi(text);
     else return false;
@@ -95,6 +96,7 @@ struct SiteLaunch {
     // cut the rest into equal predicted work, a slow column weighing w_slow / 2^10 evaluations and an easy one w_easy / 2^10
     int32_t share_work = 0, reserve_q = 0, w_slow = 0, w_easy = 0;
     int32_t compact_chunked = 0;   // long loci: the work list by the chunk-parallel count / scan / scatter kernels (pi_kernels.hpp)
+    int32_t pi_split = 0;          // long loci: the PI partial sums by pi_net_kernel + pi_interval_kernel instead of pi_partial_kernel
 };
 
 // Workgroups of the site-rate launch
@@ -232,6 +234,12 @@ SiteLaunch decide_site_launch(const SiteShape& shape, int num_cus, const PlanKno
     // A/B and test switch that forces either path on any shape.
     s.compact_chunked = shape.max_locus_cols > 2048 ? 1 : 0;
     if (knobs.compact_chunked) s.compact_chunked = (*knobs.compact_chunked != '0');
+    // Long loci take the PI partial sums in two kernels, the net-PI time tiles and the interval integrals (pi_kernels.hpp): each
+    // at its own register count, for a second pass over the rates and the cull.  That pass costs short loci more than the split
+    // gives them (C2 +6 us, R1 +24 us: DESIGN section 8, r12), so the switch is the chunked compaction's.  The sums are the
+    // same to the bit either way; TPHIP_PI_SPLIT=0/1 is the A/B and test switch that forces either path on any shape.
+    s.pi_split = shape.max_locus_cols > 2048 ? 1 : 0;
+    if (knobs.pi_split) s.pi_split = (*knobs.pi_split != '0');
     s.dedup_mode = shape.pattern_dedup;
     if (knobs.dedup)   // test/tuning knob: 0 = never, 1 = always, anything else = automatic
         s.dedup_mode = (*knobs.dedup == '0') ? DEDUP_OFF : (*knobs.dedup == '1') ? DEDUP_ON : DEDUP_AUTO;

@@ -794,7 +794,15 @@ static int launch_pi_tables(tphip_plan* p, const double* d_rates, const int32_t*
                             hipStream_t st, int slot) {
     PiParams Q = pi_params(p, d_rates, d_nres, ws);
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 2], st));
-    if (p->n_pi_chunks > 0) pi_partial_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(kPiBlock), 0, st>>>(Q);
+    if (p->n_pi_chunks > 0) {
+        const dim3 grid((unsigned)p->n_pi_chunks), block(kPiBlock);
+        if (p->site.pi_split) {   // between them the two kernels write every entry of `partial`
+            pi_net_kernel<<<grid, block, 0, st>>>(Q);
+            if (p->n_i > 0) pi_interval_kernel<<<grid, block, 0, st>>>(Q);
+        } else {
+            pi_partial_kernel<<<grid, block, 0, st>>>(Q);
+        }
+    }
     pi_reduce_kernel<<<dim3((unsigned)p->nloci), dim3(kPiReduceBlock), 0, st>>>(Q.partial, p->d_locus_pichunk_offsets.p, p->T,
                                                                    p->d_times.p, p->n_t, p->n_i, d_tables);
     if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 3], st));
