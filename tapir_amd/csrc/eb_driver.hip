@@ -179,12 +179,8 @@ int eb_setup(tphip_plan* p, const uint8_t* d_states, const tphip_eb_opts* o, con
     const size_t n = (size_t)p->ncols, L = (size_t)p->nloci, K = (size_t)o->ncat;
     const size_t nw = (size_t)(p->nwords > 0 ? p->nwords : 1);
     const size_t need = eb_layout(nullptr, n, L, K, nw, W);
-    if (p->eb_ws_bytes < need) {
-        if (p->d_eb_ws) { HIP_TRY(hipFree(p->d_eb_ws)); p->d_eb_ws = nullptr; p->eb_ws_bytes = 0; }
-        HIP_TRY(hipMalloc(&p->d_eb_ws, need));
-        p->eb_ws_bytes = need;
-    }
-    eb_layout(p->d_eb_ws, n, L, K, nw, W);
+    if (const int rc = p->eb_ws.reserve(need)) return rc;
+    eb_layout(p->eb_ws.p, n, L, K, nw, W);
     EbPrep& B = W.prep;
     PosteriorParams& E = W.E;
 
@@ -307,12 +303,8 @@ int tphip_eb_start_scale_dev(tphip_plan* p, const uint8_t* d_states, double* sca
     EbWorkspace W;
     const size_t nw = (size_t)(p->nwords > 0 ? p->nwords : 1);
     const size_t need = eb_layout(nullptr, (size_t)p->ncols, L, 2, nw, W);
-    if (p->eb_ws_bytes < need) {
-        if (p->d_eb_ws) { HIP_TRY(hipFree(p->d_eb_ws)); p->d_eb_ws = nullptr; p->eb_ws_bytes = 0; }
-        HIP_TRY(hipMalloc(&p->d_eb_ws, need));
-        p->eb_ws_bytes = need;
-    }
-    eb_layout(p->d_eb_ws, (size_t)p->ncols, L, 2, nw, W);
+    if (const int rc = p->eb_ws.reserve(need)) return rc;
+    eb_layout(p->eb_ws.p, (size_t)p->ncols, L, 2, nw, W);
     if (p->n_pi_chunks <= 0) {   // no column at all
         for (size_t l = 0; l < L; ++l) scale[l] = 1.0 / p->prog.chrono_length;
         return TPHIP_OK;

@@ -1,6 +1,8 @@
-// launch_constants.hpp -- the constants that the kernels and the host's launch decisions (site_launch_plan.hpp) share.
-// No HIP header: site_launch_plan.hpp and its test program compile with a plain C++ compiler.
+// launch_constants.hpp -- the constants that the kernels and the host's launch decisions (site_launch_plan.hpp,
+// locus_launch_plan.hpp) share.
+// No HIP header: the two decision headers and their test programs compile with a plain C++ compiler.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace tphip {
@@ -19,6 +21,23 @@ constexpr int kSiteLdsHeader = 160;  // doubles of LDS before the stack: tip tab
 constexpr int kStreamWords = -1;   // NW value of the streamed-words path
 constexpr int kStreamWordsSpill = -2;   // launcher variant: streamed words + SPILL
 constexpr int kMixedVariant = 100;   // launcher variants 102 / 108: packed words in registers, mixed-loci mode
+
+// ---- stage-1 likelihood and gradient kernels (locus_*_kernel.hpp; launch decisions: locus_launch_plan.hpp) ----
+#ifndef TPHIP_LIK_BLOCK
+#define TPHIP_LIK_BLOCK 128   // threads per workgroup of the locus likelihood kernels (a build-time knob for A/B runs)
+#endif
+constexpr int kLikBlock = TPHIP_LIK_BLOCK;
+constexpr int kGradBlock = 128;
+constexpr int kGradWaves = kGradBlock / 64;
+constexpr int kGradEF = 12;     // per node: e^{lam_k t}[4], F01 F02 F03 F12 F13 F23, t, pad
+constexpr int kGradSlots = 4;   // LDS accumulator addresses per (wave, branch); fewer (GradParams.nslots) on big trees
+constexpr size_t kValueWorkspaceBytes = (size_t)1 << 30;
+constexpr int kValueTipRow = 20;     // doubles per taxon in the LDS tip table: 4 rows of P^T + a row of ones
+constexpr int kValueMaxDepth = 5;   // deepest register stack instantiated (a Sethi-Ullman-ordered tree of 2^(D+1) tips needs D)
+constexpr int kGrad2Block = 128;
+constexpr int kGrad2Waves = kGrad2Block / 64;
+constexpr int kGrad2EF = 12;        // per (candidate, node): e^{lam_k t}[4], F01 F02 F03 F12 F13 F23, t, pad
+constexpr int kGrad2MaxRDepth = 8;  // parked adjoints of the reverse sweep (LDS): log2(taxa) on a balanced tree
 
 // ---- classification and PI kernels (pi_kernels.hpp) ----
 constexpr int kPiBlock = 256;

@@ -6,15 +6,11 @@
 #include <string>
 #include <vector>
 #include "gtr_model.hpp"
+#include "launch_constants.hpp"   // kGrad2Block, kGrad2Waves, kGrad2EF, kGrad2MaxRDepth
 #include "locus_lik_common.hpp"
 #include "locus_value_params.hpp"
 
 namespace tphip {
-
-constexpr int kGrad2Block = 128;
-constexpr int kGrad2Waves = kGrad2Block / 64;
-constexpr int kGrad2EF = 12;        // per (candidate, node): e^{lam_k t}[4], F01 F02 F03 F12 F13 F23, t, pad
-constexpr int kGrad2MaxRDepth = 8;  // parked adjoints of the reverse sweep (LDS): log2(taxa) on a balanced tree
 
 // reverse-sweep record of one internal node n with children A and B (binary trees), two int4:
 //   a.x  flags (below)          a.y  node n (its tables; unused for the root)

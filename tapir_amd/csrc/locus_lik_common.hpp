@@ -3,13 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "launch_constants.hpp"   // kLikBlock (TPHIP_LIK_BLOCK)
 
 namespace tphip {
 
-#ifndef TPHIP_LIK_BLOCK
-#define TPHIP_LIK_BLOCK 128   // threads per workgroup of the locus likelihood kernels (a build-time knob for A/B runs)
-#endif
-constexpr int kLikBlock = TPHIP_LIK_BLOCK;
 // A partial is rescaled when its largest entry falls below this.  Two partials meet in a POP_MUL before the next check,
 // so the threshold must keep the PRODUCT of two just-unscaled partials above the smallest normal number (1e-308):
 // 1e-200 let a 400-taxon tree underflow to L = 0.

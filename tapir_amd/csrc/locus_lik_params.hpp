@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gtr_model.hpp"
+#include "launch_constants.hpp"
 #include "locus_lik_common.hpp"
 
 namespace tphip {
@@ -43,10 +44,7 @@ struct LikParams {
 #ifndef TPHIP_GRAD_MIN_WAVES
 #define TPHIP_GRAD_MIN_WAVES 2   // waves per SIMD the register allocation must allow (2: <= 256 VGPRs, no scratch)
 #endif
-constexpr int kGradBlock = 128;
-constexpr int kGradWaves = kGradBlock / 64;
-constexpr int kGradEF = 12;     // per node: e^{lam_k t}[4], F01 F02 F03 F12 F13 F23, t, pad
-constexpr int kGradSlots = 4;   // LDS accumulator addresses per (wave, branch); fewer (GradParams.nslots) on big trees
+// (kGradBlock, kGradWaves, kGradEF, kGradSlots: launch_constants.hpp)
 
 struct GradParams {
     LikParams L;                // candidates as for locus_loglik_kernel (cand_pidx / cand_pfac are honoured too); L.out = lnL

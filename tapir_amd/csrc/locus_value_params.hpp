@@ -5,13 +5,12 @@
 #include <cstdint>
 #include <vector>
 #include "gtr_model.hpp"
+#include "launch_constants.hpp"   // kValueWorkspaceBytes, kValueTipRow, kValueMaxDepth
 #include "tree_program.hpp"
 
 namespace tphip {
 
-constexpr size_t kValueWorkspaceBytes = (size_t)1 << 30;
 constexpr int kValueOpEnd = 0xff;   // code of the two records that close the op stream
-constexpr int kValueTipRow = 20;     // doubles per taxon in the LDS tip table: 4 rows of P^T + a row of ones
 // Tip states travel as 4-bit CODES, not masks: 0..3 = A, C, G, T (row of the tip table), 4 = gap / N (the row of ones),
 // 5..14 = the ten other IUPAC sets (slow path: the rows of the set's bits are added).  16 nibbles each:
 constexpr unsigned long long kValueCodeOfMask = 0x4EDCBA9387625104ull;   // nibble m = code of state mask m (0 and 15 -> 4)
@@ -92,8 +91,6 @@ inline bool build_value_program(const TreeProgram& prog, int32_t ntaxa, int32_t 
     vops.push_back(make_int4(kValueOpEnd, 0, 0, 0));
     return ok;
 }
-
-constexpr int kValueMaxDepth = 5;   // deepest register stack instantiated (a Sethi-Ullman-ordered tree of 2^(D+1) tips needs D)
 
 // host side of the value kernels (locus_value_launch.hip)
 hipError_t launch_locus_value_kernel(int cols, int depth, dim3 grid, size_t lds_bytes, hipStream_t st, const ValueParams& V);

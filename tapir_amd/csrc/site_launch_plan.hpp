@@ -32,12 +32,17 @@ struct PlanKnobs {
     std::optional<double> site_first_fraction, site_reserve;
     std::optional<std::pair<double, double>> site_class_weights;   // "slow,easy"; text that does not parse = not set
     std::optional<int> host_split;
+    // stage 1 (locus_launch_plan.hpp): columns per thread of locus_value_kernel, 1 or 2 (text below 2 = 1); the eigenbasis value
+    // kernel instead of it whenever the variable is set, whatever its text
+    std::optional<int> value_cols;
+    bool value_eigenbasis = false;
 };
 
 constexpr const char* kPlanKnobNames[] = {
     "TPHIP_SITE_CHUNK", "TPHIP_SITE_SPILL", "TPHIP_SITE_PERSISTENT", "TPHIP_SITE_MIXED", "TPHIP_SITE_WAVES",
     "TPHIP_SITE_FIRST_FRACTION", "TPHIP_SITE_GRID_MULT", "TPHIP_SITE_TAIL_ORDER", "TPHIP_SITE_SHARE_WORK", "TPHIP_SITE_RESERVE",
-    "TPHIP_SITE_CLASS_WEIGHTS", "TPHIP_COMPACT_CHUNKED", "TPHIP_PI_SPLIT", "TPHIP_DEDUP", "TPHIP_HOST_SPLIT"};
+    "TPHIP_SITE_CLASS_WEIGHTS", "TPHIP_COMPACT_CHUNKED", "TPHIP_PI_SPLIT", "TPHIP_DEDUP", "TPHIP_HOST_SPLIT",
+    "TPHIP_VALUE_COLS", "TPHIP_VALUE_EIGENBASIS"};
 
 // One knob from its text (an environment variable's value).  False: no knob of that name.
 inline bool set_plan_knob(PlanKnobs* k, const char* name, const char* text) {
@@ -60,6 +65,8 @@ inline bool set_plan_knob(PlanKnobs* k, const char* name, const char* text) {
     else if (is("TPHIP_PI_SPLIT")) k->pi_split = text[0];
     else if (is("TPHIP_DEDUP")) k->dedup = text[0];
     else if (is("TPHIP_HOST_SPLIT")) k->host_split = atoi(text);
+    else if (is("TPHIP_VALUE_COLS")) k->value_cols = atoi(text) >= 2 ? 2 : 1;
+    else if (is("TPHIP_VALUE_EIGENBASIS")) k->value_eigenbasis = true;
     else return false;
     return true;
 }

@@ -332,7 +332,7 @@ extern "C" int tphip_stage1_fit_dev(tphip_plan* p, const uint8_t* d_states, cons
         std::vector<int64_t> hoff((size_t)L + 1);
         uint32_t* d_packed = nullptr;
         hipError_t e = hipMemcpy(hoff.data(), d_poff, sizeof(int64_t) * ((size_t)L + 1), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && p->value_cols > 0 && npat > 0) {
+        if (e == hipSuccess && p->locus.value_cols > 0 && npat > 0) {
             e = hipMalloc((void**)&d_packed, sizeof(uint32_t) * (size_t)p->nwords * (size_t)npat);
             if (e == hipSuccess) e = launch_value_pack_codes_kernel(st, d_pat, npat, p->d_tip_taxon.p, p->nwords, d_packed);
         }

@@ -1,5 +1,6 @@
 // tphip.hip -- C ABI (include/tphip.h) over the gfx950 kernels.  Host side only does validation, the
 // one-off tree compilation, table uploads and kernel launches; there is no CPU compute path.
+// (The stage-1 likelihood and gradient entry points are in locus_driver.hip.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,7 +14,7 @@
 
 #include "gtr_model.hpp"
 #include "gtr_setup_kernel.hpp"
-#include "locus_lik_params.hpp"
+#include "locus_grad2_params.hpp"
 #include "locus_value_params.hpp"
 #include "pattern_kernels.hpp"
 #include <hipcub/hipcub.hpp>
@@ -45,33 +46,12 @@ int tphip_device_count(void) {
 int tphip_plan_destroy(tphip_plan* plan) {
     if (!plan) return TPHIP_OK;
     (void)hipSetDevice(plan->device);
-    plan->d_ops.release(); plan->d_fused_ops.release(); plan->d_models.release(); plan->d_offsets.release();
-    plan->d_locus_pichunk_offsets.release(); plan->d_site_chunk_locus.release(); plan->d_site_chunk_index.release();
-    plan->d_pi_chunk_locus.release(); plan->d_pi_chunk_index.release(); plan->d_times.release();
-    plan->d_intervals.release(); plan->d_evals.release(); plan->d_tip_taxon.release(); plan->d_op_node.release(); plan->d_cls_steps.release();
-    plan->d_lik_ops.release();
-    plan->d_value_ops.release();
-    plan->d_value_tip_node.release();
-    plan->d_cat.release();
     free_host_buffers(plan);
     free_parts(plan);
-    if (plan->d_tape) { (void)hipFree(plan->d_tape); plan->d_tape = nullptr; }
-    if (plan->d_value_ws) { (void)hipFree(plan->d_value_ws); plan->d_value_ws = nullptr; }
-    if (plan->d_grad_eig) { (void)hipFree(plan->d_grad_eig); plan->d_grad_eig = nullptr; }
-    if (plan->d_value_packed) { (void)hipFree(plan->d_value_packed); plan->d_value_packed = nullptr; }
-    if (plan->d_part) { (void)hipFree(plan->d_part); plan->d_part = nullptr; }
-    if (plan->d_col_weight) { (void)hipFree(plan->d_col_weight); plan->d_col_weight = nullptr; }
-    if (plan->d_eb_ws) { (void)hipFree(plan->d_eb_ws); plan->d_eb_ws = nullptr; }
-    if (plan->d_sim_nodes) { (void)hipFree(plan->d_sim_nodes); plan->d_sim_nodes = nullptr; }
-    if (plan->d_sim_ids) { (void)hipFree(plan->d_sim_ids); plan->d_sim_ids = nullptr; }
-    if (plan->d_grad_params) { (void)hipFree(plan->d_grad_params); plan->d_grad_params = nullptr; }
-    plan->d_grad2_fops.release(); plan->d_grad2_rops.release();
-    if (plan->d_grad2_ws) { (void)hipFree(plan->d_grad2_ws); plan->d_grad2_ws = nullptr; }
-    if (plan->d_grad2_params) { (void)hipFree(plan->d_grad2_params); plan->d_grad2_params = nullptr; }
-    if (plan->d_arena) { (void)hipFree(plan->d_arena); plan->d_arena = nullptr; }
-    if (plan->h_arena) { (void)hipHostFree(plan->h_arena); plan->h_arena = nullptr; }
+    // what a pattern view of stage 1 swaps stays a raw pointer (stage1_driver.hip), as do the simulation's arrays
+    for (void* q : {(void*)plan->d_col_weight, (void*)plan->d_value_packed, plan->d_sim_nodes, (void*)plan->d_sim_ids}) if (q) (void)hipFree(q);
     for (hipEvent_t e : plan->ev) (void)hipEventDestroy(e);
-    delete plan;
+    delete plan;   // its buffers free themselves, on the plan's device
     return TPHIP_OK;
 }
 
@@ -276,7 +256,7 @@ static hipError_t upload_plan(tphip_plan* p, const tphip_plan_desc* d, const std
                 p->grad2_nrops = (int32_t)(rops.size() / 2);
                 p->grad2_ntape = nslot;
                 p->grad2_rdepth = rdepth;
-                p->grad2_ok = e == hipSuccess;
+                p->grad2_built = e == hipSuccess;
             }
         }
     }
@@ -303,68 +283,7 @@ static hipError_t upload_plan(tphip_plan* p, const tphip_plan_desc* d, const std
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    d_pi.release();
-    d_exch.release();
     return e;
-}
-
-// Launch configuration of the stage-1 kernels (locus likelihood, value, gradient): LDS sizes, whether they may run at all on
-// this tree, resident blocks per CU.
-static void configure_stage1_kernels(tphip_plan* p) {
-    // locus likelihood (value) kernel: no staging of the state masks in LDS, which cost it more than it saved (measured
-    // 13.6 ms vs 10.0 ms per 1616 candidates x 20000 columns x 64 taxa)
-    p->lik_lds = ((size_t)p->nnodes * 4 + (size_t)p->prog.stack_depth * 4 * kLikBlock) * sizeof(double);
-    p->lik_ok = p->lik_lds <= 150 * 1024;
-    if (p->lik_ok && p->lik_lds > 64 * 1024)
-        p->lik_ok = locus_loglik_kernel_allow_lds(150 * 1024) == hipSuccess;
-    // value kernel on transition matrices (locus_value_kernel.hpp): C columns per thread share the op decode and the
-    // scalar loads of a branch's matrix; parked siblings live in registers (template depth), LDS holds the tip matrices
-    // and the packed state masks
-    {
-        int cols = p->max_locus_cols >= 512 ? 2 : 1;
-        if (const char* env = getenv("TPHIP_VALUE_COLS")) cols = atoi(env) >= 2 ? 2 : 1;
-        p->value_cols = 0;
-        if (p->value_nops > 0 && p->prog.stack_depth <= kValueMaxDepth && !getenv("TPHIP_VALUE_EIGENBASIS")) {
-            const size_t need = (size_t)p->ntaxa * kValueTipRow * sizeof(double) + (size_t)p->nwords * cols * kLikBlock * sizeof(uint32_t);
-            if (need <= 96 * 1024 &&
-                (need <= 64 * 1024 || locus_value_kernel_allow_lds(cols, p->prog.stack_depth, 96 * 1024) == hipSuccess)) {
-                p->value_cols = cols;
-                p->value_lds = need;
-            }
-        }
-    }
-    // gradient kernel: staging helps it (95.6 -> 91.7 ms)
-    p->grad_slots = kGradSlots;   // fewer accumulator addresses per branch when the tree would not fit otherwise
-    while (p->grad_slots > 1 && (size_t)p->nnodes * (kGradEF + 2 * kGradWaves * p->grad_slots) * sizeof(double) > 100 * 1024)
-        p->grad_slots >>= 1;
-    p->grad_lds = (size_t)p->nnodes * (kGradEF + 2 * kGradWaves * p->grad_slots) * sizeof(double);
-    const size_t grad_stage_bytes = (size_t)p->ntaxa * kGradBlock;
-    p->grad_stage = (grad_stage_bytes <= 48 * 1024 && p->grad_lds + grad_stage_bytes <= 150 * 1024) ? 1 : 0;
-    if (p->grad_stage) p->grad_lds += grad_stage_bytes;
-    p->grad_ok = p->grad_lds <= 150 * 1024;
-    if (p->grad_ok && p->grad_lds > 64 * 1024)
-        p->grad_ok = locus_grad_kernel_allow_lds(150 * 1024) == hipSuccess;
-    if (p->grad_ok) {
-        int bpc = 1;
-        if (locus_grad_kernel_occupancy(p->grad_lds, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-        // the tape of the resident blocks should stay within reach of the 256 MB memory-side cache: with 64 taxa, 4
-        // blocks per CU (390 MB of tape) ran slower than 3 (91 vs 85 ms); fewer than 3 loses more to latency
-        const size_t tape_per_block = (size_t)std::max(1, p->prog.ntape + p->prog.stack_depth) * 4 * kGradBlock * sizeof(double);
-        if (tape_per_block * (size_t)p->num_cus * (size_t)bpc > ((size_t)300 << 20)) bpc = std::min(bpc, 3);
-        p->grad_blocks_per_cu = bpc;
-    }
-    // transition-matrix gradient kernel: LDS = tip table + tipY + parked adjoints + per-branch accumulators + state codes
-    if (p->grad2_ok) {
-        p->grad2_lds = ((size_t)p->ntaxa * kValueTipRow + 64 + (size_t)p->grad2_rdepth * 4 * kGrad2Block +
-                        2 * (size_t)kGrad2Waves * p->nnodes) * sizeof(double) + (size_t)p->nwords * kGrad2Block * sizeof(uint32_t);
-        p->grad2_ok = p->value_cols > 0 && p->grad2_lds <= 96 * 1024 &&
-                      (p->grad2_lds <= 64 * 1024 || locus_grad2_kernel_allow_lds(p->prog.stack_depth, 96 * 1024) == hipSuccess);
-        if (p->grad2_ok) {
-            int bpc = 1;
-            if (locus_grad2_kernel_occupancy(p->prog.stack_depth, p->grad2_lds, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-            p->grad2_blocks_per_cu = bpc;
-        }
-    }
 }
 
 static int plan_setup_failed(tphip_plan* p, hipError_t e) {
@@ -479,8 +398,8 @@ int tphip_plan_create(const tphip_plan_desc* d_in, tphip_plan** out) {
     e = upload_plan(p, d, cat, chunks);
     if (e != hipSuccess) return plan_setup_failed(p, e);
 
-    // 6. the stage-1 kernels
-    configure_stage1_kernels(p);
+    // 6. the stage-1 kernels (locus_launch_plan.hpp)
+    configure_locus_launch(p, knobs);
     p->saved = save_desc(d);
     *out = p;
     return TPHIP_OK;
@@ -932,233 +851,6 @@ int tphip_quad_townsend_dev(int32_t device, const double* d_rates, int64_t n, do
     return TPHIP_OK;
 }
 
-// Slices per candidate for the locus likelihood / gradient kernels: enough work items to fill the device even when
-// only a few candidates are in flight (the general model's one point per locus), never more than a locus has blocks.
-static int lik_nsplit(const tphip_plan* p, int64_t ncand, int block) {
-    const int64_t target = (int64_t)p->num_cus * 8;
-    int64_t ns = (target + ncand - 1) / std::max<int64_t>(ncand, 1);
-    const int64_t max_blocks = std::max<int64_t>(1, (p->max_locus_cols + block - 1) / block);
-    ns = std::min(ns, max_blocks);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(ns, 4096));
-}
-
-// device buffer grown on demand (its contents are not kept)
-static int grow(void** ptr, size_t& have, size_t need) {
-    if (need <= have && *ptr) return TPHIP_OK;
-    if (*ptr) { HIP_TRY(hipFree(*ptr)); *ptr = nullptr; have = 0; }
-    HIP_TRY(hipMalloc(ptr, need ? need : 1));
-    have = need;
-    return TPHIP_OK;
-}
-
-int tphip_locus_loglik_dev(tphip_plan* p, const uint8_t* d_states, int64_t ncand, const int32_t* d_cand_locus,
-                           const double* d_cand_exch, const double* d_blen_vecs, const int32_t* d_cand_vec,
-                           const double* d_cand_scale, const int32_t* d_cand_pidx, const double* d_cand_pfac, double* d_out,
-                           void* stream) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    if (ncand < 0 || (ncand && (!d_states || !d_cand_locus || !d_cand_exch || !d_blen_vecs || !d_cand_vec || !d_cand_scale ||
-                                !d_cand_pidx || !d_cand_pfac || !d_out)))
-        return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ncand == 0) return TPHIP_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    LikParams L;
-    L.states = d_states; L.ncols_total = p->ncols; L.locus_offsets = p->d_offsets.p; L.models = p->d_models.p;
-    L.col_weight = p->d_col_weight;
-    L.lops = p->d_lik_ops.p; L.nops = (int32_t)p->prog.ops.size(); L.nnodes = p->nnodes; L.ntaxa = p->ntaxa;
-    L.stack_depth = p->prog.stack_depth; L.cand_locus = d_cand_locus; L.cand_exch = d_cand_exch;
-    L.blen_vecs = d_blen_vecs; L.cand_vec = d_cand_vec; L.cand_scale = d_cand_scale; L.cand_pidx = d_cand_pidx;
-    L.cand_pfac = d_cand_pfac; L.out = d_out;
-    if (p->value_cols > 0) {
-        // transition-matrix form: eigen-systems and matrices of a chunk of candidates, then the pruning kernel
-        const int C = p->value_cols;
-        const int nsplit = lik_nsplit(p, ncand, kLikBlock * C);
-        if (nsplit > 1) {
-            int rc = grow((void**)&p->d_part, p->part_bytes, (size_t)ncand * nsplit * sizeof(double));
-            if (rc) return rc;
-        }
-        const size_t per_cand = ((size_t)p->nnodes * 16 + 36) * sizeof(double);
-        int64_t chunk = std::max<int64_t>(1, (int64_t)(kValueWorkspaceBytes / per_cand));
-        chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, ((int64_t)1 << 30) / nsplit));   // grid.x limit
-        chunk = std::min<int64_t>(chunk, ncand);
-        int rc = grow((void**)&p->d_value_ws, p->value_ws_bytes, (size_t)chunk * per_cand);
-        if (rc) return rc;
-        double* d_eig = p->d_value_ws;
-        double* d_pmat = p->d_value_ws + (size_t)chunk * 36;
-        ValueParams V;
-        V.states = d_states; V.ncols_total = p->ncols; V.locus_offsets = p->d_offsets.p; V.col_weight = p->d_col_weight;
-        V.models = p->d_models.p; V.vops = p->d_value_ops.p; V.nvops = p->value_nops; V.ntaxa = p->ntaxa;
-        V.nnodes = p->nnodes; V.pmat = d_pmat; V.nsplit = nsplit;
-        V.tip_taxon = p->d_tip_taxon.p; V.nwords = p->nwords; V.tip_node = p->d_value_tip_node.p;
-        V.packed = (d_states == p->lib_states) ? p->d_value_packed : nullptr;
-        hipStream_t st = (hipStream_t)stream;
-        for (int64_t done = 0; done < ncand; done += chunk) {
-            const int64_t n = std::min<int64_t>(ncand - done, chunk);
-            HIP_TRY(launch_lik_eigen_kernel(st, p->d_models.p, d_cand_locus + done, d_cand_exch + done * 6, n, d_eig));
-            HIP_TRY(launch_lik_pmat_kernel(st, d_eig, d_blen_vecs, d_cand_vec + done, d_cand_scale + done, d_cand_pidx + done,
-                                           d_cand_pfac + done, n, p->nnodes, d_pmat));
-            V.cand_locus = d_cand_locus + done;
-            V.out = (nsplit > 1 ? p->d_part : d_out) + done * nsplit;
-            HIP_TRY(launch_locus_value_kernel(C, p->prog.stack_depth, dim3((unsigned)(n * nsplit)), p->value_lds, st, V));
-        }
-        HIP_TRY(hipGetLastError());
-        if (nsplit > 1) {
-            HIP_TRY(launch_split_sum_kernel(st, p->d_part, d_out, ncand, nsplit, 1));
-        }
-        return TPHIP_OK;
-    }
-    if (!p->lik_ok) return fail(TPHIP_ERR_INVALID, "tree too large for the locus-likelihood kernel's LDS tables");
-    const size_t lds = p->lik_lds;
-    const int nsplit = lik_nsplit(p, ncand, kLikBlock);
-    L.nsplit = nsplit;
-    if (nsplit > 1) {
-        int rc = grow((void**)&p->d_part, p->part_bytes, (size_t)ncand * nsplit * sizeof(double));
-        if (rc) return rc;
-        L.out = p->d_part;
-    }
-    const int64_t per_launch = std::max<int64_t>(1, ((int64_t)1 << 30) / nsplit);   // grid.x limit
-    for (int64_t done = 0; done < ncand; done += per_launch) {
-        const int64_t n = std::min<int64_t>(ncand - done, per_launch);
-        LikParams Q = L;
-        Q.cand_locus += done; Q.cand_exch += done * 6; Q.cand_vec += done; Q.cand_scale += done; Q.cand_pidx += done;
-        Q.cand_pfac += done; Q.out += done * nsplit;
-        HIP_TRY(launch_locus_loglik_kernel(dim3((unsigned)(n * nsplit)), lds, (hipStream_t)stream, Q));
-    }
-    HIP_TRY(hipGetLastError());
-    if (nsplit > 1) {
-        HIP_TRY(launch_split_sum_kernel((hipStream_t)stream, p->d_part, d_out, ncand, nsplit, 1));
-    }
-    return TPHIP_OK;
-}
-
-int tphip_locus_gradient_dev(tphip_plan* p, const uint8_t* d_states, int64_t ncand, const int32_t* d_cand_locus,
-                             const double* d_cand_exch, const double* d_blen_vecs, const int32_t* d_cand_vec,
-                             const double* d_cand_scale, const int32_t* d_cand_pidx, const double* d_cand_pfac, double* d_lnl,
-                             double* d_dexch, double* d_dlogt, double* d_sum_dlogt, double* d_d2logt, void* stream) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    if (ncand < 0 || (ncand && (!d_states || !d_cand_locus || !d_cand_exch || !d_blen_vecs || !d_cand_vec || !d_cand_scale ||
-                                !d_cand_pidx || !d_cand_pfac || !d_lnl || !d_dexch || !d_sum_dlogt)))
-        return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ncand == 0) return TPHIP_OK;
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->grad2_ok && d_states == p->lib_states && p->d_value_packed) {
-        // transition-matrix gradient kernel (locus_grad2_kernel.hpp): eigen-systems, matrices and branch tables of a chunk
-        // of candidates, then resident workgroups loop over (candidate, column slice) items, each with its own tape
-        hipStream_t st = (hipStream_t)stream;
-        const int nsplit = lik_nsplit(p, ncand, kGrad2Block);
-        const size_t nn = (size_t)p->nnodes;
-        const size_t per_cand = (36 + nn * (16 + kGrad2EF)) * sizeof(double);
-        int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)4 << 30) / per_cand));
-        chunk = std::min<int64_t>(chunk, ncand);
-        int rc = grow((void**)&p->d_grad2_ws, p->grad2_ws_bytes, (size_t)chunk * per_cand);
-        if (rc) return rc;
-        double* d_eig = p->d_grad2_ws;
-        double* d_pmat = d_eig + (size_t)chunk * 36;
-        double* d_ef = d_pmat + (size_t)chunk * nn * 16;
-        const size_t items_all = (size_t)ncand * nsplit;
-        if (nsplit > 1) {
-            rc = grow((void**)&p->d_part, p->part_bytes, items_all * (8 + (d_dlogt ? nn : 0) + (d_d2logt ? nn : 0)) * sizeof(double));
-            if (rc) return rc;
-        }
-        const int64_t grid_max = (int64_t)p->num_cus * p->grad2_blocks_per_cu;
-        const size_t need_tape = (size_t)std::min<int64_t>((int64_t)std::min<int64_t>(chunk, ncand) * nsplit, grid_max) *
-                                 (size_t)std::max(1, p->grad2_ntape) * 4 * kGrad2Block * sizeof(double);
-        rc = grow((void**)&p->d_tape, p->tape_bytes, need_tape);
-        if (rc) return rc;
-        if (!p->d_grad2_params) HIP_TRY(hipMalloc((void**)&p->d_grad2_params, sizeof(Grad2Params) * 64));
-        double* o_lnl = nsplit > 1 ? p->d_part : d_lnl;
-        double* o_sum = nsplit > 1 ? p->d_part + items_all : d_sum_dlogt;
-        double* o_dex = nsplit > 1 ? p->d_part + 2 * items_all : d_dexch;
-        double* o_dlt = d_dlogt ? (nsplit > 1 ? p->d_part + 8 * items_all : d_dlogt) : nullptr;
-        double* o_d2 = d_d2logt ? (nsplit > 1 ? p->d_part + (8 + (d_dlogt ? nn : 0)) * items_all : d_d2logt) : nullptr;
-        int slot = 0;
-        for (int64_t done = 0; done < ncand; done += chunk, ++slot) {
-            const int64_t n = std::min<int64_t>(ncand - done, chunk);
-            HIP_TRY(launch_lik_eigen_kernel(st, p->d_models.p, d_cand_locus + done, d_cand_exch + done * 6, n, d_eig));
-            HIP_TRY(launch_lik_pmat_kernel(st, d_eig, d_blen_vecs, d_cand_vec + done, d_cand_scale + done, d_cand_pidx + done,
-                                           d_cand_pfac + done, n, p->nnodes, d_pmat));
-            HIP_TRY(launch_grad2_ef_kernel(st, d_eig, d_blen_vecs, d_cand_vec + done, d_cand_scale + done, d_cand_pidx + done,
-                                           d_cand_pfac + done, n, p->nnodes, d_ef));
-            Grad2Params G2;
-            G2.packed = p->d_value_packed; G2.ncols_total = p->ncols; G2.locus_offsets = p->d_offsets.p; G2.col_weight = p->d_col_weight;
-            G2.models = p->d_models.p; G2.fops = p->d_grad2_fops.p; G2.rops = p->d_grad2_rops.p; G2.nrops = p->grad2_nrops;
-            G2.ntaxa = p->ntaxa; G2.nnodes = p->nnodes; G2.nwords = p->nwords; G2.ntape = p->grad2_ntape; G2.rdepth = p->grad2_rdepth;
-            G2.tip_node = p->d_value_tip_node.p; G2.cand_locus = d_cand_locus + done; G2.eig = d_eig; G2.pmat = d_pmat; G2.ef = d_ef;
-            G2.ncand = n; G2.nsplit = nsplit; G2.tape = p->d_tape;
-            const size_t o = (size_t)done * nsplit;
-            G2.out_lnl = o_lnl + o; G2.out_sum_dlogt = o_sum + o; G2.out_dexch = o_dex + o * 6;
-            G2.out_dlogt = o_dlt ? o_dlt + o * nn : nullptr; G2.out_d2logt = o_d2 ? o_d2 + o * nn : nullptr;
-            if (slot >= 64) { HIP_TRY(hipStreamSynchronize(st)); slot = 0; }   // the parameter blocks in flight are a ring of 64
-            Grad2Params* d_par = (Grad2Params*)p->d_grad2_params + slot;
-            HIP_TRY(hipMemcpyAsync(d_par, &G2, sizeof(Grad2Params), hipMemcpyHostToDevice, st));
-            const int64_t grid = std::min<int64_t>(n * nsplit, grid_max);
-            HIP_TRY(launch_locus_grad2_kernel(p->prog.stack_depth, dim3((unsigned)grid), p->grad2_lds, st, d_par));
-        }
-        if (nsplit > 1) {
-            (void)launch_split_sum_kernel(st, o_lnl, d_lnl, ncand, nsplit, 1);
-            (void)launch_split_sum_kernel(st, o_sum, d_sum_dlogt, ncand, nsplit, 1);
-            (void)launch_split_sum_kernel(st, o_dex, d_dexch, ncand, nsplit, 6);
-            if (d_dlogt) (void)launch_split_sum_kernel(st, o_dlt, d_dlogt, ncand, nsplit, (int)nn);
-            if (d_d2logt) (void)launch_split_sum_kernel(st, o_d2, d_d2logt, ncand, nsplit, (int)nn);
-            HIP_TRY(hipGetLastError());
-        }
-        return TPHIP_OK;
-    }
-    GradParams G;
-    LikParams& L = G.L;
-    L.states = d_states; L.ncols_total = p->ncols; L.locus_offsets = p->d_offsets.p; L.models = p->d_models.p;
-    L.col_weight = p->d_col_weight;
-    L.lops = p->d_lik_ops.p; L.nops = (int32_t)p->prog.ops.size(); L.nnodes = p->nnodes; L.ntaxa = p->ntaxa;
-    L.stack_depth = p->prog.stack_depth; L.cand_locus = d_cand_locus; L.cand_exch = d_cand_exch;
-    L.blen_vecs = d_blen_vecs; L.cand_vec = d_cand_vec; L.cand_scale = d_cand_scale; L.cand_pidx = d_cand_pidx;
-    L.cand_pfac = d_cand_pfac; L.out = d_lnl;
-    G.ntape = p->prog.ntape; G.ncand = ncand; G.nslots = p->grad_slots;
-    G.out_dexch = d_dexch; G.out_dlogt = d_dlogt; G.out_sum_dlogt = d_sum_dlogt; G.out_d2logt = d_d2logt;
-    if (!p->grad_ok) return fail(TPHIP_ERR_INVALID, "tree too large for the locus-gradient kernel's LDS tables");
-    const size_t lds = p->grad_lds;
-    L.stage_states = p->grad_stage;
-    const int blocks_per_cu = p->grad_blocks_per_cu;   // resident workgroups loop over the candidates; each owns one tape
-    const int nsplit = lik_nsplit(p, ncand, kGradBlock);
-    L.nsplit = nsplit;
-    const size_t nn = (size_t)p->nnodes, items = (size_t)ncand * nsplit;
-    if (nsplit > 1) {   // partials: lnl[items], sum[items], dexch[items][6], dlogt[items][nn]
-        int rc = grow((void**)&p->d_part, p->part_bytes, items * (8 + (d_dlogt ? nn : 0) + (d_d2logt ? nn : 0)) * sizeof(double));
-        if (rc) return rc;
-        L.out = p->d_part;
-        G.out_sum_dlogt = p->d_part + items;
-        G.out_dexch = p->d_part + 2 * items;
-        G.out_dlogt = d_dlogt ? p->d_part + 8 * items : nullptr;
-        G.out_d2logt = d_d2logt ? p->d_part + (8 + (d_dlogt ? nn : 0)) * items : nullptr;
-    }
-    const int64_t grid = std::min<int64_t>((int64_t)items, (int64_t)p->num_cus * blocks_per_cu);
-    const size_t need = (size_t)grid * (size_t)std::max(1, p->prog.ntape + p->prog.stack_depth) * 4 * kGradBlock * sizeof(double);
-    int rc = grow((void**)&p->d_tape, p->tape_bytes, need);
-    if (rc) return rc;
-    G.tape = p->d_tape;
-    // eigen-systems of the candidates by one thread each (locus_value_launch.hip) instead of thread 0 of every work item
-    G.cand_eig = nullptr;
-    {
-        rc = grow((void**)&p->d_grad_eig, p->grad_eig_bytes, (size_t)ncand * 36 * sizeof(double));
-        if (rc) return rc;
-        HIP_TRY(launch_lik_eigen_kernel((hipStream_t)stream, p->d_models.p, d_cand_locus, d_cand_exch, ncand, p->d_grad_eig));
-        G.cand_eig = p->d_grad_eig;
-    }
-    if (!p->d_grad_params) HIP_TRY(hipMalloc((void**)&p->d_grad_params, sizeof(GradParams)));
-    HIP_TRY(hipMemcpyAsync(p->d_grad_params, &G, sizeof(GradParams), hipMemcpyHostToDevice, (hipStream_t)stream));
-    HIP_TRY(launch_locus_grad_kernel(dim3((unsigned)grid), lds, (hipStream_t)stream, (const GradParams*)p->d_grad_params));
-    if (nsplit > 1) {
-        auto sum = [&](const double* part, double* out, int width) {
-            (void)launch_split_sum_kernel((hipStream_t)stream, part, out, ncand, nsplit, width);
-        };
-        sum(L.out, d_lnl, 1);
-        sum(G.out_sum_dlogt, d_sum_dlogt, 1);
-        sum(G.out_dexch, d_dexch, 6);
-        if (d_dlogt) sum(G.out_dlogt, d_dlogt, (int)nn);
-        if (d_d2logt) sum(G.out_d2logt, d_d2logt, (int)nn);
-        HIP_TRY(hipGetLastError());
-    }
-    return TPHIP_OK;
-}
-
 int tphip_state_histogram_dev(int32_t device, const uint8_t* d_states, int64_t ncols_total, int32_t ntaxa,
                               const int64_t* d_locus_offsets, int64_t nloci, int64_t* d_hist, void* stream) {
     if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
@@ -1179,10 +871,10 @@ int tphip_state_histogram_dev(int32_t device, const uint8_t* d_states, int64_t n
 // Pageable memory is copied by the runtime's own staged hipMemcpy (same code path, no overlap).
 namespace {
 struct HostBuffers {
-    uint8_t* states = nullptr; size_t states_bytes = 0;
-    char* percol = nullptr; size_t percol_bytes = 0;    // rate | subst | lnl | nres | flag, one allocation
-    double* tables = nullptr; size_t tables_bytes = 0;
-    void* ws = nullptr; size_t ws_bytes = 0;
+    DevGrow states;
+    DevGrow percol;    // rate | subst | lnl | nres | flag, one allocation
+    DevGrow tables;
+    DevGrow ws;
     hipStream_t copy_stream = nullptr, run_stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_site = nullptr;
 };
@@ -1197,14 +889,13 @@ bool is_pinned(const void* q) {   // host memory the DMA engines can reach direc
 struct tphip_host_buffers : HostBuffers {};
 
 static void free_host_buffers(tphip_plan* p) {
-    HostBuffers* B = p->hostbuf;
+    tphip_host_buffers* B = p->hostbuf;
     if (!B) return;
-    for (void* q : {(void*)B->states, (void*)B->percol, (void*)B->tables, B->ws}) if (q) (void)hipFree(q);
     if (B->copy_stream) (void)hipStreamDestroy(B->copy_stream);
     if (B->run_stream) (void)hipStreamDestroy(B->run_stream);
     if (B->ev_in) (void)hipEventDestroy(B->ev_in);
     if (B->ev_site) (void)hipEventDestroy(B->ev_site);
-    delete B;
+    delete B;   // and with it the four device buffers
     p->hostbuf = nullptr;
 }
 
@@ -1227,25 +918,27 @@ static int host_enqueue(tphip_plan* p, const uint8_t* states, size_t spitch, hip
     // per-column block: rate | subst | lnl (8 B each) | nres (4 B) | flag (1 B), each part 256-byte aligned
     const size_t o_rate = 0, o_subst = align_up(8 * n, 256), o_lnl = o_subst + align_up(8 * n, 256),
                  o_nres = o_lnl + align_up(8 * n, 256), o_flag = o_nres + align_up(4 * n, 256);
-    int rc = grow((void**)&B.percol, B.percol_bytes, o_flag + align_up(n, 256));
+    int rc = B.percol.reserve(o_flag + align_up(n, 256));
     if (rc) return rc;
-    rc = grow(&B.ws, B.ws_bytes, p->ws.total);
+    rc = B.ws.reserve(p->ws.total);
     if (rc) return rc;
-    double* d_rate = (double*)(B.percol + o_rate);
-    double* d_subst = (double*)(B.percol + o_subst);
-    double* d_lnl = (double*)(B.percol + o_lnl);
-    int32_t* d_nres = (int32_t*)(B.percol + o_nres);
-    uint8_t* d_flag = (uint8_t*)(B.percol + o_flag);
+    char* percol = (char*)B.percol.p;
+    double* d_rate = (double*)(percol + o_rate);
+    double* d_subst = (double*)(percol + o_subst);
+    double* d_lnl = (double*)(percol + o_lnl);
+    int32_t* d_nres = (int32_t*)(percol + o_nres);
+    uint8_t* d_flag = (uint8_t*)(percol + o_flag);
     hipStream_t cs = B.copy_stream, rs = B.run_stream;
     if (do_site) {
         if (!states || !rate || !subst || !lnl || !flag || !nres) return fail(TPHIP_ERR_INVALID, "null host pointer");
-        rc = grow((void**)&B.states, B.states_bytes, n * (size_t)p->ntaxa + 1);
+        rc = B.states.reserve(n * (size_t)p->ntaxa + 1);
         if (rc) return rc;
+        uint8_t* d_states = (uint8_t*)B.states.p;
         if (after) HIP_TRY(hipStreamWaitEvent(rs, after, 0));
-        if (spitch == n) HIP_TRY(hipMemcpyAsync(B.states, states, n * (size_t)p->ntaxa, hipMemcpyHostToDevice, rs));
-        else HIP_TRY(hipMemcpy2DAsync(B.states, n, states, spitch, n, (size_t)p->ntaxa, hipMemcpyHostToDevice, rs));
+        if (spitch == n) HIP_TRY(hipMemcpyAsync(d_states, states, n * (size_t)p->ntaxa, hipMemcpyHostToDevice, rs));
+        else HIP_TRY(hipMemcpy2DAsync(d_states, n, states, spitch, n, (size_t)p->ntaxa, hipMemcpyHostToDevice, rs));
         HIP_TRY(hipEventRecord(B.ev_in, rs));
-        rc = launch_site_rates(p, B.states, d_rate, d_subst, d_lnl, d_flag, d_nres, B.ws, rs, -1);
+        rc = launch_site_rates(p, d_states, d_rate, d_subst, d_lnl, d_flag, d_nres, B.ws.p, rs, -1);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(B.ev_site, rs));
     } else {
@@ -1255,9 +948,9 @@ static int host_enqueue(tphip_plan* p, const uint8_t* states, size_t spitch, hip
     }
     if (do_pi) {
         if (!tables) return fail(TPHIP_ERR_INVALID, "null host pointer");
-        rc = grow((void**)&B.tables, B.tables_bytes, sizeof(double) * W * (size_t)p->nloci + 8);
+        rc = B.tables.reserve(sizeof(double) * W * (size_t)p->nloci + 8);
         if (rc) return rc;
-        rc = launch_pi_tables(p, d_rate, (do_site || nres_in) ? d_nres : nullptr, B.tables, B.ws, rs, -1);
+        rc = launch_pi_tables(p, d_rate, (do_site || nres_in) ? d_nres : nullptr, (double*)B.tables.p, B.ws.p, rs, -1);
         if (rc) return rc;
     }
     if (do_site) {
@@ -1272,7 +965,7 @@ static int host_enqueue(tphip_plan* p, const uint8_t* states, size_t spitch, hip
         HIP_TRY(hipMemcpyAsync(flag, d_flag, n, hipMemcpyDeviceToHost, os));
         HIP_TRY(hipMemcpyAsync(nres, d_nres, sizeof(int32_t) * n, hipMemcpyDeviceToHost, os));
     }
-    if (do_pi) HIP_TRY(hipMemcpyAsync(tables, B.tables, sizeof(double) * W * (size_t)p->nloci, hipMemcpyDeviceToHost, rs));
+    if (do_pi) HIP_TRY(hipMemcpyAsync(tables, B.tables.p, sizeof(double) * W * (size_t)p->nloci, hipMemcpyDeviceToHost, rs));
     return TPHIP_OK;
 }
 
@@ -1441,18 +1134,6 @@ int tphip_eval_columns(tphip_plan* p, const uint8_t* states, const double* u, do
     return TPHIP_OK;
 }
 
-int tphip_plan_set_column_weights(tphip_plan* p, const double* weights) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->d_col_weight) { HIP_TRY(hipFree(p->d_col_weight)); p->d_col_weight = nullptr; }
-    if (!weights || p->ncols == 0) return TPHIP_OK;
-    for (int64_t c = 0; c < p->ncols; ++c)
-        if (!(weights[c] >= 0.0)) return fail(TPHIP_ERR_INVALID, "column weights must be >= 0");
-    HIP_TRY(hipMalloc((void**)&p->d_col_weight, sizeof(double) * (size_t)p->ncols));
-    HIP_TRY(hipMemcpy(p->d_col_weight, weights, sizeof(double) * (size_t)p->ncols, hipMemcpyHostToDevice));
-    return TPHIP_OK;
-}
-
 // per-locus eigen-systems from DEVICE arrays pi [L][4] (floored, any scale) and exch [L][6]; for stage1_driver.hip
 int tphip_internal_set_models_dev(tphip_plan* p, const double* d_pi, const double* d_exch, void* stream) {
     const int bs = 64;
@@ -1512,183 +1193,6 @@ int tphip_plan_set_models(tphip_plan* p, const double* pi, const double* exch) {
     // locus groups of the pipelined host path were built from the old models: rebuilt on next use
     for (tphip_plan* q : p->parts) (void)tphip_plan_destroy(q);
     p->parts.clear();
-    return TPHIP_OK;
-}
-
-int tphip_free_device(tphip_plan* p, void* d_ptr) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    HIP_TRY(hipSetDevice(p->device));
-    if (d_ptr && d_ptr == (void*)p->lib_states) {   // the alignment cache goes: so do the codes packed from it
-        if (p->d_value_packed) { HIP_TRY(hipFree(p->d_value_packed)); p->d_value_packed = nullptr; }
-        p->lib_states = nullptr;
-    }
-    if (d_ptr) HIP_TRY(hipFree(d_ptr));
-    return TPHIP_OK;
-}
-
-// Candidate batch staged through the plan's arena: one pinned buffer, one H2D copy in, one D2H copy out.
-namespace {
-struct CandBatch {
-    size_t off_locus, off_exch, off_blen, off_vec, off_scale, off_pidx, off_pfac, in_bytes;
-    size_t off_out, out_bytes, total;
-};
-
-int arena_reserve(tphip_plan* p, size_t bytes) {
-    if (bytes <= p->arena_bytes) return TPHIP_OK;
-    const size_t want = std::max(bytes, p->arena_bytes * 2);
-    if (p->d_arena) { HIP_TRY(hipFree(p->d_arena)); p->d_arena = nullptr; }
-    if (p->h_arena) { HIP_TRY(hipHostFree(p->h_arena)); p->h_arena = nullptr; }
-    p->arena_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&p->d_arena, want));
-    HIP_TRY(hipHostMalloc((void**)&p->h_arena, want, hipHostMallocDefault));
-    p->arena_bytes = want;
-    return TPHIP_OK;
-}
-
-int check_candidates(const tphip_plan* p, int64_t nvec, int64_t ncand, const int32_t* cand_locus, const int32_t* cand_vec,
-                     const int32_t* cand_pidx) {
-    for (int64_t c = 0; c < ncand; ++c) {
-        if (cand_locus[c] < 0 || cand_locus[c] >= p->nloci) return fail(TPHIP_ERR_INVALID, "cand_locus out of range");
-        if (cand_vec[c] < 0 || cand_vec[c] >= nvec) return fail(TPHIP_ERR_INVALID, "cand_vec out of range");
-        if (cand_pidx[c] >= p->nnodes) return fail(TPHIP_ERR_INVALID, "cand_pidx out of range");
-    }
-    return TPHIP_OK;
-}
-
-// device copy of the alignment: the caller's cache, or a scratch buffer for this call
-int stage_alignment(tphip_plan* p, const uint8_t* states, void** d_states_cache, Scratch& S, uint8_t** d_s) {
-    const size_t nb = (size_t)p->ncols * (size_t)p->ntaxa;
-    *d_s = d_states_cache ? (uint8_t*)*d_states_cache : nullptr;
-    if (*d_s) return TPHIP_OK;
-    if (d_states_cache) {
-        HIP_TRY(hipMalloc((void**)d_s, nb ? nb : 1));
-        *d_states_cache = *d_s;
-    } else {
-        *d_s = S.get<uint8_t>(nb);
-        if (!*d_s) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    }
-    HIP_TRY(hipMemcpy(*d_s, states, nb, hipMemcpyHostToDevice));
-    if (d_states_cache && p->value_cols > 0 && p->ncols > 0) {
-        // a copy that stays: pack its state codes once for locus_value_kernel (8 per word, tip order) instead of once per
-        // likelihood evaluation.  Only for the copy made here -- the library cannot know when a caller's own device array changes.
-        if (p->d_value_packed) { HIP_TRY(hipFree(p->d_value_packed)); p->d_value_packed = nullptr; }
-        p->lib_states = nullptr;
-        HIP_TRY(hipMalloc((void**)&p->d_value_packed, sizeof(uint32_t) * (size_t)p->nwords * (size_t)p->ncols));
-        HIP_TRY(launch_value_pack_codes_kernel(nullptr, *d_s, p->ncols, p->d_tip_taxon.p, p->nwords, p->d_value_packed));
-        HIP_TRY(hipStreamSynchronize(nullptr));   // later launches may come on any stream
-        p->lib_states = *d_s;
-    }
-    return TPHIP_OK;
-}
-
-}  // namespace
-
-// device copy of the alignment in the caller's cache slot, for the other translation units (stage1_driver.hip)
-int tphip_internal_stage_alignment(tphip_plan* p, const uint8_t* states, void** d_states_cache, uint8_t** d_s) {
-    Scratch S;
-    return stage_alignment(p, states, d_states_cache, S, d_s);
-}
-
-namespace {
-int stage_candidates(tphip_plan* p, int64_t nvec, const double* blen_vecs, int64_t ncand, const int32_t* cand_locus,
-                     const double* cand_exch, const int32_t* cand_vec, const double* cand_scale, const int32_t* cand_pidx,
-                     const double* cand_pfac, size_t out_doubles, CandBatch* B) {
-    const size_t n = (size_t)ncand, nn = (size_t)p->nnodes;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    B->off_locus = take(sizeof(int32_t) * n);
-    B->off_exch = take(sizeof(double) * n * 6);
-    B->off_blen = take(sizeof(double) * (size_t)nvec * nn);
-    B->off_vec = take(sizeof(int32_t) * n);
-    B->off_scale = take(sizeof(double) * n);
-    B->off_pidx = take(sizeof(int32_t) * n);
-    B->off_pfac = take(sizeof(double) * n);
-    B->in_bytes = off;
-    B->off_out = take(sizeof(double) * out_doubles);
-    B->out_bytes = sizeof(double) * out_doubles;
-    B->total = off;
-    int rc = arena_reserve(p, B->total);
-    if (rc) return rc;
-    char* h = p->h_arena;
-    memcpy(h + B->off_locus, cand_locus, sizeof(int32_t) * n);
-    memcpy(h + B->off_exch, cand_exch, sizeof(double) * n * 6);
-    memcpy(h + B->off_blen, blen_vecs, sizeof(double) * (size_t)nvec * nn);
-    memcpy(h + B->off_vec, cand_vec, sizeof(int32_t) * n);
-    memcpy(h + B->off_scale, cand_scale, sizeof(double) * n);
-    memcpy(h + B->off_pidx, cand_pidx, sizeof(int32_t) * n);
-    memcpy(h + B->off_pfac, cand_pfac, sizeof(double) * n);
-    HIP_TRY(hipMemcpyAsync(p->d_arena, h, B->in_bytes, hipMemcpyHostToDevice, nullptr));
-    return TPHIP_OK;
-}
-}  // namespace
-
-int tphip_locus_loglik(tphip_plan* p, const uint8_t* states, void** d_states_cache, int64_t nvec, const double* blen_vecs,
-                       int64_t ncand, const int32_t* cand_locus, const double* cand_exch, const int32_t* cand_vec,
-                       const double* cand_scale, const int32_t* cand_pidx, const double* cand_pfac, double* out) {
-    if (!p || !states || ncand < 0 || nvec < 0 ||
-        (ncand && (!blen_vecs || !cand_locus || !cand_exch || !cand_vec || !cand_scale || !cand_pidx || !cand_pfac || !out)))
-        return fail(TPHIP_ERR_INVALID, "null argument");
-    if (ncand == 0) return TPHIP_OK;
-    int rc = check_candidates(p, nvec, ncand, cand_locus, cand_vec, cand_pidx);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
-    uint8_t* d_s = nullptr;
-    rc = stage_alignment(p, states, d_states_cache, S, &d_s);
-    if (rc) return rc;
-    CandBatch B;
-    rc = stage_candidates(p, nvec, blen_vecs, ncand, cand_locus, cand_exch, cand_vec, cand_scale, cand_pidx, cand_pfac,
-                          (size_t)ncand, &B);
-    if (rc) return rc;
-    char* d = p->d_arena;
-    rc = tphip_locus_loglik_dev(p, d_s, ncand, (const int32_t*)(d + B.off_locus), (const double*)(d + B.off_exch),
-                                (const double*)(d + B.off_blen), (const int32_t*)(d + B.off_vec),
-                                (const double*)(d + B.off_scale), (const int32_t*)(d + B.off_pidx),
-                                (const double*)(d + B.off_pfac), (double*)(d + B.off_out), nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(p->h_arena + B.off_out, d + B.off_out, B.out_bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    memcpy(out, p->h_arena + B.off_out, B.out_bytes);
-    return TPHIP_OK;
-}
-
-int tphip_locus_gradient(tphip_plan* p, const uint8_t* states, void** d_states_cache, int64_t nvec, const double* blen_vecs,
-                         int64_t ncand, const int32_t* cand_locus, const double* cand_exch, const int32_t* cand_vec,
-                         const double* cand_scale, const int32_t* cand_pidx, const double* cand_pfac, double* lnl,
-                         double* dexch, double* dlogt, double* sum_dlogt, double* d2logt) {
-    if (!p || !states || ncand < 0 || nvec < 0 ||
-        (ncand && (!blen_vecs || !cand_locus || !cand_exch || !cand_vec || !cand_scale || !cand_pidx || !cand_pfac || !lnl ||
-                   !dexch || !sum_dlogt)))
-        return fail(TPHIP_ERR_INVALID, "null argument");
-    if (ncand == 0) return TPHIP_OK;
-    int rc = check_candidates(p, nvec, ncand, cand_locus, cand_vec, cand_pidx);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
-    uint8_t* d_s = nullptr;
-    rc = stage_alignment(p, states, d_states_cache, S, &d_s);
-    if (rc) return rc;
-    const size_t n = (size_t)ncand, nn = (size_t)p->nnodes;
-    CandBatch B;   // outputs: lnl[n] | sum_dlogt[n] | dexch[6n] | dlogt[n * nn] (optional) | d2logt[n * nn] (optional)
-    rc = stage_candidates(p, nvec, blen_vecs, ncand, cand_locus, cand_exch, cand_vec, cand_scale, cand_pidx, cand_pfac,
-                          n * (8 + (dlogt ? nn : 0) + (d2logt ? nn : 0)), &B);
-    if (rc) return rc;
-    char* d = p->d_arena;
-    double* d_o = (double*)(d + B.off_out);
-    rc = tphip_locus_gradient_dev(p, d_s, ncand, (const int32_t*)(d + B.off_locus), (const double*)(d + B.off_exch),
-                                  (const double*)(d + B.off_blen), (const int32_t*)(d + B.off_vec),
-                                  (const double*)(d + B.off_scale), (const int32_t*)(d + B.off_pidx),
-                                  (const double*)(d + B.off_pfac), d_o, d_o + 2 * n, dlogt ? d_o + 8 * n : nullptr, d_o + n,
-                                  d2logt ? d_o + (8 + (dlogt ? nn : 0)) * n : nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(p->h_arena + B.off_out, d + B.off_out, B.out_bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    const double* h_o = (const double*)(p->h_arena + B.off_out);
-    memcpy(lnl, h_o, sizeof(double) * n);
-    memcpy(sum_dlogt, h_o + n, sizeof(double) * n);
-    memcpy(dexch, h_o + 2 * n, sizeof(double) * n * 6);
-    if (dlogt) memcpy(dlogt, h_o + 8 * n, sizeof(double) * n * nn);
-    if (d2logt) memcpy(d2logt, h_o + (8 + (dlogt ? nn : 0)) * n, sizeof(double) * n * nn);
     return TPHIP_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "locus_lik_params.hpp"
 #include "locus_value_params.hpp"
 #include "locus_grad2_params.hpp"
+#include "locus_launch_plan.hpp"
 #include "site_launch_plan.hpp"
 #include "site_rate_params.hpp"
 #include "tphip.h"
@@ -37,10 +38,15 @@ inline int fail(int code, const std::string& msg) {
 constexpr int kProfileRing = 1024;
 constexpr double kPiFloor = 1e-12;
 
+// device array of a fixed size, freed with its owner (on the device that is current then: tphip_plan_destroy sets the plan's)
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t alloc(size_t count) {
         n = count;
         return hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
@@ -54,6 +60,37 @@ struct DevBuf {
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
+    }
+};
+
+// device buffer grown on demand (its contents are not kept), freed with its owner
+struct DevGrow {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevGrow() = default;
+    DevGrow(const DevGrow&) = delete;
+    DevGrow& operator=(const DevGrow&) = delete;
+    ~DevGrow() { if (p) (void)hipFree(p); }
+    int reserve(size_t need) {
+        if (need <= bytes && p) return TPHIP_OK;
+        if (p) { HIP_TRY(hipFree(p)); p = nullptr; bytes = 0; }
+        HIP_TRY(hipMalloc(&p, need ? need : 1));
+        bytes = need;
+        return TPHIP_OK;
+    }
+};
+
+// grow-only device arena + pinned host mirror of the same size (arena_reserve in locus_driver.hip: doubling)
+struct HostArena {
+    char* d = nullptr;
+    char* h = nullptr;
+    size_t bytes = 0;
+    HostArena() = default;
+    HostArena(const HostArena&) = delete;
+    HostArena& operator=(const HostArena&) = delete;
+    ~HostArena() {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
     }
 };
 
@@ -97,51 +134,38 @@ struct tphip_plan {
     DevBuf<int64_t> d_offsets, d_locus_pichunk_offsets;
     DevBuf<int32_t> d_tip_taxon, d_op_node;
     DevBuf<int32_t> d_cls_steps;   // TreeProgram::cls_steps, read as int2 by classify_kernel
-    // launch configuration of the locus likelihood / gradient kernels, fixed at plan creation: LDS bytes, whether the
-    // gradient kernel stages its state masks, resident gradient blocks per CU
-    size_t lik_lds = 0, grad_lds = 0;
-    int32_t grad_stage = 0, grad_blocks_per_cu = 1, grad_slots = 4;
-    bool lik_ok = false, grad_ok = false;
+    // launch configuration of the locus likelihood / gradient kernels, fixed at plan creation (locus_launch_plan.hpp:
+    // decide_locus_launch)
+    LocusLaunch locus;
     int32_t ncat = 0;
     DevBuf<double> d_cat;     // [2 * ncat] category rates, then log weights
     DevBuf<int4> d_lik_ops;   // {code, taxon, node, tape slot} per op for the locus likelihood / gradient kernels
-    double* d_tape = nullptr;   // reverse-mode tape of locus_grad_kernel, grown on demand
-    double* d_grad_eig = nullptr;   // per-candidate eigen-systems for locus_grad_kernel
-    size_t grad_eig_bytes = 0;
-    double* d_value_ws = nullptr;   // per-candidate eigen-systems + transition matrices of locus_value_kernel (one chunk)
-    size_t value_ws_bytes = 0;
+    DevGrow tape;       // reverse-mode tape of the gradient kernels
+    DevGrow grad_eig;   // per-candidate eigen-systems for locus_grad_kernel
+    DevGrow value_ws;   // per-candidate eigen-systems + transition matrices of locus_value_kernel (one chunk)
     const uint8_t* lib_states = nullptr;   // the device copy of the alignment the library made itself (stage_alignment) ...
     uint32_t* d_value_packed = nullptr;    // ... and its state codes packed for locus_value_kernel (valid for exactly that copy)
-    int32_t value_cols = 0;         // columns per thread of locus_value_kernel (0: tree too large for it, eigenbasis kernel instead)
-    size_t value_lds = 0;
     DevBuf<int4> d_value_ops;       // fused op stream of locus_value_kernel
     DevBuf<int32_t> d_value_tip_node;
     int32_t value_nops = 0;
-    size_t tape_bytes = 0;
-    // grow-only device arena + pinned host mirror for the host-pointer likelihood / gradient calls: the optimiser
-    // makes thousands of small calls, so they must not hipMalloc or issue a dozen pageable copies each
-    char* d_arena = nullptr;
-    char* h_arena = nullptr;
-    size_t arena_bytes = 0;
-    void* d_grad_params = nullptr;   // device copy of the gradient kernel's parameter block
+    // the host-pointer likelihood / gradient calls stage through it: the optimiser makes thousands of small calls, so they
+    // must not hipMalloc or issue a dozen pageable copies each
+    HostArena arena;
+    DevGrow grad_params;   // device copy of the gradient kernel's parameter block
     // transition-matrix gradient kernel (locus_grad2_kernel.hpp): binary trees with the value kernel's packed state codes
-    bool grad2_ok = false;
+    bool grad2_built = false;        // its programs are on the device (whether it runs: locus.grad2_ok)
     DevBuf<int4> d_grad2_fops, d_grad2_rops;
-    int32_t grad2_nrops = 0, grad2_ntape = 0, grad2_rdepth = 0, grad2_blocks_per_cu = 1;
-    size_t grad2_lds = 0;
-    double* d_grad2_ws = nullptr;    // per-candidate transition matrices + branch tables of one chunk of candidates
-    size_t grad2_ws_bytes = 0;
-    void* d_grad2_params = nullptr;
-    void* d_eb_ws = nullptr;         // workspace of the empirical-Bayes calls (eb_driver.hip), grown on demand
-    size_t eb_ws_bytes = 0;
+    int32_t grad2_nrops = 0, grad2_ntape = 0, grad2_rdepth = 0;
+    DevGrow grad2_ws;       // per-candidate transition matrices + branch tables of one chunk of candidates
+    DevGrow grad2_params;   // ring of 64 parameter blocks
+    DevGrow eb_ws;          // workspace of the empirical-Bayes calls (eb_driver.hip)
     // simulation kernel (simulate_driver.hip), made on first use: the tree as SimNode[nnodes], the workgroup size at which the
     // packed states of its internal nodes fit the LDS and their words per column; the stream ids of a call with locus_ids
     void* d_sim_nodes = nullptr;
     int32_t sim_block = 0, sim_words = 0;
     int64_t* d_sim_ids = nullptr;
     double* d_col_weight = nullptr;  // optional column multiplicities for the locus likelihood / gradient kernels
-    double* d_part = nullptr;   // per-slice partial sums of the locus likelihood / gradient kernels, grown on demand
-    size_t part_bytes = 0;
+    DevGrow part;   // per-slice partial sums of the locus likelihood / gradient kernels
     int64_t max_locus_cols = 0;
     int32_t nnodes = 0;
     int32_t nwords = 0;
@@ -177,7 +201,10 @@ struct EbPrep {
     int32_t* work_count;          // [nloci]       (patterns)
 };
 
-// helpers of tphip.hip for the other translation units of the library (not declared in include/tphip.h)
+// launch configuration of the stage-1 kernels of a new plan, from its tree and batch (locus_driver.hip, for tphip_plan_create)
+__attribute__((visibility("hidden"))) void configure_locus_launch(tphip_plan* p, const PlanKnobs& knobs);
+
+// helpers of tphip.hip and locus_driver.hip for the other translation units of the library (not declared in include/tphip.h)
 // (hidden visibility: the shared library exports exactly what include/tphip.h declares)
 extern "C" {
 __attribute__((visibility("hidden"))) int tphip_internal_stage_alignment(tphip_plan* p, const uint8_t* states, void** d_states_cache,
