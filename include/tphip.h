@@ -517,6 +517,49 @@ int tphip_quartet_sites(tphip_plan *plan, const double *rates, const int32_t *nr
                         double *sites);
 
 /* ------------------------------------------------------------------------------------------------
+ * Quartet signal and noise with unequal tips (an extension: Su & Townsend 2015).  The four-taxon tree is
+ * ((a:Ta, b:Tb)u, (c:Tc, d:Td)v) with the internode u-v of length t_o, all in the tree's original time units.  A site of
+ * final rate r under the locus' model normalised to one substitution has A = P(r Ta), B = P(r Tb), C = P(r Tc), D = P(r Td),
+ * N = P(r t_o), P(tau) = exp(Q tau / kappa), and with R_u[i][j] = sum_v N_uv C_vi D_vj and i != j throughout
+ *   signal y  = sum_u pi_u sum_i A_ui B_ui sum_{j != i} R_u[j][j]   (tip pattern iijj, supports ab|cd)
+ *   noise  x1 = sum_u pi_u sum_{i != j} A_ui B_uj R_u[i][j]         (tip pattern ijij, supports ac|bd)
+ *   noise  x2 = sum_u pi_u sum_{i != j} A_ui B_uj R_u[j][i]         (tip pattern ijji, supports ad|bc).
+ * A NaN (culled) or zero rate gives exactly 0 for all three; all tips 0 gives x1 = x2 = 0 exactly.  Inputs are those of
+ * tphip_quartet_tables.
+ *
+ * Row per (locus, quartet), 13 doubles, rows [nloci][n_q][13]: the sums over the locus' columns of y, x1, x2, y^2, x1^2,
+ * x2^2, y x1, y x2, x1 x2, then p_correct, p_ac, p_ad, p_polytomy: the probabilities that the count of signal sites S, of
+ * ijij sites N1 or of ijji sites N2 ends more than 0.5 ahead of both others, or that none does -- by the bivariate-normal
+ * approximation of the section above (Var = sum - sum of squares, Cov = -(cross sum); the correlation is clamped to
+ * [-0.999, 0.999] for p_correct and to [-0.999, 0.99] for the wrong topologies where the two thresholds differ);
+ * (0, 0, 0, 1) for an empty or fully culled locus.
+ *
+ * Determinism: a row depends on the locus' final rates, its model and the quartet's (Ta, Tb, Tc, Td, t_o) only -- not on the
+ * other loci of the plan, on the other quartets of the list or on how a batch is sharded.  Calls on one plan must not overlap.
+ * Errors are TPHIP_ERR_INVALID throughout, a workspace below tphip_unequal_quartet_workspace_bytes() included. */
+typedef struct tphip_unequal_quartet_opts {
+    uint32_t struct_size;      /* sizeof(tphip_unequal_quartet_opts) of the caller */
+    int32_t n_q;               /* quartets, 1..256 */
+    const double *tips;        /* HOST [n_q][4] Ta, Tb, Tc, Td >= 0; read before the call returns */
+    const double *internode;   /* HOST [n_q] t_o > 0; read before the call returns */
+} tphip_unequal_quartet_opts;
+
+/* bytes of device workspace (8-byte aligned) tphip_unequal_quartet_tables_dev needs for these options */
+int tphip_unequal_quartet_workspace_bytes(const tphip_plan *plan, const tphip_unequal_quartet_opts *opts, size_t *bytes);
+/* d_rows [nloci][n_q][13].  Enqueues on `stream`, does not synchronise. */
+int tphip_unequal_quartet_tables_dev(tphip_plan *plan, const double *d_rates, const int32_t *d_nres,
+                                     const tphip_unequal_quartet_opts *opts, double *d_rows, void *d_workspace,
+                                     size_t workspace_bytes, void *stream);
+/* the per-site values: d_sites [3][n_q][ncols], y, x1, x2.  Enqueues on `stream`, does not synchronise. */
+int tphip_unequal_quartet_sites_dev(tphip_plan *plan, const double *d_rates, const int32_t *d_nres,
+                                    const tphip_unequal_quartet_opts *opts, double *d_sites, void *stream);
+/* host-pointer twins: the library allocates its own buffers, as tphip_pi_tables does */
+int tphip_unequal_quartet_tables(tphip_plan *plan, const double *rates, const int32_t *nres,
+                                 const tphip_unequal_quartet_opts *opts, double *rows);
+int tphip_unequal_quartet_sites(tphip_plan *plan, const double *rates, const int32_t *nres,
+                                const tphip_unequal_quartet_opts *opts, double *sites);
+
+/* ------------------------------------------------------------------------------------------------
  * Parametric bootstrap of the site rates and the PI rows (an extension).  The site bootstrap above resamples columns with
  * their rates held fixed; this one asks how noisy the rates themselves are: every column is simulated down the plan's tree
  * under the locus' model at the column's own rate, with the observed pattern of missing cells, its rate is re-estimated by

@@ -9,6 +9,8 @@ Same positionals, same required/optional flags and defaults, same output directo
 --bootstrap / --bootstrap-seed / --bootstrap-level (site-bootstrap bands in a second file,
 phylogenetic-informativeness-bootstrap.sqlite; the other outputs stay byte for byte the same), --quartets (quartet signal
 and noise in another file of its own, phylogenetic-informativeness-quartets.sqlite; again nothing else changes),
+--unequal-quartets / --tree-quartets (the same for quartets with four tip lengths of their own, typed or read off the input
+tree's internodes, in phylogenetic-informativeness-unequal-quartets.sqlite),
 --parametric-bootstrap / --parametric-bootstrap-seed / --parametric-bootstrap-level (the rates re-estimated on simulated
 alignments: bands in phylogenetic-informativeness-parametric-bootstrap.sqlite, per-site moments in NAME.rates-bootstrap.json).
 
@@ -124,10 +126,25 @@ def get_args(argv=None):
                           "incorrectly or not at all (Townsend, Su & Tekle 2012) go into "
                           "phylogenetic-informativeness-quartets.sqlite.  With --site-rates it needs the loci's model: "
                           "--site-model jc|f81 or --exchangeabilities")
+    new.add_argument('--unequal-quartets', type=_unequal_quartets, default=None, metavar='Ta/Tb/Tc/Td:to[,...]',
+                     help="signal and noise of four-taxon trees ((a:Ta,b:Tb),(c:Tc,d:Td)) with four tip branches of their own "
+                          "and an internode of length to, in the tree's time units (floats; to > 0, tips >= 0; at most 256): "
+                          "per locus the expected numbers of signal sites and of noise sites for either wrong topology and the "
+                          "probabilities of ab|cd, ac|bd, ad|bc or no resolution (Su & Townsend 2015) go into "
+                          "phylogenetic-informativeness-unequal-quartets.sqlite.  The lengths are not held against the tree's "
+                          "depth: a lineage through the parent of a node can be nearly twice as long.  Under --site-rates the "
+                          "model rule of --quartets applies")
+    new.add_argument('--tree-quartets', default=False, action='store_true',
+                     help="the same for every internode of the input tree, each with the nearest tip of the four subtrees "
+                          "around it (rows node1, node2, ... in post-order, after any --unequal-quartets rows; the clades are "
+                          "listed in the file's table `clade`).  No depth check either: a lineage through the parent can be "
+                          "nearly twice the tree's depth")
     args = parser.parse_args(argv)
-    if args.quartets is not None and args.site_rates and args.site_model == 'locus' and args.exchangeabilities is None:
-        parser.error("--quartets needs the loci's substitution model, which --site-rates does not read: "
-                     "add --site-model jc, --site-model f81 or --exchangeabilities")
+    for flag, given in (('--quartets', args.quartets is not None), ('--unequal-quartets', args.unequal_quartets is not None),
+                        ('--tree-quartets', args.tree_quartets)):
+        if given and args.site_rates and args.site_model == 'locus' and args.exchangeabilities is None:
+            parser.error("{0} needs the loci's substitution model, which --site-rates does not read: "
+                         "add --site-model jc, --site-model f81 or --exchangeabilities".format(flag))
     if args.bootstrap == 0:
         for flag, value in (('--bootstrap-seed', args.bootstrap_seed), ('--bootstrap-level', args.bootstrap_level)):
             if value is not None:
@@ -167,7 +184,9 @@ def get_args(argv=None):
             parser.error("--parametric-bootstrap-level must be in (0, 1)")
     if args.site_model != 'locus':
         for flag, given in (('--exchangeabilities', args.exchangeabilities is not None), ('--subs-model', bool(args.subs_model)),
-                            ('--site-rates', args.site_rates and args.quartets is None)):   # (with --quartets: the model of that stage)
+                            # (with a quartet flag: the model of that stage)
+                            ('--site-rates', args.site_rates and args.quartets is None and args.unequal_quartets is None
+                             and not args.tree_quartets)):
             if given:
                 parser.error("--site-model {0} fixes the model: it cannot be combined with {1}".format(args.site_model, flag))
     eb_flags = (('--eb-categories', args.eb_categories), ('--eb-alpha', args.eb_alpha), ('--eb-alpha-bounds', args.eb_alpha_bounds))
@@ -220,6 +239,29 @@ def _quartets(string):
         out.append((item.strip(), tip, internode))
     if not 1 <= len(out) <= 256:
         raise argparse.ArgumentTypeError("--quartets takes 1..256 quartets")
+    return out
+
+
+def _unequal_quartets(string):
+    """Ta/Tb/Tc/Td:to[,...] -> [(label as typed, Ta, Tb, Tc, Td, to)]"""
+    out = []
+    for item in string.split(','):
+        try:
+            tips, b = item.split(':')
+            ta, tb, tc, td = (float(v) for v in tips.split('/'))
+            internode = float(b)
+        except Exception:
+            raise argparse.ArgumentTypeError("Cannot convert quartet %r to Ta/Tb/Tc/Td:to (five numbers)" % item)
+        if not np.all(np.isfinite([ta, tb, tc, td, internode])):
+            raise argparse.ArgumentTypeError("quartet %r: Ta, Tb, Tc, Td and to must be finite" % item)
+        if not internode > 0:
+            raise argparse.ArgumentTypeError("quartet %r: the internode length to must be positive" % item)
+        for name, tip in zip(("Ta", "Tb", "Tc", "Td"), (ta, tb, tc, td)):
+            if not tip >= 0:
+                raise argparse.ArgumentTypeError("quartet %r: the tip length %s must not be negative" % (item, name))
+        out.append((item.strip(), ta, tb, tc, td, internode))
+    if not 1 <= len(out) <= 256:
+        raise argparse.ArgumentTypeError("--unequal-quartets takes 1..256 quartets")
     return out
 
 
@@ -501,6 +543,29 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
         if rank == 0:
             db.write_quartet_db(os.path.join(args.output, 'phylogenetic-informativeness-quartets.sqlite'), files,
                                 all_rows.reshape(len(files), len(labels), 8), labels, lengths, models["model"])
+    if args.unequal_quartets or args.tree_quartets:
+        # (as --quartets; the typed rows first, then the input tree's internodes, read in the tree's original units)
+        eng = engine_mod
+        if eng is None:
+            from . import engine as eng
+        typed = args.unequal_quartets or []
+        of_tree = compute.tree_quartets(newick.read_tree(args.tree, args.tree_format)) if args.tree_quartets else []
+        labels = [q[0] for q in typed] + [q[0] for q in of_tree]
+        lengths = np.array([q[1:6] for q in typed] + [q[2:7] for q in of_tree], dtype=np.float64).reshape(-1, 5)
+        ids = list(tdist.shard_loci(len(files), rank, world))
+        if args.site_rates:
+            models = _site_rates_models(mine, args)
+        elif models is None:
+            models = dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)), model="gtr" if args.site_model == 'locus' else "f81")
+        rows = pipeline.unequal_quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent, blen,
+                                               leaf, T, args.device, lengths, model=models["model"])
+        # (a tree without an internode and nothing typed: no row to compute or gather, the file says so)
+        all_rows = (_gather_rows(rows.reshape(len(ids), 13 * len(labels)), len(files), rank, world, on_gpu) if labels
+                    else np.zeros((len(files), 0)))
+        if rank == 0:
+            db.write_unequal_quartet_db(os.path.join(args.output, 'phylogenetic-informativeness-unequal-quartets.sqlite'), files,
+                                        all_rows.reshape(len(files), len(labels), 13), labels, lengths, models["model"],
+                                        clades=[(q[0], q[1]) for q in of_tree])
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

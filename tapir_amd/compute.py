@@ -108,6 +108,53 @@ def correct_branch_lengths(tree_file, format, d=""):
     return depth, correction_factor, pth
 
 
+def tree_quartets(root):
+    """The quartets of the tree's internodes by the nearest-tip convention: for every internal edge
+    of the unrooted tree (a root with exactly two children is removed and its two edges joined) one row
+    (label, clade_leaf_names, Ta, Tb, Tc, Td, t_o): t_o the edge's length, (Ta, Tb) the two shortest lineages leaving its
+    clade-side end away from the edge, (Tc, Td) the two shortest leaving the other end, each pair ascending.  A lineage's
+    length is the distance from that end through one neighbour other than the edge to the nearest leaf in that direction.
+    Edges of length 0 are skipped.  Post-order of the clade-side end; labels node1, node2, ... in that order.  The tree is
+    read as it is: call it on the input tree, not on the one correct_tree rescaled."""
+    order = newick.postorder(root)
+    length = lambda n: n.length or 0.0   # noqa: E731
+    down = {}                            # distance to the nearest leaf below
+    for n in order:
+        down[id(n)] = min((length(c) + down[id(c)] for c in n.children), default=0.0)
+    joined = len(root.children) == 2
+    up = {}                              # distance to the nearest leaf through the parent edge
+    for n in reversed(order):            # parents before children
+        if n is root:
+            continue
+        p = n.parent
+        ways = [length(s) + down[id(s)] for s in p.children if s is not n]
+        if p is not root:
+            ways.append(up[id(p)])
+        up[id(n)] = length(n) + min(ways) if ways else float("inf")
+    out = []
+    for n in order:
+        if n is root or n.is_leaf():
+            continue
+        p = n.parent
+        near = sorted(length(c) + down[id(c)] for c in n.children)
+        if p is root and joined:
+            other = p.children[1]
+            if n is not p.children[0] or other.is_leaf():
+                continue                 # the joined edge is taken once, from the root's first child
+            t_o = length(n) + length(other)
+            far = sorted(length(c) + down[id(c)] for c in other.children)
+        else:
+            t_o = length(n)
+            far = [length(s) + down[id(s)] for s in p.children if s is not n]
+            if p is not root:
+                far.append(up[id(p)])
+            far.sort()
+        if t_o == 0.0 or len(near) < 2 or len(far) < 2:
+            continue
+        out.append(("node%d" % (len(out) + 1), [leaf.name for leaf in newick.leaves(n)], near[0], near[1], far[0], far[1], t_o))
+    return out
+
+
 def get_net_pi_for_periods(pi, times):
     """Sum across sites of the PI matrix at the requested times (tapir/compute.py:76-79).
     A time >= T raises IndexError exactly as numpy indexing does in the reference."""

@@ -1,0 +1,300 @@
+// unequal_quartet_kernels.hpp -- signal and noise of a four-taxon tree whose four tip branches differ, per site, their
+// per-locus sums and the probabilities that the locus resolves the internode, or one of the two wrong topologies
+// (Townsend, Su & Tekle 2012; Su & Townsend 2015).  Included by unequal_quartet_driver.hip only (a
+// __global__ definition must live in one translation unit).
+//
+// The quartet is ((a:Ta, b:Tb)u, (c:Tc, d:Td)v) with u-v of length t_o.  For a site of final rate r (finalize_rate) under
+// the locus' generator normalised to one substitution, A = P(r Ta), B = P(r Tb), C = P(r Tc), D = P(r Td), N = P(r t_o) with
+// P of transition_row.hpp.  Rooted at u (the model is reversible), with R_u[i][j] = sum_v N_uv C_vi D_vj and i != j:
+//   signal y  = sum_u pi_u sum_i A_ui B_ui sum_{j != i} R_u[j][j]      (pattern iijj, supports ab|cd)
+//   noise  x1 = sum_u pi_u sum_{i != j} A_ui B_uj R_u[i][j]            (pattern ijij, supports ac|bd)
+//   noise  x2 = sum_u pi_u sum_{i != j} A_ui B_uj R_u[j][i]            (pattern ijji, supports ad|bc)
+// Every sum is a sum of products of matrix entries: nothing of the form "total minus the rest".
+//
+// The arithmetic of a site is written with explicit fma() under contract(off): (y, x1, x2) is then a function of (model, r,
+// the five lengths) alone -- not of the kernel it is inlined into, nor of the quartet's position in the list -- which is
+// what the bit-identity contract of the rows rests on.  x2 walks the pairs (i, j) in x1's order and takes the term
+// (A_uj B_ui) R_u[i][j]: with Ta = Tb the two are then the same number, bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "gtr_model.hpp"
+#include "pi_rate.hpp"
+#include "transition_row.hpp"
+
+namespace tphip {
+
+constexpr int kUqBlock = 256;
+constexpr int kUqColsPerThread = 4;
+constexpr int kUqChunk = kUqBlock * kUqColsPerThread;   // the plan's PI chunks (pi_kernels.hpp: kPiChunk)
+static_assert(kUqChunk == 1024, "the plan's chunk_locus / chunk_index are cut for 1024 columns");
+constexpr int kUqBatch = 64;     // quartets per launch: their lengths travel as kernel arguments (no copy, no synchronisation)
+constexpr int kUqSums = 9;       // Y, X1, X2, Yy, X1x1, X2x2, YX1, YX2, X1X2
+constexpr int kUqRow = 13;       // + p_correct, p_ac, p_ad, p_polytomy
+constexpr int kUqReduceBlock = 64;
+
+struct UnequalQuartetBatch {
+    double tip[4][kUqBatch];     // Ta, Tb, Tc, Td
+    double internode[kUqBatch];
+};
+
+struct UnequalQuartetParams {
+    PiParams pi;                 // rates, cull and the chunk map; pi.partial is not used
+    const LocusModel* models;
+    int32_t f81;                 // the plan's models are F81: the closed form e I + (1 - e) Pi
+    int32_t n_q;                 // quartets of the whole call (row pitch of partial / sites)
+    int32_t q0, nq;              // this launch: quartets q0 .. q0 + nq - 1 = the entries 0 .. nq - 1 of the batch
+    double* partial;             // [nchunks][n_q][9]
+    double* sites;               // [3][n_q][ncols]
+    int64_t ncols;
+};
+
+__device__ __forceinline__ bool uquartet_live(double r) { return isfinite(r) && r != 0.0; }   // as nansum: NaN and 0 add exactly 0
+
+__device__ __forceinline__ double uquartet_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// (y, x1, x2) of one live site.  C and D are held whole (32 doubles); of A, B and N only what all rows of a matrix share
+// (transition_exps: three numbers each), and row u of each is made where u needs it.  Per u: n C (16 products), R_u (16
+// products + 48 fma), the three contributions.
+__device__ __forceinline__ void uquartet_signal_noise(const LocusModel& m, bool f81, double r, double ta, double tb, double tc,
+                                                      double td, double to, double& y, double& x1, double& x2) {
+#pragma clang fp contract(off)
+    double eA[3], eB[3], eN[3], e[3], C[16], D[16];
+    transition_exps(m, f81, transition_scale(m, r, ta), eA);
+    if (tb == ta) {                  // (wave-uniform; the rule on an ultrametric tree) the same three numbers, not made twice
+        eB[0] = eA[0]; eB[1] = eA[1]; eB[2] = eA[2];
+    } else {
+        transition_exps(m, f81, transition_scale(m, r, tb), eB);
+    }
+    transition_exps(m, f81, transition_scale(m, r, to), eN);
+    transition_exps(m, f81, transition_scale(m, r, tc), e);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) transition_row(m, f81, e, i, C + 4 * i);
+    transition_exps(m, f81, transition_scale(m, r, td), e);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) transition_row(m, f81, e, i, D + 4 * i);
+    double sy = 0.0, s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        double a[4], b[4], n[4], nC[16], R[16];
+        transition_row(m, f81, eA, u, a);
+        transition_row(m, f81, eB, u, b);
+        transition_row(m, f81, eN, u, n);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) nC[4 * v + i] = n[v] * C[4 * v + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double s = nC[i] * D[j];
+                s = fma(nC[4 + i], D[4 + j], s);
+                s = fma(nC[8 + i], D[8 + j], s);
+                s = fma(nC[12 + i], D[12 + j], s);
+                R[4 * i + j] = s;
+            }
+        }
+        // signal: sum_i (a_i b_i) (sum_{j != i} R_jj), the inner sums by three additions each
+        const double d0 = R[0], d1 = R[5], d2 = R[10], d3 = R[15];
+        double in = (a[0] * b[0]) * ((d1 + d2) + d3);
+        in = fma(a[1] * b[1], (d0 + d2) + d3, in);
+        in = fma(a[2] * b[2], (d0 + d1) + d3, in);
+        in = fma(a[3] * b[3], (d0 + d1) + d2, in);
+        sy = fma(m.pi[u], in, sy);
+        // noise: the twelve pairs i != j in row order; x2 takes the transposed tip product on the same entry of R
+        double i1 = 0.0, i2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (i == j) continue;
+                i1 = fma(a[i] * b[j], R[4 * i + j], i1);
+                i2 = fma(a[j] * b[i], R[4 * i + j], i2);
+            }
+        }
+        s1 = fma(m.pi[u], i1, s1);
+        s2 = fma(m.pi[u], i2, s2);
+    }
+    y = sy;
+    x1 = s1;
+    x2 = s2;
+}
+
+// One workgroup per 1024-column chunk of a locus, a thread four columns (column = base + j * 256 + thread, as
+// pi_partial_kernel).  The locus' model is wave-uniform: it is read through the scalar cache into SGPRs, once per wave.
+// Quartets go through one at a time; a thread's nine running sums of the quartet live in registers while it walks its four
+// columns (their rates wait in LDS, so that the walk is a loop -- one copy of the site arithmetic -- not four unrolled
+// ones).  The nine sums are then added over the wave by a butterfly and over the four waves in order: a fixed shape, no
+// atomics.  Static LDS: 8 KB of rates + 18 KB of wave sums.
+constexpr int kUqWavesPerSimd = 2;
+__global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_partial_kernel(UnequalQuartetParams P, UnequalQuartetBatch B) {
+    __shared__ double rate[kUqColsPerThread][kUqBlock];
+    __shared__ double red[kUqBatch * kUqSums][kUqBlock / 64];
+    const int chunk = blockIdx.x;
+    const int locus = P.pi.chunk_locus[chunk];
+    const int64_t lo = P.pi.locus_offsets[locus], hi = P.pi.locus_offsets[locus + 1];
+    const int64_t base = lo + (int64_t)P.pi.chunk_index[chunk] * kUqChunk;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const LocusModel& model = P.models[locus];
+#pragma unroll
+    for (int j = 0; j < kUqColsPerThread; ++j) {
+        const int64_t col = base + j * kUqBlock + threadIdx.x;
+        rate[j][threadIdx.x] = (col < hi) ? finalize_rate(P.pi, col) : 0.0;   // a thread reads back its own slots only
+    }
+    const bool f81 = P.f81 != 0;
+#pragma unroll 1
+    for (int q = 0; q < P.nq; ++q) {
+        const double ta = B.tip[0][q], tb = B.tip[1][q], tc = B.tip[2][q], td = B.tip[3][q], to = B.internode[q];
+        double s[kUqSums];
+#pragma unroll
+        for (int w = 0; w < kUqSums; ++w) s[w] = 0.0;
+#pragma unroll 1
+        for (int j = 0; j < kUqColsPerThread; ++j) {
+            const double r = rate[j][threadIdx.x];
+            if (!uquartet_live(r)) continue;
+            double y, x1, x2;
+            uquartet_signal_noise(model, f81, r, ta, tb, tc, td, to, y, x1, x2);
+            s[0] += y;
+            s[1] += x1;
+            s[2] += x2;
+            s[3] = fma(y, y, s[3]);
+            s[4] = fma(x1, x1, s[4]);
+            s[5] = fma(x2, x2, s[5]);
+            s[6] = fma(y, x1, s[6]);
+            s[7] = fma(y, x2, s[7]);
+            s[8] = fma(x1, x2, s[8]);
+        }
+#pragma unroll
+        for (int w = 0; w < kUqSums; ++w) {
+            const double v = uquartet_wave_sum(s[w]);
+            if (lane == 0) red[q * kUqSums + w][wave] = v;
+        }
+    }
+    __syncthreads();
+    double* out = P.partial + ((size_t)chunk * P.n_q + P.q0) * kUqSums;
+    for (int w = threadIdx.x; w < P.nq * kUqSums; w += kUqBlock) out[w] = ((red[w][0] + red[w][1]) + red[w][2]) + red[w][3];
+}
+
+// Dense per-site values: sites[0][q][col] = y, sites[1][q][col] = x1, sites[2][q][col] = x2; a thread is one column at a
+// time and walks the batch's quartets.  Culled and zero-rate columns get exactly 0.
+__global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_sites_kernel(UnequalQuartetParams P, UnequalQuartetBatch B) {
+    const int chunk = blockIdx.x;
+    const int locus = P.pi.chunk_locus[chunk];
+    const int64_t lo = P.pi.locus_offsets[locus], hi = P.pi.locus_offsets[locus + 1];
+    const int64_t base = lo + (int64_t)P.pi.chunk_index[chunk] * kUqChunk;
+    const LocusModel& model = P.models[locus];
+    const bool f81 = P.f81 != 0;
+    const size_t plane = (size_t)P.n_q * (size_t)P.ncols;
+#pragma unroll 1
+    for (int j = 0; j < kUqColsPerThread; ++j) {
+        const int64_t col = base + j * kUqBlock + threadIdx.x;
+        if (col >= hi) continue;
+        const double r = finalize_rate(P.pi, col);
+        const bool live = uquartet_live(r);
+#pragma unroll 1
+        for (int q = 0; q < P.nq; ++q) {
+            double y = 0.0, x1 = 0.0, x2 = 0.0;
+            if (live) uquartet_signal_noise(model, f81, r, B.tip[0][q], B.tip[1][q], B.tip[2][q], B.tip[3][q], B.internode[q], y, x1, x2);
+            double* o = P.sites + (size_t)(P.q0 + q) * P.ncols + col;
+            o[0] = y;
+            o[plane] = x1;
+            o[2 * plane] = x2;
+        }
+    }
+}
+
+// ---- resolution probabilities: bivariate normal with continuity correction ------------------------------------------
+// positive nodes and their weights of the 64-point Gauss-Legendre rule on [-1, 1] (the rule and constants of section 3.6)
+__device__ const double kUqGl64X[32] = {
+    0.024350292663424432509, 0.07299312178779903945, 0.12146281929612055447, 0.16964442042399281804,
+    0.21742364374000708415, 0.26468716220876741637, 0.31132287199021095616, 0.35722015833766811595,
+    0.4022701579639916037, 0.44636601725346408798, 0.48940314570705295748, 0.53127946401989454566,
+    0.57189564620263403428, 0.61115535517239325025, 0.64896547125465733986, 0.68523631305423324256,
+    0.71988185017161082685, 0.75281990726053189661, 0.78397235894334140761, 0.81326531512279755974,
+    0.84062929625258036275, 0.86599939815409281976, 0.88931544599511410585, 0.91052213707850280576,
+    0.92956917213193957582, 0.94641137485840281606, 0.96100879965205371892, 0.97332682778991096374,
+    0.98333625388462595693, 0.99101337147674432074, 0.99634011677195527935, 0.99930504173577213946};
+__device__ const double kUqGl64W[32] = {
+    0.048690957009139720383, 0.048575467441503426935, 0.04834476223480295717, 0.047999388596458307728,
+    0.047540165714830308662, 0.046968182816210017325, 0.046284796581314417296, 0.04549162792741814448,
+    0.04459055816375656306, 0.043583724529323453377, 0.042473515123653589007, 0.04126256324262352861,
+    0.039953741132720341387, 0.038550153178615629129, 0.03705512854024004604, 0.035472213256882383811,
+    0.033805161837141609392, 0.032057928354851553585, 0.030234657072402478868, 0.028339672614259483228,
+    0.026377469715054658672, 0.024352702568710873338, 0.022270173808383254159, 0.020134823153530209372,
+    0.017951715775697343085, 0.015726030476024719322, 0.013463047896718642598, 0.011168139460131128819,
+    0.008846759826363947723, 0.0065044579689783628561, 0.0041470332605624676353, 0.0017832807216964329473};
+
+// h != k: (h - k)^2 / (2 cos^2) + h k / (1 + sin) is (h^2 + k^2 - 2 h k sin) / (2 cos^2) without that numerator's
+// cancellation near theta = pi / 2
+__device__ __forceinline__ double uquartet_bvn_integrand(double h, double k, double theta) {
+    const double s = sin(theta);
+    if (h == k) return exp(-(k * k) / (1.0 + s));          // smooth up to rho = 1
+    const double c = cos(theta);
+    const double d = h - k;
+    return exp(-((d * d) / (2.0 * c * c) + (h * k) / (1.0 + s)));
+}
+
+// B(h, k, rho) = P(Z1 > h, Z2 > k) = Phi(-h) Phi(-k) + (1 / 2 pi) int_0^{asin rho} integrand d theta; rho already clamped
+__device__ __forceinline__ double uquartet_bvn_upper(double h, double k, double rho) {
+    const double half = 0.5 * asin(rho);
+    double sum = 0.0;
+    for (int i = 0; i < 32; ++i) {
+        const double d = half * kUqGl64X[i];
+        sum += kUqGl64W[i] * (uquartet_bvn_integrand(h, k, half - d) + uquartet_bvn_integrand(h, k, half + d));
+    }
+    const double tail = (0.5 * erfc(h * 0.70710678118654752440)) * (0.5 * erfc(k * 0.70710678118654752440));
+    return fmax(0.0, tail + half * sum * 0.15915494309189533577);   // 1 / (2 pi); rho < 0: the two terms cancel, never below 0
+}
+
+// The probability that W ends strictly ahead of O1 and of O2.  e / var: expectation and variance of the three counts,
+// w_o1, w_o2, o1_o2: the cross sums (Cov = -cross sum).  cap: the upper clamp of rho where h != k.
+__device__ __forceinline__ double uquartet_win(double eW, double eO1, double eO2, double varW, double varO1, double varO2,
+                                               double w_o1, double w_o2, double o1_o2, double cap) {
+    const double s1 = (varW + varO1) + 2.0 * w_o1;
+    const double s2 = (varW + varO2) + 2.0 * w_o2;
+    if (!(s1 > 0.0) || !(s2 > 0.0)) return 0.0;
+    const double h = (0.5 - (eW - eO1)) / sqrt(s1);
+    const double k = (0.5 - (eW - eO2)) / sqrt(s2);
+    double rho = ((varW + (w_o1 + w_o2)) - o1_o2) / sqrt(s1 * s2);
+    rho = fmin(1.0, fmax(-1.0, rho));
+    if (h != k) rho = fmin(cap, fmax(-0.999, rho));
+    return uquartet_bvn_upper(h, k, rho);
+}
+
+// One workgroup per locus: the nine sums of every quartet over the locus' chunks in ascending order, then the four
+// probabilities, a thread per quartet.  rows [L][n_q][13].
+__global__ __launch_bounds__(kUqReduceBlock) void uquartet_reduce_kernel(const double* __restrict__ partial,
+                                                                        const int64_t* __restrict__ locus_chunk_offsets, int32_t n_q,
+                                                                        double* __restrict__ rows) {
+    const int locus = blockIdx.x;
+    const int64_t c0 = locus_chunk_offsets[locus], c1 = locus_chunk_offsets[locus + 1];
+    const int Wp = n_q * kUqSums;
+    double* row = rows + (size_t)locus * n_q * kUqRow;
+    for (int w = threadIdx.x; w < Wp; w += kUqReduceBlock) {
+        double s = 0.0;
+        for (int64_t c = c0; c < c1; ++c) s += partial[(size_t)c * Wp + w];
+        row[(w / kUqSums) * kUqRow + (w % kUqSums)] = s;
+    }
+    __syncthreads();   // a quartet's nine sums were written by up to nine threads of this workgroup
+    for (int q = threadIdx.x; q < n_q; q += kUqReduceBlock) {
+        double* o = row + q * kUqRow;
+        const double Y = o[0], X1 = o[1], X2 = o[2], yx1 = o[6], yx2 = o[7], x1x2 = o[8];
+        const double vS = Y - o[3], v1 = X1 - o[4], v2 = X2 - o[5];
+        const double pc = uquartet_win(Y, X1, X2, vS, v1, v2, yx1, yx2, x1x2, 0.999);
+        const double p1 = X1 > 0.0 ? uquartet_win(X1, Y, X2, v1, vS, v2, yx1, x1x2, yx2, 0.99) : 0.0;
+        const double p2 = X2 > 0.0 ? uquartet_win(X2, Y, X1, v2, vS, v1, yx2, x1x2, yx1, 0.99) : 0.0;
+        o[9] = pc;
+        o[10] = p1;
+        o[11] = p2;
+        o[12] = fmax(0.0, ((1.0 - pc) - p1) - p2);
+    }
+}
+
+}  // namespace tphip

@@ -167,3 +167,44 @@ def write_quartet_db(db_name, names, rows, labels, quartets, model):
     conn.commit()
     c.close()
     conn.close()
+
+
+UNEQUAL_QUARTET_DDL = [
+    "CREATE TABLE loci (id INTEGER PRIMARY KEY AUTOINCREMENT, locus TEXT)",
+    "CREATE TABLE quartet (id INT, quartet TEXT, tip_a FLOAT, tip_b FLOAT, tip_c FLOAT, tip_d FLOAT, internode FLOAT, "
+    "signal FLOAT, noise_ac FLOAT, noise_ad FLOAT, p_correct FLOAT, p_ac FLOAT, p_ad FLOAT, p_polytomy FLOAT, "
+    "FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE clade (quartet TEXT, ntaxa INT, taxa TEXT)",
+    "CREATE TABLE meta (key TEXT PRIMARY KEY, value TEXT)",
+]
+
+
+def write_unequal_quartet_db(db_name, names, rows, labels, quartets, model, clades=()):
+    """phylogenetic-informativeness-unequal-quartets.sqlite, a third file of its own (every other output stays byte for byte
+    what it is without --unequal-quartets / --tree-quartets).  rows [L, n_q, 13] from pipeline.unequal_quartet_tables;
+    labels: the typed quartets "Ta/Tb/Tc/Td:to" as typed, then node1, node2, ... for the tree's; quartets [n_q, 5] their
+    values.  signal, noise_ac and noise_ad are the expected numbers of sites of the patterns iijj, ijij and ijji.  clades:
+    (label, leaf names) per tree quartet: the clade below the internode, comma-joined.  Loci get the ids 1..L in file order."""
+    import numpy as np
+    if os.path.exists(db_name):
+        os.remove(db_name)
+    conn = sqlite3.connect(db_name)
+    c = conn.cursor()
+    for stmt in UNEQUAL_QUARTET_DDL:
+        c.execute(stmt)
+    L, n_q = len(names), len(labels)
+    rows = np.asarray(rows, dtype=np.float64).reshape(L, n_q, 13)
+    quartets = np.asarray(quartets, dtype=np.float64).reshape(n_q, 5)
+    c.executemany("INSERT INTO loci(locus) VALUES (?)", [(locus_name(n),) for n in names])
+    keys = np.asarray([r[0] for r in c.execute("SELECT id FROM loci ORDER BY id").fetchall()], dtype=np.int64)
+    if L and n_q:
+        c.executemany("INSERT INTO quartet VALUES (?,?,?,?,?,?,?,?,?,?,?,?,?,?)",
+                      zip(np.repeat(keys, n_q).tolist(), list(labels) * L, *[np.tile(quartets[:, k], L).tolist() for k in range(5)],
+                          *[rows[:, :, k].reshape(-1).tolist() for k in (0, 1, 2, 9, 10, 11, 12)]))
+    c.executemany("INSERT INTO clade VALUES (?,?,?)", [(label, len(taxa), ",".join(taxa)) for label, taxa in clades])
+    c.executemany("INSERT INTO meta VALUES (?,?)", [("quartets", ",".join(labels)), ("model", str(model)),
+                                                    ("approximation", "bivariate normal with continuity correction"),
+                                                    ("tree_quartets", "nearest tip on each side of the internode")])
+    conn.commit()
+    c.close()
+    conn.close()

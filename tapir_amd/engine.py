@@ -58,6 +58,10 @@ class QuartetOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("tip", _vp), ("internode", _vp)]
 
 
+class UnequalQuartetOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("tips", _vp), ("internode", _vp)]
+
+
 class SimulateOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("replicate", _i32), ("seed", ctypes.c_uint64), ("locus_ids", _vp)]
 
@@ -134,6 +138,11 @@ SYMBOLS = [
     ("tphip_quartet_sites_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp, _vp]),
     ("tphip_quartet_tables", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp]),
     ("tphip_quartet_sites", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(QuartetOpts), _vp]),
+    ("tphip_unequal_quartet_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(UnequalQuartetOpts), ctypes.POINTER(ctypes.c_size_t)]),
+    ("tphip_unequal_quartet_tables_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(UnequalQuartetOpts), _vp, _vp, ctypes.c_size_t, _vp]),
+    ("tphip_unequal_quartet_sites_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(UnequalQuartetOpts), _vp, _vp]),
+    ("tphip_unequal_quartet_tables", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(UnequalQuartetOpts), _vp]),
+    ("tphip_unequal_quartet_sites", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(UnequalQuartetOpts), _vp]),
     ("tphip_simulate_columns_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp, _vp]),
     ("tphip_simulate_columns", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp]),
     ("tphip_parboot_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ParbootOpts), ctypes.POINTER(ctypes.c_size_t)]),
@@ -714,6 +723,59 @@ class Plan:
         """tphip_quartet_sites_dev on device tensors: d_sites [2, n_q, ncols]; enqueues, does not synchronise."""
         opts, keep = self._quartet_opts(quartets)
         _check(self._lib.tphip_quartet_sites_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
+
+    # ---- quartets with unequal tips (csrc/unequal_quartet_driver.hip) ----------------------------
+    @staticmethod
+    def _unequal_quartet_opts(quartets):
+        """quartets: [n_q, 5] rows (Ta, Tb, Tc, Td, t_o).  Returns the options and the arrays they point into (keep them alive)."""
+        q = _np(quartets, np.float64).reshape(-1, 5)
+        tips, internode = np.ascontiguousarray(q[:, :4]), np.ascontiguousarray(q[:, 4])
+        opts = UnequalQuartetOpts(struct_size=ctypes.sizeof(UnequalQuartetOpts), n_q=len(q), tips=tips.ctypes.data,
+                                  internode=internode.ctypes.data)
+        return opts, (tips, internode)
+
+    def unequal_quartet_workspace_bytes(self, quartets):
+        """bytes of device workspace for unequal_quartet_tables_dev with these quartets."""
+        opts, keep = self._unequal_quartet_opts(quartets)
+        n = ctypes.c_size_t()
+        _check(self._lib.tphip_unequal_quartet_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
+        return n.value
+
+    def unequal_quartet_tables(self, rates, nres, quartets):
+        """Signal and noise of the quartets ((a:Ta, b:Tb), (c:Tc, d:Td)) with internode t_o under the plan's models
+        (tphip_unequal_quartet_tables).  rates / nres as for pi_tables; quartets [n_q, 5] rows (Ta, Tb, Tc, Td, t_o) in the
+        tree's original time units.  Returns rows [L, n_q, 13]: the sums of y, x1, x2, y^2, x1^2, x2^2, y x1, y x2, x1 x2, then
+        p_correct, p_ac, p_ad, p_polytomy."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        nres = None if nres is None else _np(nres, np.int32)
+        opts, keep = self._unequal_quartet_opts(quartets)
+        rows = np.zeros((self.nloci, opts.n_q, 13))
+        _check(self._lib.tphip_unequal_quartet_tables(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), rows.ctypes.data))
+        return rows
+
+    def unequal_quartet_sites(self, rates, nres, quartets):
+        """The per-site values behind unequal_quartet_tables (tphip_unequal_quartet_sites): [3, n_q, ncols], signal y, then
+        the noise x1 (pattern ijij) and x2 (ijji); exactly 0 for a culled or zero-rate column."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        nres = None if nres is None else _np(nres, np.int32)
+        opts, keep = self._unequal_quartet_opts(quartets)
+        sites = np.zeros((3, opts.n_q, self.ncols))
+        _check(self._lib.tphip_unequal_quartet_sites(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), sites.ctypes.data))
+        return sites
+
+    def unequal_quartet_tables_dev(self, d_rates, d_nres, quartets, d_rows, d_ws, stream=0):
+        """tphip_unequal_quartet_tables_dev on device tensors (d_nres may be None): d_rows [L, n_q, 13]; enqueues, does not
+        synchronise."""
+        opts, keep = self._unequal_quartet_opts(quartets)
+        _check(self._lib.tphip_unequal_quartet_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_rows),
+                                                          _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
+
+    def unequal_quartet_sites_dev(self, d_rates, d_nres, quartets, d_sites, stream=0):
+        """tphip_unequal_quartet_sites_dev on device tensors: d_sites [3, n_q, ncols]; enqueues, does not synchronise."""
+        opts, keep = self._unequal_quartet_opts(quartets)
+        _check(self._lib.tphip_unequal_quartet_sites_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
 
     # ---- parametric bootstrap of site rates and PI rows (csrc/simulate_driver.hip) ---------------
     def _ids(self, locus_ids):

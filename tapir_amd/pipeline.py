@@ -910,6 +910,35 @@ def quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, 
         plan.close()
 
 
+def unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr"):
+    """Rows [L, n_q, 13] of quartets with unequal tips (the sums of y, x1, x2, y^2, x1^2, x2^2, y x1, y x2, x1 x2, then
+    p_correct, p_ac, p_ad, p_polytomy) for already-final rates, on a no-rounding plan exactly as
+    quartet_tables.  quartets: [n_q, 5] rows (Ta, Tb, Tc, Td, t_o) in the tree's original time units; a list longer than
+    the engine's 256 goes through in calls of at most 256.  A locus' rows depend on its rates, its model and the quartet
+    only, so neither the split nor the rank or the loci beside it change them."""
+    quartets = np.asarray(quartets, dtype=np.float64).reshape(-1, 5)
+    L = len(per_locus)
+    if L == 0 or len(quartets) == 0:
+        return np.zeros((L, len(quartets), 13))
+    if model not in ("gtr", "f81"):
+        raise PipelineError("unknown model %r" % (model,))
+    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
+    if model == "gtr":
+        exch = np.asarray(exch, dtype=np.float64)
+        exch = np.tile(exch, (L, 1)) if exch.ndim == 1 else exch.reshape(L, 6)
+    else:
+        exch = None
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
+    rates = np.concatenate(per_locus)
+    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, [], [], correction=1.0, threshold=0,
+                    round_decimals=-1, device=device, model=model)
+    try:
+        return np.concatenate([plan.unequal_quartet_tables(rates, None, quartets[q0:q0 + 256])
+                               for q0 in range(0, len(quartets), 256)], axis=1)
+    finally:
+        plan.close()
+
+
 def _tuples(names, per_locus, tables, T, times, intervals):
     n_t, n_i = len(times), len(intervals)
     out = []
