@@ -14,7 +14,11 @@ constexpr int kReserveShift = 16;     // the reserved fraction of a locus' easy 
 constexpr int kShareWeightShift = 10; // predicted evaluations per column of a class, in units of 2^-10 (the weighted scan stays exact)
 constexpr double kDefaultReserve = 0.15;  // shares by predicted work (SiteParams::share_work): this fraction of every locus' easy columns
                                           //   forms its reserved tail; TPHIP_SITE_RESERVE
-constexpr int kMixedLoci = 8;        // loci whose columns a wave of the mixed-loci mode carries at a time (site_rate_kernel.hpp)
+// the later shares' cut of the reserved tails (tail_shares.hpp): lane-fills per share in the three bands, and the fractions of
+// the tails that the first two take; TPHIP_SITE_TAIL_SHARES (chosen with tools/share_replay.py: profiles/r17_tail_share_sweep.txt)
+constexpr int kTailFillsBig = 5, kTailFillsMid = 3, kTailFillsSmall = 2;
+constexpr double kTailFracBig = 0.4, kTailFracMid = 0.3;
+constexpr int kMixedLoci = 8;       // loci whose columns a wave of the mixed-loci mode carries at a time (site_rate_kernel.hpp)
 constexpr int kMixedLdsHeader = kMixedLoci * 64 + 64 + 32;   // doubles: tip tables, 2^(j/64), segment table
 constexpr int kMixedColBits = 28;    // a work entry of that mode = column | locus-in-group << 28: batches below 2^28 columns
 constexpr int kSiteLdsHeader = 160;  // doubles of LDS before the stack: tip table [16][4] + model [32] + 2^(j/64) [64]

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "launch_constants.hpp"
+#include "tail_shares.hpp"
 #include "tphip.h"
 
 namespace tphip {
@@ -31,6 +32,11 @@ struct PlanKnobs {
     std::optional<char> site_spill, site_persistent, site_mixed, site_tail_order, site_share_work, compact_chunked, pi_split, dedup;
     std::optional<double> site_first_fraction, site_reserve;
     std::optional<std::pair<double, double>> site_class_weights;   // "slow,easy"; text that does not parse = not set
+    // "big,mid,small[,frac_big,frac_mid]": lane-fills per later share in the three bands of the reserved tails and the fractions
+    // of the tails that the first two bands take (tail_shares.hpp); "0" = later shares of equal column counts; text that
+    // holds neither = not set
+    struct TailSharesKnob { int big = 0, mid = 0, small = 0; double frac_big = -1.0, frac_mid = -1.0; };
+    std::optional<TailSharesKnob> site_tail_shares;
     std::optional<int> host_split;
     // stage 1 (locus_launch_plan.hpp): columns per thread of locus_value_kernel, 1 or 2 (text below 2 = 1); the eigenbasis value
     // kernel instead of it whenever the variable is set, whatever its text
@@ -41,7 +47,7 @@ struct PlanKnobs {
 constexpr const char* kPlanKnobNames[] = {
     "TPHIP_SITE_CHUNK", "TPHIP_SITE_SPILL", "TPHIP_SITE_PERSISTENT", "TPHIP_SITE_MIXED", "TPHIP_SITE_WAVES",
     "TPHIP_SITE_FIRST_FRACTION", "TPHIP_SITE_GRID_MULT", "TPHIP_SITE_TAIL_ORDER", "TPHIP_SITE_SHARE_WORK", "TPHIP_SITE_RESERVE",
-    "TPHIP_SITE_CLASS_WEIGHTS", "TPHIP_COMPACT_CHUNKED", "TPHIP_PI_SPLIT", "TPHIP_DEDUP", "TPHIP_HOST_SPLIT",
+    "TPHIP_SITE_CLASS_WEIGHTS", "TPHIP_SITE_TAIL_SHARES", "TPHIP_COMPACT_CHUNKED", "TPHIP_PI_SPLIT", "TPHIP_DEDUP", "TPHIP_HOST_SPLIT",
     "TPHIP_VALUE_COLS", "TPHIP_VALUE_EIGENBASIS"};
 
 // One knob from its text (an environment variable's value).  False: no knob of that name.
@@ -60,6 +66,12 @@ inline bool set_plan_knob(PlanKnobs* k, const char* name, const char* text) {
     else if (is("TPHIP_SITE_CLASS_WEIGHTS")) {
         double a = 0, b = 0;
         if (sscanf(text, "%lf,%lf", &a, &b) == 2) k->site_class_weights = std::make_pair(a, b);
+    }
+    else if (is("TPHIP_SITE_TAIL_SHARES")) {
+        PlanKnobs::TailSharesKnob t;
+        const int n = sscanf(text, "%d,%d,%d,%lf,%lf", &t.big, &t.mid, &t.small, &t.frac_big, &t.frac_mid);
+        if (n == 1 && t.big == 0) k->site_tail_shares = PlanKnobs::TailSharesKnob();
+        else if (n == 3 || n == 5) k->site_tail_shares = t;
     }
     else if (is("TPHIP_COMPACT_CHUNKED")) k->compact_chunked = text[0];
     else if (is("TPHIP_PI_SPLIT")) k->pi_split = text[0];
@@ -102,13 +114,21 @@ struct SiteLaunch {
     // easy columns go to a reserved tail that the later, small shares cut into equal column counts; the first round's shares
     // cut the rest into equal predicted work, a slow column weighing w_slow / 2^10 evaluations and an easy one w_easy / 2^10
     int32_t share_work = 0, reserve_q = 0, w_slow = 0, w_easy = 0;
+    // how the later shares cut the reserved tails (tail_shares.hpp; fills_big = 0: into equal column counts) and how many of
+    // them the longest tails this shape can have would need
+    TailShares tail_shares;
+    int64_t tail_share_bound = 0;
     int32_t compact_chunked = 0;   // long loci: the work list by the chunk-parallel count / scan / scatter kernels (pi_kernels.hpp)
     int32_t pi_split = 0;          // long loci: the PI partial sums by pi_net_kernel + pi_interval_kernel instead of pi_partial_kernel
 };
 
-// Workgroups of the site-rate launch
+// Workgroups of the site-rate launch.  Later shares in whole lane-fills: the resident waves and every later share that the
+// longest possible tails need.  decide_site_launch sizes the shares to fit waves x grid_mult; only shares spelled out by the
+// knob make the grid larger.  The workgroups that the real tails leave without a share are the last of the grid.
 inline int64_t site_grid(const SiteLaunch& s, int64_t n_site_chunks) {
-    return s.mixed ? s.waves : s.persistent ? (int64_t)s.waves * s.grid_mult : n_site_chunks;
+    if (s.mixed) return s.waves;
+    if (!s.persistent) return n_site_chunks;
+    return std::max((int64_t)s.waves * s.grid_mult, s.waves + s.tail_share_bound);
 }
 
 // Target slice length of the non-persistent mode (small batches) and of the eval diagnostic: needs no device, and the
@@ -236,6 +256,39 @@ SiteLaunch decide_site_launch(const SiteShape& shape, int num_cus, const PlanKno
         // without later shares there is nobody to take a reserved tail
         reserve = (s.share_work && s.grid_mult > 1) ? std::min(std::max(reserve, 0.0), 1.0) : 0.0;
         s.reserve_q = (int32_t)lround(reserve * (1 << kReserveShift));
+        // The later shares cut the concatenated tails in whole lane-fills, long shares first (tail_shares.hpp; DESIGN section
+        // 3.1): a share of n fills of easy columns issues about 2 n + 1 rounds, and a share that ends inside a fill pays for the
+        // whole fill.  The tails cannot be longer than the reserved fraction of all columns; when the shares below would
+        // not fit the grid for that length, all three grow by the same factor.  Batches that take later shares by the
+        // knobs alone (shares under 1500 columns: the tails are a few fills altogether) keep the equal column counts, as
+        // TPHIP_SITE_TAIL_SHARES=0 does everywhere; shares spelled out by the knob apply to tails of any length.
+        if (s.reserve_q > 0) {
+            const int64_t tails_max = (ncols * (int64_t)s.reserve_q) >> kReserveShift;
+            const int64_t room = (int64_t)s.waves * (s.grid_mult - 1);
+            const auto set = [&s](int big, int mid, int small, double fb, double fm) {
+                TailShares& t = s.tail_shares;
+                t.fills_small = std::max(1, std::min(small, 1 << 20));
+                t.fills_mid = std::max(t.fills_small, std::min(mid, 1 << 20));
+                t.fills_big = std::max(t.fills_mid, std::min(big, 1 << 20));
+                fb = std::min(std::max(fb, 0.0), 1.0);
+                fm = std::min(std::max(fm, 0.0), 1.0 - fb);
+                t.frac_big_q = (int32_t)lround(fb * (1 << kReserveShift));
+                t.frac_mid_q = std::min((int32_t)lround(fm * (1 << kReserveShift)), (1 << kReserveShift) - t.frac_big_q);
+            };
+            if (knobs.site_tail_shares) {
+                const PlanKnobs::TailSharesKnob& k = *knobs.site_tail_shares;
+                if (k.big > 0) set(k.big, k.mid, k.small, k.frac_big >= 0 ? k.frac_big : kTailFracBig, k.frac_mid >= 0 ? k.frac_mid : kTailFracMid);
+            } else if (uneven) {
+                for (int scale = 1;; ++scale) {
+                    set(kTailFillsBig * scale, kTailFillsMid * scale, kTailFillsSmall * scale, kTailFracBig, kTailFracMid);
+                    if (tail_share_bound(tails_max, s.tail_shares) <= room || scale >= (1 << 16)) break;
+                }
+                // real tails of less than a fill per later workgroup (R1: 57 site patterns per locus of 2048 columns, a tail
+                // of 7 columns) stay with the equal column counts: tail_shares.hpp
+                s.tail_shares.min_total = (int32_t)std::min<int64_t>(room * kSiteBlock, INT32_MAX);
+            }
+            if (s.tail_shares.fills_big > 0) s.tail_share_bound = tail_share_bound(tails_max, s.tail_shares);
+        }
     }
     // Long loci build the work list chunk-parallel (compact_count / scan / scatter kernels); TPHIP_COMPACT_CHUNKED=0/1 is the
     // A/B and test switch that forces either path on any shape.
@@ -319,7 +372,8 @@ inline WorkspaceLayout layout_workspace(const SiteShape& shape, const SiteLaunch
         w.dedup_on = take(sizeof(int32_t) * nloci);
     }
     if (s.lds_depth < shape.stack_depth) {
-        const size_t rows = (size_t)s.waves * (size_t)s.grid_mult * (size_t)(shape.stack_depth - s.lds_depth);
+        // one row per workgroup of the persistent grid (the only mode with the spill variant)
+        const size_t rows = (size_t)site_grid(s, 0) * (size_t)(shape.stack_depth - s.lds_depth);
         w.spill = take(rows * 12 * kSiteBlock * sizeof(double));
     }
     w.total = off + 256;

@@ -855,16 +855,23 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
             // Shares by predicted work.  Every locus' part of the list is [main part][reserved tail of easy columns]
             // (compact_kernel).  The first main_shares workgroups cut the concatenated main parts into equal predicted work:
             // the locus of a cut from the weighted prefix, the place inside the locus by interpolation on its columns.  The
-            // others cut the concatenated reserved tails into equal column counts: those columns are all easy, a share's lanes
-            // finish nearly in step and its drain is short.  g0 and g1 count columns of the main parts or of the tails
-            // (SiteParams::part_prefix), whichever this share walks.
+            // others cut the concatenated reserved tails: those columns are all easy, a share's lanes finish nearly in step
+            // and its drain is short.  The cuts are whole lane-fills, long shares first (tail_shares.hpp): the grid holds a
+            // workgroup for every share the longest possible tails would need, and those past the shares of the real tails --
+            // the last of the grid -- leave below with an empty range.  (tail_shares.fills_big = 0, or tails of less than a
+            // fill per later workgroup: equal column counts over all later workgroups.)  g0 and g1 count columns of the main parts or of the tails (SiteParams::part_prefix),
+            // whichever this share walks.
             const unsigned M = (unsigned)P.main_shares;
             if (blockIdx.x >= M) {
                 ++part_pre;
                 ++part_beg;
                 const int64_t ttotal = part_pre[2 * P.nloci];
-                g0 = (int64_t)(blockIdx.x - M) * ttotal / (nshares - M);
-                g1 = (int64_t)(blockIdx.x - M + 1) * ttotal / (nshares - M);
+                if (tail_shares_apply(ttotal, P.tail_shares)) {
+                    tail_share_range((int64_t)(blockIdx.x - M), ttotal, P.tail_shares, &g0, &g1);
+                } else {
+                    g0 = (int64_t)(blockIdx.x - M) * ttotal / (nshares - M);
+                    g1 = (int64_t)(blockIdx.x - M + 1) * ttotal / (nshares - M);
+                }
             } else {
                 const int64_t wtotal = P.work_wprefix[P.nloci];
                 auto main_cut = [&](unsigned b) -> int64_t {

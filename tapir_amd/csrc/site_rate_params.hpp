@@ -6,6 +6,7 @@
 #include <cstdint>
 #include "gtr_model.hpp"
 #include "launch_constants.hpp"   // kSiteBlock, the LDS headers, the launcher variants, ...
+#include "tail_shares.hpp"
 #include "tree_program.hpp"
 
 namespace tphip {
@@ -67,7 +68,8 @@ struct SiteParams {
     int32_t share_work = 0;        // persistent, one locus at a time: shares by predicted work.  compact_kernel put a fixed fraction of
                                    //   every locus' easy (unmarked) columns into a reserved tail of the locus' part of the list; the
                                    //   first `main_shares` workgroups cut the main parts into equal predicted work (work_wprefix), the
-                                   //   others cut the reserved tails into equal column counts (tail_prefix).  0: shares as above
+                                   //   others cut the reserved tails in whole lane-fills (tail_shares, below) or into equal column
+                                   //   counts.  0: shares as above
     int32_t main_shares = 0;
     const int64_t* work_wprefix = nullptr;   // [nloci+1] exclusive scan of the main parts' predicted work (scan_classes_kernel)
     const int64_t* part_prefix = nullptr;    // [nloci+1][2] exclusive scans of the column counts of the main parts / the reserved tails
@@ -84,6 +86,9 @@ struct SiteParams {
     unsigned long long* eval_counter;
     double* spill;                 // SPILL variant: [grid waves][stack_depth - lds_depth][12][64] parked partials beyond the LDS stack
     int32_t lds_depth;             // parked partials kept in LDS (= stack_depth unless the SPILL variant runs)
+    TailShares tail_shares;        // share_work: the later shares' cut of the reserved tails (tail_shares.hpp); fills_big = 0: equal
+                                   //   column counts over the gridDim.x - main_shares later workgroups.  (Last: the WORK
+                                   //   instantiations alone read it, and the other fields keep their places.)
 };
 
 // Slices a locus with `count` optimiser columns is cut into in the non-persistent mode: about chunk_cols each.

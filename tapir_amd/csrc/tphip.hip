@@ -622,6 +622,7 @@ static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_r
     S.first_fraction = (p->site.first_fraction > 0.0) ? p->site.first_fraction : 1.0 / (double)p->site.grid_mult;
     S.share_work = p->site.share_work;
     S.main_shares = (p->site.reserve_q > 0) ? p->site.waves : p->site.waves * p->site.grid_mult;
+    S.tail_shares = p->site.tail_shares;
     S.work_wprefix = (const int64_t*)((char*)ws + p->ws.work_wprefix); S.part_prefix = (const int64_t*)((char*)ws + p->ws.part_prefix);
     S.part_start = (const int64_t*)((char*)ws + p->ws.part_start);
     S.ncat = p->ncat; S.cat = p->d_cat.p;
