@@ -21,17 +21,6 @@ constexpr size_t kBsAlign = 256;
 constexpr size_t kBsPreferredCap = (size_t)1 << 30;   // like stage 1's chunks: about 1 GiB of workspace at most
 constexpr int32_t kBsMaxResampleReps = 1 << 20;
 
-PiParams bs_pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres) {
-    PiParams Q;
-    Q.rates = d_rates; Q.nres = d_nres; Q.locus_offsets = p->d_offsets.p;
-    Q.chunk_locus = nullptr; Q.chunk_index = nullptr;
-    Q.T = p->T; Q.intervals = p->d_intervals.p; Q.n_i = p->n_i; Q.integ_mode = p->integ_mode;
-    Q.correction = p->correction; Q.threshold = p->threshold;
-    Q.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
-    Q.partial = nullptr;
-    return Q;
-}
-
 inline int32_t bs_width(const tphip_plan* p) { return p->T + p->n_i; }
 inline size_t bs_pitch(int64_t cols) { return (size_t)((cols + 1) & ~(int64_t)1); }   // 16-bit counters per row: whole words
 inline size_t bs_integ_bytes(const tphip_plan* p, int64_t cols) { return align_up(sizeof(double) * (size_t)cols * (size_t)p->n_i, kBsAlign); }
@@ -187,7 +176,7 @@ int tphip_pi_resample_dev(tphip_plan* p, const double* d_rates, const int32_t* d
     hipStream_t st = (hipStream_t)stream;
     size_t usable = 0;
     char* base = ws ? bs_ws_base(ws, ws_bytes, &usable) : nullptr;
-    const PiParams Q = bs_pi_params(p, d_rates, d_nres);
+    const PiParams Q = plan_pi_params(p, d_rates, d_nres);
     // the workspace holds the per-site integrals only: consecutive loci as far as it reaches
     int64_t l0 = 0;
     while (l0 < p->nloci) {
@@ -231,7 +220,7 @@ int tphip_pi_bootstrap_dev(tphip_plan* p, const double* d_rates, const int32_t* 
     }
     base += bs_ids_bytes(p);
     usable -= bs_ids_bytes(p);
-    const PiParams Q = bs_pi_params(p, d_rates, d_nres);
+    const PiParams Q = plan_pi_params(p, d_rates, d_nres);
     SummaryParams S = bs_summary_params(B, Wb, o.level);
     int64_t l0 = 0;
     while (l0 < p->nloci) {

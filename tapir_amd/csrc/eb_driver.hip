@@ -195,16 +195,10 @@ int eb_setup(tphip_plan* p, const uint8_t* d_states, const tphip_eb_opts* o, con
     if (rc) return rc;
 
     SiteParams& S = E.S;
-    S = SiteParams{};
-    S.states = d_states; S.ncols_total = p->ncols; S.models = p->d_models.p;
-    S.ops = p->d_fused_ops.p; S.nops = (int32_t)p->prog.fused_ops.size();   // the packed tip words go with the fused-cherry stream
-    S.stack_depth = p->prog.stack_depth; S.chrono_length = p->prog.chrono_length;
-    S.locus_offsets = p->d_offsets.p; S.chunk_locus = p->d_site_chunk_locus.p; S.chunk_index = p->d_site_chunk_index.p;
-    S.chunk_cols = p->site.chunk_cols;
+    S = plan_site_params(p, d_states, true);   // the packed tip words go with the fused-cherry stream
     S.packed = B.packed; S.nwords = p->nwords;
     S.work_cols = o->use_patterns ? B.work_cols : nullptr;
     S.work_count = o->use_patterns ? B.work_count : nullptr;
-    S.nloci = p->nloci; S.first_fraction = 1.0; S.lds_depth = p->prog.stack_depth;
     E.ncat = o->ncat; E.cat_rate = W.cat_rate; E.cat_logw = W.cat_logw; E.log_scale = W.X.u; E.done = nullptr;
     return TPHIP_OK;
 }
@@ -212,8 +206,7 @@ int eb_setup(tphip_plan* p, const uint8_t* d_states, const tphip_eb_opts* o, con
 int launch_posterior(tphip_plan* p, const PosteriorParams& E, hipStream_t st) {
     if (p->n_site_chunks <= 0) return TPHIP_OK;
     const size_t lds = site_lds_bytes(p->prog.stack_depth);
-    const int variant = p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : kStreamWords;
-    HIP_TRY(launch_site_posterior_kernel(variant, p->model, dim3((unsigned)p->n_site_chunks), lds, st, E));
+    HIP_TRY(launch_site_posterior_kernel(site_variant(p->nwords), p->model, dim3((unsigned)p->n_site_chunks), lds, st, E));
     return TPHIP_OK;
 }
 

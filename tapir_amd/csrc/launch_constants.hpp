@@ -48,7 +48,7 @@ constexpr int kPiBlock = 256;
 constexpr int kPiColsPerThread = 4;
 constexpr int kPiChunk = kPiBlock * kPiColsPerThread;  // 1024 columns per workgroup
 
-// ---- site-pattern de-duplication (pattern_kernels.hpp) ----
+// ---- site-pattern de-duplication (dedup_kernels.hpp) ----
 enum : int32_t { DEDUP_AUTO = 0, DEDUP_OFF = 1, DEDUP_ON = 2 };
 // Batches below this many columns are not de-duplicated in automatic mode: they run in the latency-bound small-batch
 // modes of site_rate_kernel (a launch lasts as long as its slowest wave), where fewer columns hardly shorten the kernel and the four extra

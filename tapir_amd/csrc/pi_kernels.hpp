@@ -50,7 +50,7 @@ struct ClassifyParams {
     uint32_t* packed;             // [ceil(ntaxa/8)][ncols_total] out: 8 four-bit masks per word, program tip order
     double start_scale;           // 1: start at the parsimony rate; 0: at HyPhy's siteRate = 1 (bf:1050), TPHIP_START_*
     uint64_t* hash;               // [ncols_total] out (may be null): hash of the column's packed words, for the
-                                  // per-pattern de-duplication of the site-rate stage (pattern_kernels.hpp)
+                                  // per-pattern de-duplication of the site-rate stage (dedup_kernels.hpp)
 };
 
 // The step table through the constant address space: classify_kernel also stores, so through a plain pointer the

@@ -18,17 +18,6 @@ namespace {
 
 constexpr int32_t kQtMaxQuartets = 256;
 
-PiParams qt_pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres) {
-    PiParams Q;
-    Q.rates = d_rates; Q.nres = d_nres; Q.locus_offsets = p->d_offsets.p;
-    Q.chunk_locus = p->d_pi_chunk_locus.p; Q.chunk_index = p->d_pi_chunk_index.p;
-    Q.T = p->T; Q.intervals = p->d_intervals.p; Q.n_i = p->n_i; Q.integ_mode = p->integ_mode;
-    Q.correction = p->correction; Q.threshold = p->threshold;
-    Q.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
-    Q.partial = nullptr;
-    return Q;
-}
-
 int qt_read_opts(const tphip_quartet_opts* o, int32_t* n_q) {
     if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_quartet_opts");
     if (o->struct_size < offsetof(tphip_quartet_opts, internode) + sizeof(const double*))
@@ -69,7 +58,7 @@ int qt_launch_batches(const tphip_plan* p, QuartetParams P, const tphip_quartet_
 
 QuartetParams qt_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres, int32_t n_q) {
     QuartetParams P;
-    P.pi = qt_pi_params(p, d_rates, d_nres);
+    P.pi = plan_pi_params(p, d_rates, d_nres);
     P.models = p->d_models.p;
     P.f81 = p->model == TPHIP_MODEL_F81 ? 1 : 0;
     P.n_q = n_q; P.q0 = 0; P.nq = 0;

@@ -244,12 +244,7 @@ int tphip_pi_parametric_bootstrap_dev(tphip_plan* p, const double* d_rates, cons
     double* tables = (double*)(base + L.tables);
     double* rows = d_rows ? d_rows : (double*)(base + L.rows);
     MomentParams M;
-    M.pi.rates = rate; M.pi.nres = nres; M.pi.locus_offsets = p->d_offsets.p;
-    M.pi.chunk_locus = nullptr; M.pi.chunk_index = nullptr;
-    M.pi.T = p->T; M.pi.intervals = p->d_intervals.p; M.pi.n_i = p->n_i; M.pi.integ_mode = p->integ_mode;
-    M.pi.correction = p->correction; M.pi.threshold = p->threshold;
-    M.pi.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
-    M.pi.partial = nullptr;
+    M.pi = plan_pi_params(p, rate, nres);
     M.ncols = p->ncols; M.B = B;
     M.mean = (double*)(base + L.mean); M.m2 = (double*)(base + L.m2);
     M.out_mean = d_rate_mean; M.out_sd = d_rate_sd;

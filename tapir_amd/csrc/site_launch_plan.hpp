@@ -1,8 +1,8 @@
 // site_launch_plan.hpp -- how the site-rate stage of a plan will run, decided on the host from a handful of numbers: the
 // batch shape, the tree's word count and stack depth, the CU count, two or three occupancy figures and the tuning knobs.
-// Plain integer and floating-point arithmetic with no HIP header: tphip.hip calls it from tphip_plan_create, and
-// tests/native/site_launch_dump.cpp compiles it with g++ so that every decision is checked without a GPU
-// (tests/test_site_launch.py).
+// Plain integer and floating-point arithmetic with no HIP header: tphip.hip calls it from tphip_plan_create, site_driver.hip
+// takes every launch's arguments from it, and tests/native/site_launch_dump.cpp compiles it with g++ so that every decision
+// is checked without a GPU (tests/test_site_launch.py).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -96,7 +96,7 @@ struct SiteShape {
     int32_t T = 0, n_i = 0;
 };
 
-// How launch_site_rates runs a plan's site-rate stage.
+// How launch_site_rates (site_driver.hip) runs a plan's site-rate stage.
 struct SiteLaunch {
     int32_t start_rule = 0;   // TPHIP_START_PARSIMONY or _REFERENCE (AUTO resolved)
     int32_t dedup_mode = 0;   // DEDUP_* (launch_constants.hpp)
@@ -131,6 +131,43 @@ inline int64_t site_grid(const SiteLaunch& s, int64_t n_site_chunks) {
     return std::max((int64_t)s.waves * s.grid_mult, s.waves + s.tail_share_bound);
 }
 
+// The launcher variant by the tree's packed tip words alone: the words in registers (<= 16 / <= 64 tips) or streamed one word
+// ahead (more than 64 tips).  The spill and the mixed-loci variants build on it (site_kernel_args).
+inline int site_variant(int32_t nwords) { return nwords <= 2 ? 2 : nwords <= 8 ? 8 : kStreamWords; }
+
+// What a site_rate_kernel launch takes from the plan's SiteLaunch besides pointers: the launcher's arguments and the
+// scheduling members of SiteParams (launch_site_rates in site_driver.hip).
+struct SiteKernelArgs {
+    int variant = 0;          // launch_site_rate_kernel's: site_variant, the spill variant of the streamed words, or kMixedVariant +
+    size_t lds_bytes = 0;
+    int64_t grid = 0;
+    int32_t persistent = 0, first_round = 0, tail_order = 0, share_work = 0, main_shares = 0;   // SiteParams members of these names
+    double first_fraction = 1.0;
+    bool spill = false;        // the deepest parked partials go to the workspace's scratch rows (SiteParams::spill)
+    bool second_list = false;  // the kernel gets the second work list (SiteParams::work_cols2): the layout has it whenever !persistent
+};
+
+inline SiteKernelArgs site_kernel_args(const SiteLaunch& s, int32_t nwords, int32_t stack_depth, int64_t n_site_chunks) {
+    SiteKernelArgs a;
+    a.spill = s.lds_depth < stack_depth;
+    a.second_list = !s.persistent;
+    a.persistent = (s.persistent || s.mixed) ? 1 : 0;   // the mixed-loci variants are launched as persistent, with equal shares
+    a.first_round = s.waves;
+    a.tail_order = (s.persistent && !s.mixed && s.tail_order) ? 1 : 0;
+    a.first_fraction = (s.first_fraction > 0.0) ? s.first_fraction : 1.0 / (double)s.grid_mult;
+    a.share_work = s.share_work;
+    a.main_shares = (s.reserve_q > 0) ? s.waves : s.waves * s.grid_mult;
+    a.grid = site_grid(s, n_site_chunks);
+    a.variant = (a.spill && nwords > 8) ? kStreamWordsSpill : site_variant(nwords);
+    a.lds_bytes = site_lds_bytes(s.lds_depth);   // (lds_depth = the stack depth unless the spill variant runs)
+    if (s.mixed) {   // equal shares: first_round = grid
+        a.first_fraction = 1.0;
+        a.variant += kMixedVariant;
+        a.lds_bytes = mixed_lds_bytes(stack_depth);
+    }
+    return a;
+}
+
 // Target slice length of the non-persistent mode (small batches) and of the eval diagnostic: needs no device, and the
 // chunk tables want it before anything else is decided.
 inline int32_t site_chunk_cols(const PlanKnobs& knobs) {
@@ -153,7 +190,7 @@ SiteLaunch decide_site_launch(const SiteShape& shape, int num_cus, const PlanKno
                        : shape.start_rule;
     s.chunk_cols = site_chunk_cols(knobs);
     // persistent grid: exactly the waves the device keeps resident for this LDS footprint
-    int per_cu = occupancy(nwords <= 2 ? 2 : nwords <= 8 ? 8 : kStreamWords, site_lds_bytes(stack_depth));
+    int per_cu = occupancy(site_variant(nwords), site_lds_bytes(stack_depth));
     if (per_cu < 1) per_cu = 1;
     s.waves = per_cu * num_cus;
     // Deep trees (256 taxa: 4 parked partials = 24 KB per wave) are capped at 6 waves per CU by the LDS stack, not by
@@ -192,7 +229,7 @@ SiteLaunch decide_site_launch(const SiteShape& shape, int num_cus, const PlanKno
         const size_t lds3 = mixed_lds_bytes(stack_depth);
         const int64_t simds = 4 * (int64_t)num_cus;
         const double est_rounds = (double)ncols * (s.start_rule == TPHIP_START_REFERENCE ? 2.2 : 1.4) / (double)(kSiteBlock * simds);
-        if (lds3 > 160 * 1024 || (per3 = occupancy(kMixedVariant + (nwords <= 2 ? 2 : 8), lds3)) < 1) s.mixed = 0;
+        if (lds3 > 160 * 1024 || (per3 = occupancy(kMixedVariant + site_variant(nwords), lds3)) < 1) s.mixed = 0;
         // a batch that wants two waves per SIMD on a tree whose tables leave room for six per CU (64 taxa: 23.3 KB of LDS
         // per wave) stays with the slices: 1900 loci x 1000 x 64, 3.36 ms in slices, 4.10 with 1024 mixed waves
         else if (est_rounds >= 28.0 && per3 < 8 && !knobs.site_mixed) s.mixed = 0;

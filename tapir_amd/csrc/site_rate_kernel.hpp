@@ -834,7 +834,7 @@ __global__ __launch_bounds__(kSiteBlock, TPHIP_SITE_MIN_WAVES) void site_rate_ke
         const int64_t total = P.work_prefix[P.nloci];
         // MIXED: one wave per SIMD or two is decided here, where the length of the work list is known (after classification
         // and de-duplication): a short list ends with the wave that carries its slowest column, and a second wave on that
-        // wave's SIMD makes each of its rounds longer (tphip.hip, where the threshold is set)
+        // wave's SIMD makes each of its rounds longer (site_launch_plan.hpp, where the threshold is set)
         unsigned nshares = gridDim.x;
         if constexpr (MIXED) {
             if (total < P.mixed_switch_cols && nshares > (unsigned)P.mixed_few_waves) nshares = (unsigned)P.mixed_few_waves;

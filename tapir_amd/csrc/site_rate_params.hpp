@@ -1,6 +1,7 @@
 // site_rate_params.hpp -- launch parameters and constants of the site-rate kernels, shared by the two translation
 // units of libtphip.so: site_rate_launch.hip (compiles site_rate_kernel.hpp, the only code built with
-// -structurizecfg-skip-uniform-regions) and tphip.hip (everything else, built without that flag).
+// -structurizecfg-skip-uniform-regions) and site_driver.hip (the stage-2 launches, built without that flag, as everything else is);
+// eb_driver.hip fills a SiteParams too (plan_site_params in tphip_internal.hpp is the common part).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

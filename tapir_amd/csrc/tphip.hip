@@ -1,27 +1,18 @@
-// tphip.hip -- C ABI (include/tphip.h) over the gfx950 kernels.  Host side only does validation, the
-// one-off tree compilation, table uploads and kernel launches; there is no CPU compute path.
-// (The stage-1 likelihood and gradient entry points are in locus_driver.hip.)
+// tphip.hip -- the plan behind the C ABI (include/tphip.h): validation, the one-off tree compilation and table uploads of
+// tphip_plan_create, the accessors and the per-locus models, and the host-pointer entry points with their pipeline of locus
+// groups.  There is no CPU compute path.  The device launches are in the drivers: stage 2 in site_driver.hip (called from here
+// through launch_site_rates / launch_pi_tables), the column compression in pattern_driver.hip, stage 1 in locus_driver.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "gtr_model.hpp"
 #include "gtr_setup_kernel.hpp"
-#include "locus_grad2_params.hpp"
-#include "locus_value_params.hpp"
-#include "pattern_kernels.hpp"
-#include <hipcub/hipcub.hpp>
-#include "pi_kernels.hpp"
-#include "site_rate_params.hpp"
-#include "tphip.h"
-#include "tree_program.hpp"
 #include "tphip_internal.hpp"
 
 using namespace tphip;
@@ -92,9 +83,14 @@ static tphip_saved_desc* save_desc(const tphip_plan_desc* d) {
 // for the other translation units of the library (stage1_driver.hip)
 const tphip_plan_desc* tphip_internal_saved_desc(const tphip_plan* p) { return (p && p->saved) ? &p->saved->d : nullptr; }
 
-static void free_parts(tphip_plan* p) {
+// the locus groups of the host-pointer pipeline (make_parts): gone with the plan, and rebuilt on next use after its models changed
+static void drop_parts(tphip_plan* p) {
     for (tphip_plan* q : p->parts) (void)tphip_plan_destroy(q);
     p->parts.clear();
+}
+
+static void free_parts(tphip_plan* p) {
+    drop_parts(p);
     delete p->saved;
     p->saved = nullptr;
 }
@@ -153,8 +149,7 @@ static int make_parts(tphip_plan* p) {
         tphip_plan* q = nullptr;
         const int rc = tphip_plan_create(&d, &q);
         if (rc) {   // whatever stops a group's plan: run the batch whole (the plain path reports real errors itself)
-            for (tphip_plan* r : p->parts) (void)tphip_plan_destroy(r);
-            p->parts.clear();
+            drop_parts(p);
             p->host_split = 1;
             return TPHIP_OK;
         }
@@ -440,429 +435,6 @@ int tphip_plan_get_models(const tphip_plan* p, double* lam, double* U, double* U
     return TPHIP_OK;
 }
 
-int tphip_profile_enable(tphip_plan* p, int32_t on) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    HIP_TRY(hipSetDevice(p->device));
-    if (on && p->ev.empty()) {
-        p->ev.resize(4 * kProfileRing);
-        for (auto& e : p->ev) HIP_TRY(hipEventCreate(&e));
-    }
-    p->profile = on != 0;
-    return TPHIP_OK;
-}
-
-static int profile_drain(tphip_plan* p) {
-    for (int s = 0; s < p->ev_used; ++s) {
-        float ms = 0;
-        HIP_TRY(hipEventSynchronize(p->ev[4 * s + 1]));
-        HIP_TRY(hipEventElapsedTime(&ms, p->ev[4 * s + 0], p->ev[4 * s + 1]));
-        p->acc_site_ms += ms;
-        HIP_TRY(hipEventSynchronize(p->ev[4 * s + 3]));
-        HIP_TRY(hipEventElapsedTime(&ms, p->ev[4 * s + 2], p->ev[4 * s + 3]));
-        p->acc_pi_ms += ms;
-        ++p->acc_launches;
-    }
-    p->ev_used = 0;
-    return TPHIP_OK;
-}
-
-int tphip_profile_read(tphip_plan* p, double* site_ms, double* pi_ms, int64_t* launches, int32_t reset) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc = profile_drain(p);
-    if (rc) return rc;
-    if (site_ms) *site_ms = p->acc_site_ms;
-    if (pi_ms) *pi_ms = p->acc_pi_ms;
-    if (launches) *launches = p->acc_launches;
-    if (reset) { p->acc_site_ms = p->acc_pi_ms = 0; p->acc_launches = 0; }
-    return TPHIP_OK;
-}
-
-int tphip_last_eval_count(tphip_plan* p, int64_t* evals) {
-    if (!p || !evals) return fail(TPHIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    unsigned long long v = 0;
-    if (p->last_run_in_parts) {   // the last site-rate launch was a host-pointer pipeline of locus groups: their sum
-        for (tphip_plan* q : p->parts) {
-            unsigned long long w = 0;
-            HIP_TRY(hipMemcpy(&w, q->d_evals.p, sizeof w, hipMemcpyDeviceToHost));
-            v += w;
-        }
-    } else {
-        HIP_TRY(hipMemcpy(&v, p->d_evals.p, sizeof v, hipMemcpyDeviceToHost));
-        if (getenv("TPHIP_SITE_TRACE_ROUNDS")) {   // meaningful in a -DTPHIP_SITE_TRACE_ROUNDS build only
-            unsigned long long c[8];
-            HIP_TRY(hipMemcpy(c, p->d_evals.p, sizeof c, hipMemcpyDeviceToHost));
-            if (c[5]) fprintf(stderr, "site_rate_kernel: %llu waves with work, evaluations %llu, rounds mean %.1f max %llu (lane use %.1f %%), wave time mean %.1f us max %.1f us\n",
-                              c[5], c[0], (double)c[1] / c[5], c[2], 100.0 * c[0] / (64.0 * c[1]), 0.01 * c[3] / c[5], 0.01 * c[4]);
-        }
-    }
-    *evals = (int64_t)v;
-    return TPHIP_OK;
-}
-
-int tphip_last_round_count(tphip_plan* p, int64_t* rounds) {
-    if (!p || !rounds) return fail(TPHIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    unsigned long long v = 0;
-    if (p->last_run_in_parts) {
-        for (tphip_plan* q : p->parts) {
-            unsigned long long w = 0;
-            HIP_TRY(hipMemcpy(&w, q->d_evals.p + 1, sizeof w, hipMemcpyDeviceToHost));
-            v += w;
-        }
-    } else {
-        HIP_TRY(hipMemcpy(&v, p->d_evals.p + 1, sizeof v, hipMemcpyDeviceToHost));
-    }
-    *rounds = (int64_t)v;
-    return TPHIP_OK;
-}
-
-// ---- launches ------------------------------------------------------------------------------------
-
-static PiParams pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres, void* ws);
-
-// The work list of long loci by the chunk-parallel kernels (pi_kernels.hpp).  work_class != null: with the class counts and
-// the reserved tails of the hand-out by predicted work (compact_classes_kernel's list), else compact_kernel's plain list.
-static void launch_compact_chunked(tphip_plan* p, const uint8_t* d_flag, const double* d_lnl, int32_t* work_cols, int32_t* work_count,
-                                  int32_t* work_class, void* ws, hipStream_t st) {
-    int2* cnt = (int2*)((char*)ws + p->ws.chunk_cnt);
-    const dim3 chunks((unsigned)p->n_pi_chunks), loci((unsigned)p->nloci), block(kCompactChunkBlock);
-    if (work_class) {
-        compact_count_kernel<true><<<chunks, block, 0, st>>>(d_flag, d_lnl, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt);
-        compact_scan_kernel<true><<<loci, block, 0, st>>>(p->d_locus_pichunk_offsets.p, cnt, work_count, work_class);
-        compact_scatter_kernel<true><<<chunks, block, 0, st>>>(d_flag, d_lnl, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt,
-                                                               work_count, work_class, p->site.reserve_q, work_cols);
-    } else {
-        compact_count_kernel<false><<<chunks, block, 0, st>>>(d_flag, nullptr, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt);
-        compact_scan_kernel<false><<<loci, block, 0, st>>>(p->d_locus_pichunk_offsets.p, cnt, work_count, nullptr);
-        compact_scatter_kernel<false><<<chunks, block, 0, st>>>(d_flag, nullptr, p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p, cnt,
-                                                                work_count, nullptr, 0, work_cols);
-    }
-}
-
-static int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_rate, double* d_subst, double* d_lnl,
-                             uint8_t* d_flag, int32_t* d_nres, void* ws, hipStream_t st, int slot) {
-    p->last_run_in_parts = false;
-    int32_t* work_cols = (int32_t*)((char*)ws + p->ws.work_cols);
-    int32_t* work_count = (int32_t*)((char*)ws + p->ws.work_count);
-    ClassifyParams C;
-    C.states = d_states; C.ncols_total = p->ncols; C.ntaxa = p->ntaxa; C.models = p->d_models.p;
-    C.locus_offsets = p->d_offsets.p; C.chunk_locus = p->d_pi_chunk_locus.p; C.chunk_index = p->d_pi_chunk_index.p;
-    C.rate = d_rate; C.subst = d_subst; C.lnl = d_lnl; C.flag = d_flag; C.nres = d_nres;
-    C.chrono_length = p->prog.chrono_length;
-    C.steps = (const int2*)p->d_cls_steps.p; C.tail_pops = p->prog.cls_tail_pops; C.max_pops = p->prog.cls_max_pops;
-    C.packed = (uint32_t*)((char*)ws + p->ws.packed);
-    C.start_scale = (p->site.start_rule == TPHIP_START_REFERENCE) ? 0.0 : 1.0;
-    const bool dedup = p->site.dedup_mode != DEDUP_OFF && p->n_pi_chunks > 0;
-    C.hash = dedup ? (uint64_t*)((char*)ws + p->ws.hash) : nullptr;
-    DedupParams D;
-    if (dedup) {
-        D.locus_offsets = p->d_offsets.p; D.chunk_locus = p->d_pi_chunk_locus.p; D.chunk_index = p->d_pi_chunk_index.p;
-        D.hash = C.hash; D.packed = C.packed; D.nwords = p->nwords; D.ncols_total = p->ncols; D.flag = d_flag;
-        D.dup_of = (int32_t*)((char*)ws + p->ws.dup_of);
-        D.tab_key = (unsigned long long*)((char*)ws + p->ws.tab_key); D.tab_val = (int32_t*)((char*)ws + p->ws.tab_val);
-        D.on = (int32_t*)((char*)ws + p->ws.dedup_on); D.mode = p->site.dedup_mode;
-        D.rate = d_rate; D.subst = d_subst; D.lnl = d_lnl;
-    }
-    if (p->n_pi_chunks > 0) {
-        classify_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(kPiBlock), 0, st>>>(C);
-        if (dedup) {   // one rate per unique site pattern (bf:1033-1044); loci that hardly repeat a column skip it
-            if (p->max_locus_cols > 2048) dedup_estimate_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(D);
-            else dedup_estimate_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(D);
-            dedup_insert_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
-            dedup_resolve_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
-        }
-        if (p->site.share_work) {
-            // shares by predicted work: the list with class counts and reserved tails, and their scans (compact_classes_kernel
-            // reads the marks, 8 more bytes per work column in its chain of barriers, and appends the tails: C3 47 -> 100 us;
-            // long loci take the chunk-parallel kernels instead: 40 us)
-            int32_t* work_class = (int32_t*)((char*)ws + p->ws.work_class);
-            if (p->site.compact_chunked) {
-                launch_compact_chunked(p, d_flag, d_lnl, work_cols, work_count, work_class, ws, st);
-            } else {
-                int32_t* scratch = p->site.reserve_q > 0 ? (int32_t*)((char*)ws + p->ws.work_cols2) : nullptr;
-                if (p->max_locus_cols > 2048) compact_classes_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site.reserve_q, scratch, work_class);
-                else compact_classes_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count, d_lnl, p->site.reserve_q, scratch, work_class);
-            }
-            ScanClasses SC;
-            SC.cls = work_class; SC.reserve_q = p->site.reserve_q; SC.w_slow = p->site.w_slow; SC.w_easy = p->site.w_easy;
-            SC.locus_offsets = p->d_offsets.p;
-            SC.wprefix = (int64_t*)((char*)ws + p->ws.work_wprefix); SC.part_prefix = (int64_t*)((char*)ws + p->ws.part_prefix);
-            SC.part_start = (int64_t*)((char*)ws + p->ws.part_start);
-            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site.chunk_cols, (int64_t*)((char*)ws + p->ws.work_prefix),
-                                              (int64_t*)((char*)ws + p->ws.slice_prefix), &SC));
-        } else {
-            if (p->site.compact_chunked) launch_compact_chunked(p, d_flag, nullptr, work_cols, work_count, nullptr, ws, st);
-            else if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
-            else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(d_flag, p->d_offsets.p, work_cols, work_count);
-            HIP_TRY(launch_scan_counts_kernel(st, work_count, p->nloci, p->site.chunk_cols, (int64_t*)((char*)ws + p->ws.work_prefix),
-                                              (int64_t*)((char*)ws + p->ws.slice_prefix), nullptr));
-        }
-    }
-    HIP_TRY(hipMemsetAsync(p->d_evals.p, 0, 8 * sizeof(unsigned long long), st));
-    SiteParams S;
-    S.states = d_states; S.ncols_total = p->ncols; S.models = p->d_models.p; S.ops = p->d_ops.p;
-    S.nops = (int32_t)p->prog.ops.size(); S.stack_depth = p->prog.stack_depth; S.chrono_length = p->prog.chrono_length;
-    S.locus_offsets = p->d_offsets.p; S.chunk_locus = p->d_site_chunk_locus.p; S.chunk_index = p->d_site_chunk_index.p;
-    S.chunk_cols = p->site.chunk_cols;
-    S.packed = (const uint32_t*)((char*)ws + p->ws.packed); S.nwords = p->nwords;
-    S.work_cols = work_cols; S.work_count = work_count;
-    S.work_cols2 = (!p->site.persistent && p->ws.work_cols2) ? (int32_t*)((char*)ws + p->ws.work_cols2) : nullptr;
-    S.work_prefix = (const int64_t*)((char*)ws + p->ws.work_prefix); S.nloci = p->nloci;
-    S.slice_prefix = (const int64_t*)((char*)ws + p->ws.slice_prefix);
-    S.rate = d_rate; S.subst = d_subst; S.lnl = d_lnl; S.flag = d_flag; S.eval_counter = p->d_evals.p;
-    const bool spill = p->site.lds_depth < p->prog.stack_depth;
-    S.lds_depth = p->site.lds_depth;
-    S.spill = spill ? (double*)((char*)ws + p->ws.spill) : nullptr;
-    S.persistent = (p->site.persistent || p->site.mixed) ? 1 : 0;
-    S.first_round = p->site.waves;
-    S.mixed_few_waves = p->site.mixed_few_waves; S.mixed_switch_cols = p->site.mixed_switch_cols;
-    S.tail_order = (p->site.persistent && !p->site.mixed && p->site.tail_order) ? 1 : 0;
-    S.first_fraction = (p->site.first_fraction > 0.0) ? p->site.first_fraction : 1.0 / (double)p->site.grid_mult;
-    S.share_work = p->site.share_work;
-    S.main_shares = (p->site.reserve_q > 0) ? p->site.waves : p->site.waves * p->site.grid_mult;
-    S.tail_shares = p->site.tail_shares;
-    S.work_wprefix = (const int64_t*)((char*)ws + p->ws.work_wprefix); S.part_prefix = (const int64_t*)((char*)ws + p->ws.part_prefix);
-    S.part_start = (const int64_t*)((char*)ws + p->ws.part_start);
-    S.ncat = p->ncat; S.cat = p->d_cat.p;
-    // profiling brackets exactly the dominant kernel, so the figure matches rocprofv3's per-kernel average
-    if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 0], st));
-    if (p->n_site_chunks > 0) {
-        const bool mixed = p->site.mixed;
-        const dim3 grid((unsigned)site_grid(p->site, p->n_site_chunks));
-        // the packed tip states are read with the fused-cherry stream (tree_program.hpp)
-        S.ops = p->d_fused_ops.p;
-        S.nops = (int32_t)p->prog.fused_ops.size();
-        // variants: packed words in registers (<= 16 / <= 64 tips); streamed one word ahead (more than 64 tips)
-        const int variant = p->nwords <= 2 ? 2 : p->nwords <= 8 ? 8 : (spill ? kStreamWordsSpill : kStreamWords);
-        if (mixed) {   // equal shares: first_round = grid
-            S.first_fraction = 1.0;
-            HIP_TRY(launch_site_rate_kernel(kMixedVariant + variant, p->model, grid, mixed_lds_bytes(p->prog.stack_depth), st, S));
-        } else   // (lds_depth = the stack depth unless the SPILL variant runs)
-            HIP_TRY(launch_site_rate_kernel(variant, p->model, grid, site_lds_bytes(p->site.lds_depth), st, S));
-    }
-    if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 1], st));
-    if (dedup) dedup_scatter_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
-    HIP_TRY(hipGetLastError());
-    return TPHIP_OK;
-}
-
-// Where the empirical-Bayes fit of a locus' scale starts: the mean over ALL its columns of classify_kernel's parsimony start
-// rate s0 (start_log_rate; 0 for the columns it answers in closed form), or 1 / tree length for a locus without a change.
-// One workgroup per locus, thread-strided sums and a binary tree: the order depends on the locus alone.
-__global__ __launch_bounds__(256) void eb_start_scale_kernel(const int64_t* __restrict__ locus_offsets, const uint8_t* __restrict__ flag,
-                                                            const double* __restrict__ start_log, double chrono_length,
-                                                            double* __restrict__ start) {
-    __shared__ double red[256];
-    const int locus = blockIdx.x;
-    const int64_t lo = locus_offsets[locus], hi = locus_offsets[locus + 1];
-    double sum = 0.0;
-    for (int64_t c = lo + threadIdx.x; c < hi; c += 256)
-        if (flag[c] == TPHIP_FLAG_OK) sum += exp(start_log[c]);
-    red[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) start[locus] = (red[0] > 0.0 && hi > lo) ? red[0] / (double)(hi - lo) : 1.0 / chrono_length;
-}
-
-// Front end of the empirical-Bayes calls (eb_driver.hip): classify_kernel for the informative-cell counts and the packed
-// tip words, then -- every column takes part in the mixture, constant ones included -- either all columns, or the first
-// column of every site pattern of a locus as a compacted work list (the stage-2 de-duplication kernels, forced on).
-int tphip_internal_eb_prepare(tphip_plan* p, const uint8_t* d_states, const EbPrep* B, int32_t use_patterns, double* d_start,
-                              void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (p->n_pi_chunks <= 0) return TPHIP_OK;
-    ClassifyParams C;
-    C.states = d_states; C.ncols_total = p->ncols; C.ntaxa = p->ntaxa; C.models = p->d_models.p;
-    C.locus_offsets = p->d_offsets.p; C.chunk_locus = p->d_pi_chunk_locus.p; C.chunk_index = p->d_pi_chunk_index.p;
-    C.rate = B->scratch[0]; C.subst = B->scratch[1]; C.lnl = B->scratch[2]; C.flag = B->flag; C.nres = B->nres;
-    C.chrono_length = p->prog.chrono_length;
-    C.steps = (const int2*)p->d_cls_steps.p; C.tail_pops = p->prog.cls_tail_pops; C.max_pops = p->prog.cls_max_pops;
-    C.packed = B->packed;
-    C.start_scale = 1.0;
-    C.hash = use_patterns ? B->hash : nullptr;
-    classify_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(kPiBlock), 0, st>>>(C);
-    if (d_start)   // before the flags are reset: they tell which columns carry a start rate
-        eb_start_scale_kernel<<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(p->d_offsets.p, B->flag, B->scratch[0],
-                                                                             p->prog.chrono_length, d_start);
-    HIP_TRY(hipMemsetAsync(B->flag, TPHIP_FLAG_OK, (size_t)p->ncols, st));
-    HIP_TRY(hipMemsetAsync(B->dup_of, 0xff, sizeof(int32_t) * (size_t)p->ncols, st));
-    if (use_patterns) {
-        DedupParams D;
-        D.locus_offsets = p->d_offsets.p; D.chunk_locus = p->d_pi_chunk_locus.p; D.chunk_index = p->d_pi_chunk_index.p;
-        D.hash = B->hash; D.packed = B->packed; D.nwords = p->nwords; D.ncols_total = p->ncols; D.flag = B->flag;
-        D.dup_of = B->dup_of; D.tab_key = B->tab_key; D.tab_val = B->tab_val; D.on = B->on; D.mode = DEDUP_ON;
-        D.rate = nullptr; D.subst = nullptr; D.lnl = nullptr;
-        if (p->max_locus_cols > 2048) dedup_estimate_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(D);
-        else dedup_estimate_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(D);
-        dedup_insert_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
-        dedup_resolve_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(D);
-        // (this front end keeps the one-workgroup-per-locus list for long loci too: it runs once per empirical-Bayes call,
-        //  not per step, and EbPrep carries no buffer for the chunk counts of launch_compact_chunked)
-        if (p->max_locus_cols > 2048) compact_kernel<1024><<<dim3((unsigned)p->nloci), dim3(1024), 0, st>>>(B->flag, p->d_offsets.p, B->work_cols, B->work_count);
-        else compact_kernel<256><<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(B->flag, p->d_offsets.p, B->work_cols, B->work_count);
-    }
-    HIP_TRY(hipGetLastError());
-    return TPHIP_OK;
-}
-
-static int launch_pi_tables(tphip_plan* p, const double* d_rates, const int32_t* d_nres, double* d_tables, void* ws,
-                            hipStream_t st, int slot) {
-    PiParams Q = pi_params(p, d_rates, d_nres, ws);
-    if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 2], st));
-    if (p->n_pi_chunks > 0) {
-        const dim3 grid((unsigned)p->n_pi_chunks), block(kPiBlock);
-        if (p->site.pi_split) {   // between them the two kernels write every entry of `partial`
-            pi_net_kernel<<<grid, block, 0, st>>>(Q);
-            if (p->n_i > 0) pi_interval_kernel<<<grid, block, 0, st>>>(Q);
-        } else {
-            pi_partial_kernel<<<grid, block, 0, st>>>(Q);
-        }
-    }
-    pi_reduce_kernel<<<dim3((unsigned)p->nloci), dim3(kPiReduceBlock), 0, st>>>(Q.partial, p->d_locus_pichunk_offsets.p, p->T,
-                                                                   p->d_times.p, p->n_t, p->n_i, d_tables);
-    if (slot >= 0) HIP_TRY(hipEventRecord(p->ev[4 * slot + 3], st));
-    HIP_TRY(hipGetLastError());
-    return TPHIP_OK;
-}
-
-static int take_slot(tphip_plan* p) {
-    if (!p->profile) return -1;
-    if (p->ev_used >= kProfileRing) {
-        if (profile_drain(p)) return -1;
-    }
-    return p->ev_used++;
-}
-
-int tphip_run_dev(tphip_plan* p, const uint8_t* d_states, double* d_rate, double* d_subst, double* d_lnl, uint8_t* d_flag,
-                  int32_t* d_nres, double* d_tables, void* ws, size_t ws_bytes, void* stream) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    if (!d_states || !d_rate || !d_subst || !d_lnl || !d_flag || !d_nres || !d_tables || !ws)
-        return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    int slot = take_slot(p);
-    int rc = launch_site_rates(p, d_states, d_rate, d_subst, d_lnl, d_flag, d_nres, ws, st, slot);
-    if (rc) return rc;
-    return launch_pi_tables(p, d_rate, d_nres, d_tables, ws, st, slot);
-}
-
-int tphip_site_rates_dev(tphip_plan* p, const uint8_t* d_states, double* d_rate, double* d_subst, double* d_lnl,
-                         uint8_t* d_flag, int32_t* d_nres, void* ws, size_t ws_bytes, void* stream) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    if (!d_states || !d_rate || !d_subst || !d_lnl || !d_flag || !d_nres || !ws)
-        return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
-    HIP_TRY(hipSetDevice(p->device));
-    int slot = take_slot(p);
-    int rc = launch_site_rates(p, d_states, d_rate, d_subst, d_lnl, d_flag, d_nres, ws, (hipStream_t)stream, slot);
-    if (rc == 0 && slot >= 0) {  // keep the pi event pair of this slot valid (zero-length)
-        HIP_TRY(hipEventRecord(p->ev[4 * slot + 2], (hipStream_t)stream));
-        HIP_TRY(hipEventRecord(p->ev[4 * slot + 3], (hipStream_t)stream));
-    }
-    return rc;
-}
-
-int tphip_pi_tables_dev(tphip_plan* p, const double* d_rates, const int32_t* d_nres, double* d_tables, void* ws,
-                        size_t ws_bytes, void* stream) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    if (!d_rates || !d_tables || !ws) return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
-    HIP_TRY(hipSetDevice(p->device));
-    int slot = take_slot(p);
-    if (slot >= 0) {
-        HIP_TRY(hipEventRecord(p->ev[4 * slot + 0], (hipStream_t)stream));
-        HIP_TRY(hipEventRecord(p->ev[4 * slot + 1], (hipStream_t)stream));
-    }
-    return launch_pi_tables(p, d_rates, d_nres, d_tables, ws, (hipStream_t)stream, slot);
-}
-
-static PiParams pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres, void* ws) {
-    PiParams Q;
-    Q.rates = d_rates; Q.nres = d_nres; Q.locus_offsets = p->d_offsets.p;
-    Q.chunk_locus = p->d_pi_chunk_locus.p; Q.chunk_index = p->d_pi_chunk_index.p;
-    Q.T = p->T; Q.intervals = p->d_intervals.p; Q.n_i = p->n_i; Q.integ_mode = p->integ_mode;
-    Q.correction = p->correction; Q.threshold = p->threshold;
-    Q.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
-    Q.partial = ws ? (double*)((char*)ws + p->ws.partial) : nullptr;
-    return Q;
-}
-
-int tphip_corrected_rates_dev(tphip_plan* p, const double* d_rates, const int32_t* d_nres, double* d_out, void* stream) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    if (p->ncols && (!d_rates || !d_out)) return fail(TPHIP_ERR_INVALID, "null device pointer");
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->ncols) {
-        corrected_rates_kernel<<<dim3((unsigned)((p->ncols + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
-            pi_params(p, d_rates, d_nres, nullptr), p->ncols, d_out);
-        HIP_TRY(hipGetLastError());
-    }
-    return TPHIP_OK;
-}
-
-int tphip_corrected_rates(tphip_plan* p, const double* rates, const int32_t* nres, double* out) {
-    if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    if (p->ncols == 0) return TPHIP_OK;
-    if (!rates || !out) return fail(TPHIP_ERR_INVALID, "null host pointer");
-    HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
-    const size_t n = (size_t)p->ncols;
-    double* d_r = S.get<double>(n);
-    double* d_o = S.get<double>(n);
-    int32_t* d_n = nres ? S.get<int32_t>(n) : nullptr;
-    if (!d_r || !d_o || (nres && !d_n)) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
-    if (nres) HIP_TRY(hipMemcpy(d_n, nres, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    int rc = tphip_corrected_rates_dev(p, d_r, d_n, d_o, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, d_o, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
-}
-
-int tphip_townsend_pi_dense_dev(int32_t device, const double* d_rates, int64_t n, const double* d_times, int32_t n_times,
-                                double* d_out, void* stream) {
-    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (n < 0 || n_times < 0 || (n && n_times && (!d_rates || !d_out || !d_times))) return fail(TPHIP_ERR_INVALID, "bad arguments");
-    HIP_TRY(hipSetDevice(device));
-    if (n && n_times) {
-        townsend_dense_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(d_rates, n, d_times,
-                                                                                                    n_times, d_out);
-        HIP_TRY(hipGetLastError());
-    }
-    return TPHIP_OK;
-}
-
-int tphip_quad_townsend_dev(int32_t device, const double* d_rates, int64_t n, double a, double b, int32_t integ_mode,
-                            double* d_integral, double* d_abserr, void* stream) {
-    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (n < 0 || (n && (!d_rates || !d_integral || !d_abserr))) return fail(TPHIP_ERR_INVALID, "bad arguments");
-    if (!(a < b)) return fail(TPHIP_ERR_INVALID, "Start time is sooner than end time in an interval");
-    if (integ_mode != TPHIP_INTEG_QUADPACK && integ_mode != TPHIP_INTEG_CLOSED) return fail(TPHIP_ERR_INVALID, "unknown integ_mode");
-    HIP_TRY(hipSetDevice(device));
-    if (n) {
-        quad_sites_kernel<<<dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (hipStream_t)stream>>>(d_rates, n, a, b, integ_mode,
-                                                                                                d_integral, d_abserr);
-        HIP_TRY(hipGetLastError());
-    }
-    return TPHIP_OK;
-}
-
-int tphip_state_histogram_dev(int32_t device, const uint8_t* d_states, int64_t ncols_total, int32_t ntaxa,
-                              const int64_t* d_locus_offsets, int64_t nloci, int64_t* d_hist, void* stream) {
-    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (!d_states || !d_locus_offsets || !d_hist || nloci < 1 || ntaxa < 1) return fail(TPHIP_ERR_INVALID, "bad arguments");
-    HIP_TRY(hipSetDevice(device));
-    state_histogram_kernel<<<dim3((unsigned)nloci), dim3(256), 0, (hipStream_t)stream>>>(
-        d_states, ncols_total, ntaxa, d_locus_offsets, (unsigned long long*)d_hist);
-    HIP_TRY(hipGetLastError());
-    return TPHIP_OK;
-}
-
 // ---- host-pointer wrappers -------------------------------------------------------------------------
 
 // Host-pointer calls keep their device buffers in the plan (grown on demand, freed with the plan): a hipMalloc /
@@ -992,16 +564,10 @@ static int host_run(tphip_plan* p, const uint8_t* states, const double* rates_in
                        p->ncols >= kHostSplitMinColumns && states && rate && subst && lnl && flag && nres &&
                        is_pinned(states) && is_pinned(rate) && is_pinned(subst) && is_pinned(lnl) && is_pinned(flag) &&
                        is_pinned(nres) && (!do_pi || (tables && is_pinned(tables)));
-    if (!split) {
-        // always drain: a failed enqueue may already have copies in flight that touch the caller's buffers
-        const int rc = host_enqueue(p, states, pitch, nullptr, rates_in, nres_in, rate, subst, lnl, flag, nres, tables,
-                                    do_site, do_pi);
-        const int rw = host_wait(p);
-        return rc ? rc : rw;
-    }
-    int rc = make_parts(p);
+    int rc = split ? make_parts(p) : TPHIP_OK;
     if (rc) return rc;
-    if (p->parts.empty()) {   // the batch does not cut into groups with columns
+    if (!split || p->parts.empty()) {   // the whole batch at once (also when it does not cut into groups with columns)
+        // always drain: a failed enqueue may already have copies in flight that touch the caller's buffers
         rc = host_enqueue(p, states, pitch, nullptr, rates_in, nres_in, rate, subst, lnl, flag, nres, tables, do_site, do_pi);
         const int rw = host_wait(p);
         return rc ? rc : rw;
@@ -1056,85 +622,6 @@ int tphip_run_fused_pitched(tphip_plan* p, const uint8_t* states, int64_t row_pi
     return host_run(p, states, nullptr, nullptr, rate, subst, lnl, flag, nres, tables, true, true, (size_t)row_pitch);
 }
 
-int tphip_townsend_pi_dense(int32_t device, const double* rates, int64_t n, const double* times, int32_t n_times, double* out) {
-    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (n < 0 || n_times < 0) return fail(TPHIP_ERR_INVALID, "bad arguments");
-    if (n == 0 || n_times == 0) return TPHIP_OK;
-    if (!rates || !times || !out) return fail(TPHIP_ERR_INVALID, "null host pointer");
-    HIP_TRY(hipSetDevice(device));
-    Scratch S;
-    double* d_r = S.get<double>((size_t)n);
-    double* d_t = S.get<double>((size_t)n_times);
-    double* d_o = S.get<double>((size_t)n * (size_t)n_times);
-    if (!d_r || !d_t || !d_o) return fail(TPHIP_ERR_HIP, "hipMalloc failed for the dense PI matrix");
-    HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_t, times, sizeof(double) * (size_t)n_times, hipMemcpyHostToDevice));
-    int rc = tphip_townsend_pi_dense_dev(device, d_r, n, d_t, n_times, d_o, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, d_o, sizeof(double) * (size_t)n * (size_t)n_times, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
-}
-
-int tphip_quad_townsend(int32_t device, const double* rates, int64_t n, double a, double b, int32_t integ_mode,
-                        double* integral, double* abserr) {
-    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (n < 0) return fail(TPHIP_ERR_INVALID, "bad arguments");
-    if (n == 0) return TPHIP_OK;
-    if (!rates || !integral || !abserr) return fail(TPHIP_ERR_INVALID, "null host pointer");
-    HIP_TRY(hipSetDevice(device));
-    Scratch S;
-    double* d_r = S.get<double>((size_t)n);
-    double* d_i = S.get<double>((size_t)n);
-    double* d_e = S.get<double>((size_t)n);
-    if (!d_r || !d_i || !d_e) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    int rc = tphip_quad_townsend_dev(device, d_r, n, a, b, integ_mode, d_i, d_e, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(integral, d_i, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(abserr, d_e, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
-}
-
-int tphip_eval_columns_dev(tphip_plan* p, const uint8_t* d_s, const double* d_u, double* d_f, double* d_g, double* d_h,
-                           void* stream) {
-    if (!p || !d_s || !d_u || !d_f || !d_g || !d_h) return fail(TPHIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    EvalParams E;
-    E.S.states = d_s; E.S.ncols_total = p->ncols; E.S.models = p->d_models.p; E.S.ops = p->d_ops.p;
-    E.S.nops = (int32_t)p->prog.ops.size(); E.S.stack_depth = p->prog.stack_depth; E.S.chrono_length = p->prog.chrono_length;
-    E.S.locus_offsets = p->d_offsets.p; E.S.chunk_locus = p->d_site_chunk_locus.p; E.S.chunk_index = p->d_site_chunk_index.p;
-    E.S.chunk_cols = p->site.chunk_cols;
-    E.S.packed = nullptr; E.S.nwords = 0;
-    E.S.work_cols = nullptr; E.S.work_cols2 = nullptr; E.S.work_count = nullptr; E.S.work_prefix = nullptr; E.S.nloci = p->nloci; E.S.persistent = 0; E.S.first_round = 0; E.S.mixed_few_waves = 0; E.S.mixed_switch_cols = 0; E.S.first_fraction = 1.0; E.S.ncat = p->ncat; E.S.cat = p->d_cat.p; E.S.rate = nullptr; E.S.subst = nullptr; E.S.lnl = nullptr;
-    E.S.flag = nullptr; E.S.eval_counter = nullptr; E.S.spill = nullptr; E.S.lds_depth = p->prog.stack_depth;
-    E.u = d_u; E.f = d_f; E.g = d_g; E.h = d_h;
-    if (p->n_site_chunks > 0)
-        HIP_TRY(launch_eval_columns_kernel(p->model, dim3((unsigned)p->n_site_chunks), site_lds_bytes(p->prog.stack_depth), (hipStream_t)stream, E));
-    return TPHIP_OK;
-}
-
-int tphip_eval_columns(tphip_plan* p, const uint8_t* states, const double* u, double* f, double* g, double* h) {
-    if (!p || !states || !u || !f || !g || !h) return fail(TPHIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
-    const size_t n = (size_t)p->ncols;
-    uint8_t* d_s = S.get<uint8_t>(n * (size_t)p->ntaxa);
-    double* d_u = S.get<double>(n);
-    double* d_f = S.get<double>(n);
-    double* d_g = S.get<double>(n);
-    double* d_h = S.get<double>(n);
-    if (!d_s || !d_u || !d_f || !d_g || !d_h) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_s, states, n * (size_t)p->ntaxa, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_u, u, sizeof(double) * n, hipMemcpyHostToDevice));
-    int rc = tphip_eval_columns_dev(p, d_s, d_u, d_f, d_g, d_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(f, d_f, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(g, d_g, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h, d_h, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
-}
-
 // per-locus eigen-systems from DEVICE arrays pi [L][4] (floored, any scale) and exch [L][6]; for stage1_driver.hip
 int tphip_internal_set_models_dev(tphip_plan* p, const double* d_pi, const double* d_exch, void* stream) {
     const int bs = 64;
@@ -1148,8 +635,7 @@ int tphip_internal_store_pi(tphip_plan* p, const double* pi) {
     if (!p || !p->saved) return fail(TPHIP_ERR_INVALID, "plan has no saved descriptor");
     p->saved->pi.assign(pi, pi + 4 * (size_t)p->nloci);
     p->saved->d.pi = p->saved->pi.data();
-    for (tphip_plan* q : p->parts) (void)tphip_plan_destroy(q);
-    p->parts.clear();
+    drop_parts(p);
     return TPHIP_OK;
 }
 
@@ -1175,8 +661,7 @@ int tphip_plan_set_models(tphip_plan* p, const double* pi, const double* exch) {
         std::vector<LocusModel> f81;
         f81_models(p->saved->pi.data(), p->nloci, &f81);
         HIP_TRY(hipMemcpy(p->d_models.p, f81.data(), sizeof(LocusModel) * L, hipMemcpyHostToDevice));
-        for (tphip_plan* q : p->parts) (void)tphip_plan_destroy(q);
-        p->parts.clear();
+        drop_parts(p);
         return TPHIP_OK;
     }
     p->saved->d.exch = p->saved->exch.data();
@@ -1192,125 +677,7 @@ int tphip_plan_set_models(tphip_plan* p, const double* pi, const double* exch) {
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     // locus groups of the pipelined host path were built from the old models: rebuilt on next use
-    for (tphip_plan* q : p->parts) (void)tphip_plan_destroy(q);
-    p->parts.clear();
-    return TPHIP_OK;
-}
-
-// Unique site patterns of device-resident columns (see tphip_compress_columns): temporaries in `tmp`, results in `keep`.
-static int compress_core(const uint8_t* d_s, int64_t ncols_total, int32_t ntaxa, const int64_t* d_off, int64_t nloci, bool want_map,
-                         Scratch& tmp, Scratch& keep, uint8_t** d_out_p, int64_t** d_newoff_p, double** d_w_p, int64_t** d_map_p,
-                         int64_t* npat_p) {
-    const size_t n = (size_t)ncols_total;
-    const int32_t nwords = (ntaxa + 7) / 8;
-    uint32_t* d_packed = tmp.get<uint32_t>(n * (size_t)nwords);
-    uint64_t* d_key = tmp.get<uint64_t>(n);
-    uint64_t* d_key2 = tmp.get<uint64_t>(n);
-    uint64_t* d_h2 = tmp.get<uint64_t>(n);
-    uint32_t* d_col = tmp.get<uint32_t>(n);
-    uint32_t* d_col2 = tmp.get<uint32_t>(n);
-    int32_t* d_head = tmp.get<int32_t>(n);
-    int64_t* d_incl = tmp.get<int64_t>(n);
-    int64_t* d_newoff = keep.get<int64_t>((size_t)nloci + 1);
-    int64_t* d_map = want_map ? keep.get<int64_t>(n) : nullptr;
-    if (!d_packed || !d_key || !d_key2 || !d_h2 || !d_col || !d_col2 || !d_head || !d_incl || !d_newoff || (want_map && !d_map))
-        return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    pack_hash_kernel<<<dim3(blocks), dim3(256)>>>(d_s, ncols_total, ntaxa, nwords, d_off, nloci, d_packed, d_key, d_h2, d_col);
-    HIP_TRY(hipGetLastError());
-    int locus_bits = 1;
-    while (((int64_t)1 << locus_bits) < nloci) ++locus_bits;
-    const int end_bit = std::min(64, kPatHashBits + locus_bits);
-    size_t tmp_sort = 0, tmp_scan = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, d_key, d_key2, d_col, d_col2, (int)n, 0, end_bit));
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, d_head, d_incl, (int)n));
-    void* d_tmp = tmp.get<char>(std::max(tmp_sort, tmp_scan));
-    if (!d_tmp) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_sort, d_key, d_key2, d_col, d_col2, (int)n, 0, end_bit));
-    head_flag_kernel<<<dim3(blocks), dim3(256)>>>(d_key2, d_col2, d_h2, d_packed, nwords, ncols_total, d_head);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_scan, d_head, d_incl, (int)n));
-    int64_t npat = 0;
-    HIP_TRY(hipMemcpy(&npat, d_incl + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost));
-    uint8_t* d_out = keep.get<uint8_t>((size_t)npat * (size_t)ntaxa);
-    int32_t* d_count = tmp.get<int32_t>((size_t)npat);
-    double* d_w = keep.get<double>((size_t)npat);
-    if (!d_out || !d_count || !d_w) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemset(d_count, 0, sizeof(int32_t) * (size_t)npat));
-    pattern_scatter_kernel<<<dim3(blocks), dim3(256)>>>(d_col2, d_head, d_incl, d_packed, nwords, ntaxa, ncols_total, npat, d_out,
-                                                      d_count, d_map);
-    pattern_offsets_kernel<<<dim3((unsigned)((nloci + 256) / 256)), dim3(256)>>>(d_off, nloci, ncols_total, d_incl, npat, d_newoff);
-    count_to_weight_kernel<<<dim3((unsigned)((npat + 255) / 256)), dim3(256)>>>(d_count, npat, d_w);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    *d_out_p = d_out; *d_newoff_p = d_newoff; *d_w_p = d_w; *npat_p = npat;
-    if (d_map_p) *d_map_p = d_map;
-    return TPHIP_OK;
-}
-
-// device-to-device twin for the other translation units (stage1_driver.hip); the three result arrays are the caller's to hipFree
-int tphip_internal_compress_dev(const uint8_t* d_s, int64_t ncols_total, int32_t ntaxa, const int64_t* d_off, int64_t nloci,
-                                uint8_t** d_out, int64_t** d_newoff, double** d_w, int64_t* npat) {
-    if (ncols_total >= ((int64_t)1 << 31)) return fail(TPHIP_ERR_INVALID, "too many columns for one call (2^31)");
-    if (nloci >= ((int64_t)1 << (64 - kPatHashBits))) return fail(TPHIP_ERR_INVALID, "too many loci for one call");
-    Scratch tmp, keep;
-    int rc = compress_core(d_s, ncols_total, ntaxa, d_off, nloci, false, tmp, keep, d_out, d_newoff, d_w, nullptr, npat);
-    if (!rc) keep.bufs.clear();   // ownership passes to the caller
-    return rc;
-}
-
-int tphip_compress_columns(int32_t device, const uint8_t* states, int64_t ncols_total, int32_t ntaxa,
-                           const int64_t* locus_offsets, int64_t nloci, uint8_t* out_states, int64_t* out_offsets,
-                           double* out_weight, int64_t* out_map, int64_t* out_npatterns) {
-    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (!states || !locus_offsets || !out_states || !out_offsets || !out_weight || !out_npatterns || nloci < 1 || ntaxa < 1 ||
-        ncols_total < 0)
-        return fail(TPHIP_ERR_INVALID, "bad arguments");
-    if (ncols_total >= ((int64_t)1 << 31)) return fail(TPHIP_ERR_INVALID, "too many columns for one call (2^31)");
-    if (nloci >= ((int64_t)1 << (64 - kPatHashBits))) return fail(TPHIP_ERR_INVALID, "too many loci for one call");
-    if (locus_offsets[0] != 0 || locus_offsets[nloci] != ncols_total) return fail(TPHIP_ERR_INVALID, "locus_offsets must span the columns");
-    for (int64_t l = 0; l < nloci; ++l)
-        if (locus_offsets[l + 1] < locus_offsets[l]) return fail(TPHIP_ERR_INVALID, "locus_offsets must not decrease");
-    if (ncols_total == 0) {
-        for (int64_t l = 0; l <= nloci; ++l) out_offsets[l] = 0;
-        *out_npatterns = 0;
-        return TPHIP_OK;
-    }
-    HIP_TRY(hipSetDevice(device));
-    Scratch S, K;
-    const size_t n = (size_t)ncols_total;
-    uint8_t* d_s = S.get<uint8_t>(n * (size_t)ntaxa);
-    int64_t* d_off = S.get<int64_t>((size_t)nloci + 1);
-    if (!d_s || !d_off) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_s, states, n * (size_t)ntaxa, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_off, locus_offsets, sizeof(int64_t) * ((size_t)nloci + 1), hipMemcpyHostToDevice));
-    uint8_t* d_out = nullptr; int64_t* d_newoff = nullptr; double* d_w = nullptr; int64_t* d_map = nullptr; int64_t npat = 0;
-    int rc = compress_core(d_s, ncols_total, ntaxa, d_off, nloci, out_map != nullptr, S, K, &d_out, &d_newoff, &d_w, &d_map, &npat);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_states, d_out, (size_t)npat * (size_t)ntaxa, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_offsets, d_newoff, sizeof(int64_t) * ((size_t)nloci + 1), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_weight, d_w, sizeof(double) * (size_t)npat, hipMemcpyDeviceToHost));
-    if (out_map) HIP_TRY(hipMemcpy(out_map, d_map, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-    *out_npatterns = npat;
-    return TPHIP_OK;
-}
-
-int tphip_state_histogram(int32_t device, const uint8_t* states, int64_t ncols_total, int32_t ntaxa,
-                          const int64_t* locus_offsets, int64_t nloci, int64_t* hist) {
-    if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (!states || !locus_offsets || !hist || nloci < 1 || ntaxa < 1 || ncols_total < 0) return fail(TPHIP_ERR_INVALID, "bad arguments");
-    HIP_TRY(hipSetDevice(device));
-    Scratch S;
-    const size_t nb = (size_t)ncols_total * (size_t)ntaxa;
-    uint8_t* d_s = S.get<uint8_t>(nb);
-    int64_t* d_o = S.get<int64_t>((size_t)nloci + 1);
-    int64_t* d_h = S.get<int64_t>(16 * (size_t)nloci);
-    if (!d_s || !d_o || !d_h) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_s, states, nb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_o, locus_offsets, sizeof(int64_t) * ((size_t)nloci + 1), hipMemcpyHostToDevice));
-    int rc = tphip_state_histogram_dev(device, d_s, ncols_total, ntaxa, d_o, nloci, d_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(hist, d_h, sizeof(int64_t) * 16 * (size_t)nloci, hipMemcpyDeviceToHost));
+    drop_parts(p);
     return TPHIP_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -13,6 +14,7 @@
 #include "locus_value_params.hpp"
 #include "locus_grad2_params.hpp"
 #include "locus_launch_plan.hpp"
+#include "pi_rate.hpp"
 #include "site_launch_plan.hpp"
 #include "site_rate_params.hpp"
 #include "tphip.h"
@@ -201,12 +203,46 @@ struct EbPrep {
     int32_t* work_count;          // [nloci]       (patterns)
 };
 
+// What every launch of a kernel that takes SiteParams shares (site_rate_kernel and the eval diagnostic in site_driver.hip,
+// the posterior kernels of eb_driver.hip): the batch, the tree's op stream -- the fused-cherry stream goes with the packed tip
+// words, the plain one with the diagnostic that reads the states -- the site chunk tables and the rate categories, with the
+// whole stack in LDS and equal shares.  Work lists, outputs and scheduling are the caller's.
+inline SiteParams plan_site_params(const tphip_plan* p, const uint8_t* d_states, bool fused) {
+    SiteParams S{};
+    S.states = d_states; S.ncols_total = p->ncols; S.models = p->d_models.p;
+    S.ops = fused ? p->d_fused_ops.p : p->d_ops.p;
+    S.nops = (int32_t)(fused ? p->prog.fused_ops.size() : p->prog.ops.size());
+    S.stack_depth = p->prog.stack_depth; S.chrono_length = p->prog.chrono_length;
+    S.locus_offsets = p->d_offsets.p; S.chunk_locus = p->d_site_chunk_locus.p; S.chunk_index = p->d_site_chunk_index.p;
+    S.chunk_cols = p->site.chunk_cols;
+    S.nloci = p->nloci; S.ncat = p->ncat; S.cat = p->d_cat.p;
+    S.lds_depth = p->prog.stack_depth; S.first_fraction = 1.0;
+    return S;
+}
+
+// The PI stage's view of the plan (finalize_rate's inputs, the schedule and the PI chunk tables); launch_pi_tables sets `partial`.
+inline PiParams plan_pi_params(const tphip_plan* p, const double* d_rates, const int32_t* d_nres) {
+    PiParams Q{};
+    Q.rates = d_rates; Q.nres = d_nres; Q.locus_offsets = p->d_offsets.p;
+    Q.chunk_locus = p->d_pi_chunk_locus.p; Q.chunk_index = p->d_pi_chunk_index.p;
+    Q.T = p->T; Q.intervals = p->d_intervals.p; Q.n_i = p->n_i; Q.integ_mode = p->integ_mode;
+    Q.correction = p->correction; Q.threshold = p->threshold;
+    Q.round_scale = (p->round_decimals >= 0) ? std::pow(10.0, (double)p->round_decimals) : 0.0;
+    return Q;
+}
+
 // launch configuration of the stage-1 kernels of a new plan, from its tree and batch (locus_driver.hip, for tphip_plan_create)
 __attribute__((visibility("hidden"))) void configure_locus_launch(tphip_plan* p, const PlanKnobs& knobs);
 
-// helpers of tphip.hip and locus_driver.hip for the other translation units of the library (not declared in include/tphip.h)
-// (hidden visibility: the shared library exports exactly what include/tphip.h declares)
+// helpers of tphip.hip, site_driver.hip, pattern_driver.hip and locus_driver.hip for the other translation units of the library
+// (not declared in include/tphip.h; hidden visibility: the shared library exports exactly what include/tphip.h declares)
 extern "C" {
+// the two stage-2 launchers (site_driver.hip), for the host-pointer paths of tphip.hip; slot = profiling slot or -1
+__attribute__((visibility("hidden"))) int launch_site_rates(tphip_plan* p, const uint8_t* d_states, double* d_rate, double* d_subst,
+                                                          double* d_lnl, uint8_t* d_flag, int32_t* d_nres, void* ws, hipStream_t st,
+                                                          int slot);
+__attribute__((visibility("hidden"))) int launch_pi_tables(tphip_plan* p, const double* d_rates, const int32_t* d_nres, double* d_tables,
+                                                         void* ws, hipStream_t st, int slot);
 __attribute__((visibility("hidden"))) int tphip_internal_stage_alignment(tphip_plan* p, const uint8_t* states, void** d_states_cache,
                                                                        uint8_t** d_s);
 __attribute__((visibility("hidden"))) const tphip_plan_desc* tphip_internal_saved_desc(const tphip_plan* p);

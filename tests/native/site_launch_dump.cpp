@@ -5,8 +5,8 @@
 //   loci <count> <columns each>            (may repeat: the loci are appended)
 //   knob <TPHIP_...> <text>                (the text an environment variable would hold)
 //   occ <variant> <lds_bytes> <resident workgroups per CU>
-// Prints the SiteLaunch fields, the occupancy queries made (in order), the chunk-table sizes, the workspace offsets and
-// the launch grid as "name value" lines.  An occupancy query that the table does not hold answers 0, as a failed one does.
+// Prints the SiteLaunch fields, the occupancy queries made (in order), the chunk-table sizes, the workspace offsets, the
+// launch grid and the launch arguments (site_kernel_args, as "args.<name>") as "name value" lines.  An occupancy query that the table does not hold answers 0, as a failed one does.
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -75,6 +75,12 @@ int main() {
     printf("chunk_tables_ok %d\n", ok ? 1 : 0);
     printf("grid %lld\n", (long long)site_grid(s, (int64_t)t.site_chunk_locus.size()));
     printf("lds_bytes %zu\nmixed_lds_bytes %zu\n", site_lds_bytes(s.lds_depth), mixed_lds_bytes(shape.stack_depth));
+    // what launch_site_rates takes from these decisions at every launch
+    const SiteKernelArgs a = site_kernel_args(s, shape.nwords, shape.stack_depth, (int64_t)t.site_chunk_locus.size());
+    printf("site_variant %d\nargs.variant %d\nargs.lds_bytes %zu\nargs.grid %lld\nargs.persistent %d\nargs.first_round %d\n",
+           site_variant(shape.nwords), a.variant, a.lds_bytes, (long long)a.grid, a.persistent, a.first_round);
+    printf("args.first_fraction %.17g\nargs.tail_order %d\nargs.share_work %d\nargs.main_shares %d\nargs.spill %d\nargs.second_list %d\n",
+           a.first_fraction, a.tail_order, a.share_work, a.main_shares, a.spill ? 1 : 0, a.second_list ? 1 : 0);
     const std::pair<const char*, size_t> regions[] = {
         {"work_cols", w.work_cols}, {"work_cols2", w.work_cols2}, {"work_count", w.work_count}, {"work_prefix", w.work_prefix},
         {"slice_prefix", w.slice_prefix}, {"work_class", w.work_class}, {"work_wprefix", w.work_wprefix}, {"part_prefix", w.part_prefix},

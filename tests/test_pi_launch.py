@@ -103,9 +103,10 @@ def test_knob_goes_through_plan_knobs_only():
     assert '"TPHIP_PI_SPLIT"' in header[header.index("kPlanKnobNames"):header.index("set_plan_knob")]
     assert "getenv" not in header
     assert "getenv" not in open(os.path.join(CSRC, "pi_kernels.hpp")).read()
-    tphip = open(os.path.join(CSRC, "tphip.hip")).read()
-    assert "TPHIP_PI_SPLIT" not in tphip
-    body = tphip[tphip.index("static int launch_pi_tables("):tphip.index("static int take_slot(")]
+    units = {name: open(os.path.join(CSRC, name)).read() for name in os.listdir(CSRC) if name.endswith(".hip")}
+    assert all("TPHIP_PI_SPLIT" not in text for text in units.values())
+    driver = units["site_driver.hip"]
+    body = driver[driver.index("int launch_pi_tables("):driver.index("static int take_slot(")]
     assert "p->site.pi_split" in body and "getenv" not in body
     for kernel in ("pi_net_kernel<<<", "pi_interval_kernel<<<", "pi_partial_kernel<<<"):
-        assert tphip.count(kernel) == 1 and kernel in body, kernel
+        assert sum(text.count(kernel) for text in units.values()) == 1 and kernel in body, kernel

@@ -1,7 +1,8 @@
 """The launch decisions of plan creation on the CPU: tapir_amd/csrc/site_launch_plan.hpp compiled with g++ into
 tests/native/site_launch_dump.cpp, an occupancy table in place of the device query.  Every expected value below was worked
 out by hand from the rules (their statement order included), for a device of 256 CUs; none comes from the code under test.
-The workspace layout is restated here independently: region sizes in order, each rounded up to 256 bytes, plus 256."""
+The workspace layout is restated here independently: region sizes in order, each rounded up to 256 bytes, plus 256.  So are the
+arguments of every site-rate launch (site_kernel_args), which the launch code takes from the same header."""
 import os
 import subprocess
 
@@ -98,6 +99,38 @@ CASES = {
 }
 
 
+# What launch_site_rates hands to the kernel at every launch (site_kernel_args), worked out by hand from the decisions above and
+# the rules, in their order:
+#   variant      2 / 8 words in registers, else the streamed words (STREAM; STREAM_SPILL when lds_depth < stack depth); MIXED + in mixed mode
+#   LDS          lds(lds_depth), mixed_lds(stack depth) in mixed mode
+#   grid         waves in mixed mode, the slices (n_site_chunks) when not persistent, else waves x grid_mult (no case has later shares
+#                spelled out by the knob, which alone make it larger)
+#   persistent   persistent or mixed;  first_round = waves;  tail_order only when persistent, not mixed and not switched off
+#   fraction     first_fraction where > 0, else 1 / grid_mult; then 1.0 in mixed mode
+#   main_shares  waves with reserved tails (reserve_q > 0), else waves x grid_mult
+#   second_list  whenever the plan is not persistent (the mixed mode is not: it only launches as persistent)
+# columns: variant, LDS bytes, grid, persistent, first_round, first_fraction, tail_order, share_work, main_shares, spill, second_list
+ARG_KEYS = ("variant", "lds_bytes", "grid", "persistent", "first_round", "first_fraction", "tail_order", "share_work", "main_shares",
+            "spill", "second_list")
+LAUNCH_ARGS = {
+    "A": (8, lds(3), 6144, 1, 2048, 0.8, 1, 1, 2048, 0, 0),        # reserve 9830 > 0: the 2048 first shares are the main ones
+    "B": (8, lds(3), 6144, 1, 2048, 0.9, 1, 0, 6144, 0, 0),        # no reserve: all 2048 x 3 shares are main shares
+    "C": (STREAM_SPILL, lds(3), 6144, 1, 2048, 0.8, 1, 0, 6144, 1, 0),   # 32 words, three of four partials in LDS
+    "D": (MIXED + 2, mixed_lds(2), 2048, 1, 2048, 1.0, 0, 0, 2048, 0, 1),   # 0.0 -> 1 / 1, and 1.0 anyway; not persistent: second list
+    "E": (8, lds(3), 3800, 0, 2048, 1.0, 0, 0, 2048, 0, 1),        # slices: the grid is the 3800 slices; 0.0 -> 1 / 1
+    "F": (MIXED + 8, mixed_lds(3), 1024, 1, 1024, 1.0, 0, 0, 1024, 0, 1),
+    "G": (STREAM, lds(4), 4608, 1, 1536, 0.9, 1, 0, 4608, 0, 0),   # lds_depth = stack depth: no spill
+    "H": (8, lds(3), 48, 1, 16, 0.8, 1, 1, 16, 0, 0),              # reserve 16384 > 0: 16 main shares of 48
+    "I": (8, lds(3), 6144, 1, 2048, 0.8, 1, 0, 6144, 0, 0),        # A without the reserve
+    "J": (8, lds(3), 6144, 1, 2048, 0.9, 1, 0, 6144, 0, 0),        # as B: the compaction is not the kernel's business
+    "K": (MIXED + 2, mixed_lds(2), 100, 1, 100, 1.0, 0, 0, 100, 0, 1),
+    "L": (STREAM, lds(4), 40000, 0, 1536, 1.0, 0, 0, 1536, 0, 1),  # the spill taken back: 40000 slices, 1536 x 1 main shares
+    "M": (8, lds(3), 6144, 1, 2048, 0.8, 0, 1, 2048, 0, 0),        # A with TPHIP_SITE_TAIL_ORDER=0
+}
+assert sorted(LAUNCH_ARGS) == sorted(CASES)
+BASE_VARIANT = {2: 2, 8: 8, 32: STREAM}   # site_variant by the shape's packed words
+
+
 def build_dump(out_dir, extra=()):
     exe = os.path.join(str(out_dir), "site_launch_dump")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I" + os.path.join(ROOT, "tapir_amd", "csrc"),
@@ -113,14 +146,15 @@ def dump_input(c):
     return "\n".join(lines) + "\n"
 
 
+def run_dump(exe, c):
+    text = subprocess.run([exe], input=dump_input(c), capture_output=True, text=True, check=True).stdout
+    return dict(line.split(" ", 1) for line in text.splitlines())
+
+
 @pytest.fixture(scope="module")
 def dumped(tmp_path_factory):
     exe = build_dump(tmp_path_factory.mktemp("site_launch"))
-    out = {}
-    for name, c in CASES.items():
-        text = subprocess.run([exe], input=dump_input(c), capture_output=True, text=True, check=True).stdout
-        out[name] = dict(line.split(" ", 1) for line in text.splitlines())
-    return out
+    return {name: run_dump(exe, c) for name, c in CASES.items()}
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -132,6 +166,29 @@ def test_decisions(dumped, name):
     assert got["chunk_tables_ok"] == "1"
     assert int(got["lds_bytes"]) == lds(c["expected"]["lds_depth"])
     assert int(got["mixed_lds_bytes"]) == mixed_lds(SHAPES[c["shape"]][2])
+
+
+def check_launch_args(got, name):
+    for key, want in zip(ARG_KEYS, LAUNCH_ARGS[name]):
+        assert float(got["args." + key]) == want, (name, key, got["args." + key], want)
+    assert int(got["site_variant"]) == BASE_VARIANT[SHAPES[CASES[name]["shape"]][1]]
+    assert int(got["args.grid"]) == CASES[name]["expected"]["grid"]
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_launch_arguments(dumped, name):
+    check_launch_args(dumped[name], name)
+
+
+def test_dump_program_under_sanitizers(tmp_path):
+    """Every case once more through the decision code and the launch arguments under AddressSanitizer and UBSan (a stand-alone
+    executable)."""
+    exe = build_dump(tmp_path, extra=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    for name in sorted(CASES):
+        got, c = run_dump(exe, CASES[name]), CASES[name]
+        for key, want in c["expected"].items():
+            assert float(got[key]) == want, (name, key, got[key], want)
+        check_launch_args(got, name)
 
 
 def restated_layout(c):
@@ -194,3 +251,15 @@ def test_decision_code_reads_no_environment():
     for name in os.listdir(csrc):
         if name.endswith(".hip"):
             assert "12 * kSiteBlock) * sizeof(double)" not in open(os.path.join(csrc, name)).read(), name
+
+
+def test_variant_rule_is_written_once():
+    """The launcher variant by the packed words is site_variant in the decision header; no .hip file restates it."""
+    csrc = os.path.join(ROOT, "tapir_amd", "csrc")
+    assert open(os.path.join(csrc, "site_launch_plan.hpp")).read().count("nwords <= 2 ? 2") == 1
+    hips = [name for name in os.listdir(csrc) if name.endswith(".hip")]
+    assert "site_driver.hip" in hips and "eb_driver.hip" in hips
+    for name in hips:
+        assert "nwords <= 2 ? 2" not in open(os.path.join(csrc, name)).read(), name
+    assert "site_variant(" in open(os.path.join(csrc, "eb_driver.hip")).read()
+    assert "site_kernel_args(" in open(os.path.join(csrc, "site_driver.hip")).read()
