@@ -560,6 +560,50 @@ int tphip_unequal_quartet_sites(tphip_plan *plan, const double *rates, const int
                                 const tphip_unequal_quartet_opts *opts, double *sites);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact quartet resolution probabilities (an extension): the law of the counts themselves in place of the bivariate-normal
+ * approximation of the two sections above.  Input: the dense per-site planes y, x1, x2, each [n_q][ncols], exactly as
+ * tphip_unequal_quartet_sites_dev writes them (d_sites, d_sites + n_q * ncols, d_sites + 2 * n_q * ncols); an equal-tip
+ * quartet passes the x plane of tphip_quartet_sites_dev for both x1 and x2.  The plan gives the loci's column ranges and the
+ * device; its models and rates play no part.  Every entry must be a probability (y, x1, x2 >= 0, y + x1 + x2 <= 1).
+ *
+ * Per site, independently, (D1, D2) = (S - N1, S - N2) moves by (+1, +1) with probability y, by (-1, 0) with x1, by (0, -1)
+ * with x2 and not at all otherwise.  The characteristic function on the M x M torus, Phi[k1, k2] = prod over the locus'
+ * sites of (p0 + y z1 z2 + x1 conj(z1) + x2 conj(z2)), z_j = exp(2 pi i k_j / M), is summed against the separable weights of
+ * the regions  correct: D1 > 0 and D2 > 0;  ac: D1 < 0 and D1 < D2;  ad: D2 < 0 and D2 < D1;  polytomy: the rest  -- over
+ * windows of M values centred at the rounded means of D1, D2 and D2 - D1.  M is the smallest of 16, 32, ..., window_cap for
+ * which Bernstein's bound on the mass outside the windows,
+ *   tail_bound = sum over V in {Var D1, Var D2, Var (D2 - D1)} of 2 exp(-t^2 / (2 (V + t / 3))),  t = M / 2 - 1
+ * (a variance of exactly 0 adds nothing), is at most tail_tolerance.
+ *
+ * Row per (locus, quartet), 6 doubles, rows [nloci][n_q][6]: p_correct, p_ac, p_ad, p_polytomy, window (M), tail_bound.  The
+ * probabilities are exact up to tail_bound and rounding, each clamped to [0, 1], p_polytomy = max(0, 1 - the other three).
+ * A pair for which no M up to window_cap meets the tolerance is not computed: NaN in the four probabilities, window = 0 and
+ * tail_bound the bound at window_cap -- a truncated answer is never reported.  An empty or fully culled locus gives
+ * (0, 0, 0, 1), window 16, tail_bound 0.
+ *
+ * Determinism: a row depends on its locus' planes and on window_cap and tail_tolerance only -- not on the other loci of the
+ * plan, on the other quartets of the call or their order, on how a batch is sharded or on the GPU count.  Every sum has a
+ * fixed shape and order; there are no floating-point atomics.  Calls on one plan may overlap if their workspaces differ.
+ * Errors are TPHIP_ERR_INVALID throughout, a workspace below tphip_quartet_exact_workspace_bytes() included; nloci * n_q is
+ * at most 2^24 per call. */
+typedef struct tphip_quartet_exact_opts {
+    uint32_t struct_size;      /* sizeof(tphip_quartet_exact_opts) of the caller */
+    int32_t n_q;               /* quartets: the planes' row count, 1..256 */
+    int32_t window_cap;        /* largest M allowed: a power of two in 16..512; 0 = 128 */
+    double tail_tolerance;     /* in (0, 1); 0 = 1e-12 */
+} tphip_quartet_exact_opts;
+
+/* bytes of device workspace (8-byte aligned) tphip_quartet_exact_dev needs for these options */
+int tphip_quartet_exact_workspace_bytes(const tphip_plan *plan, const tphip_quartet_exact_opts *opts, size_t *bytes);
+/* d_rows [nloci][n_q][6].  Enqueues on `stream`, does not synchronise, copies nothing: it can be captured. */
+int tphip_quartet_exact_dev(tphip_plan *plan, const double *d_y, const double *d_x1, const double *d_x2,
+                            const tphip_quartet_exact_opts *opts, double *d_rows, void *d_workspace, size_t workspace_bytes,
+                            void *stream);
+/* host-pointer twin: the library allocates its own buffers; x1 == x2 is uploaded once */
+int tphip_quartet_exact(tphip_plan *plan, const double *y, const double *x1, const double *x2,
+                        const tphip_quartet_exact_opts *opts, double *rows);
+
+/* ------------------------------------------------------------------------------------------------
  * Parametric bootstrap of the site rates and the PI rows (an extension).  The site bootstrap above resamples columns with
  * their rates held fixed; this one asks how noisy the rates themselves are: every column is simulated down the plan's tree
  * under the locus' model at the column's own rate, with the observed pattern of missing cells, its rate is re-estimated by

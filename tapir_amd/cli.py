@@ -10,7 +10,8 @@ Same positionals, same required/optional flags and defaults, same output directo
 phylogenetic-informativeness-bootstrap.sqlite; the other outputs stay byte for byte the same), --quartets (quartet signal
 and noise in another file of its own, phylogenetic-informativeness-quartets.sqlite; again nothing else changes),
 --unequal-quartets / --tree-quartets (the same for quartets with four tip lengths of their own, typed or read off the input
-tree's internodes, in phylogenetic-informativeness-unequal-quartets.sqlite),
+tree's internodes, in phylogenetic-informativeness-unequal-quartets.sqlite), --exact-quartets / --exact-quartets-window (the
+exact resolution probabilities beside the normal approximation: a table quartet_exact in those quartet files),
 --parametric-bootstrap / --parametric-bootstrap-seed / --parametric-bootstrap-level (the rates re-estimated on simulated
 alignments: bands in phylogenetic-informativeness-parametric-bootstrap.sqlite, per-site moments in NAME.rates-bootstrap.json).
 
@@ -139,7 +140,26 @@ def get_args(argv=None):
                           "around it (rows node1, node2, ... in post-order, after any --unequal-quartets rows; the clades are "
                           "listed in the file's table `clade`).  No depth check either: a lineage through the parent can be "
                           "nearly twice the tree's depth")
+    new.add_argument('--exact-quartets', default=False, action='store_true',
+                     help="beside the normal approximation of --quartets, --unequal-quartets and --tree-quartets, the exact "
+                          "probabilities from the law of the site counts itself (a table `quartet_exact` in each quartet "
+                          "database the run writes: p_correct, p_incorrect or p_ac and p_ad, p_polytomy, the window used and "
+                          "the bound on the mass outside it; exact to that bound and rounding).  Matters for loci with few "
+                          "expected signal sites, where the approximation is off by up to 0.05.  Needs one of those flags")
+    new.add_argument('--exact-quartets-window', type=int, default=None, metavar='M',
+                     help="largest window of --exact-quartets, a power of two in 16..512 (default 128: variances of the count "
+                          "differences up to about 46); a locus and quartet that need a larger one get NULL probabilities "
+                          "and window 0, never a truncated answer.  Needs --exact-quartets")
     args = parser.parse_args(argv)
+    if args.exact_quartets:
+        if args.quartets is None and args.unequal_quartets is None and not args.tree_quartets:
+            parser.error("--exact-quartets needs --quartets, --unequal-quartets or --tree-quartets")
+        if args.exact_quartets_window is None:
+            args.exact_quartets_window = 128
+        if args.exact_quartets_window not in (16, 32, 64, 128, 256, 512):
+            parser.error("--exact-quartets-window must be a power of two in 16..512")
+    elif args.exact_quartets_window is not None:
+        parser.error("--exact-quartets-window needs --exact-quartets")
     for flag, given in (('--quartets', args.quartets is not None), ('--unequal-quartets', args.unequal_quartets is not None),
                         ('--tree-quartets', args.tree_quartets)):
         if given and args.site_rates and args.site_model == 'locus' and args.exchangeabilities is None:
@@ -540,9 +560,16 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
         rows = pipeline.quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent, blen, leaf, T,
                                        args.device, lengths, model=models["model"])
         all_rows = _gather_rows(rows.reshape(len(ids), 8 * len(labels)), len(files), rank, world, on_gpu)
+        if args.exact_quartets:
+            exact = pipeline.exact_quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent, blen,
+                                                  leaf, T, args.device, lengths, model=models["model"],
+                                                  window_cap=args.exact_quartets_window)
+            all_exact = _gather_rows(exact.reshape(len(ids), 6 * len(labels)), len(files), rank, world, on_gpu)
         if rank == 0:
-            db.write_quartet_db(os.path.join(args.output, 'phylogenetic-informativeness-quartets.sqlite'), files,
-                                all_rows.reshape(len(files), len(labels), 8), labels, lengths, models["model"])
+            name = os.path.join(args.output, 'phylogenetic-informativeness-quartets.sqlite')
+            db.write_quartet_db(name, files, all_rows.reshape(len(files), len(labels), 8), labels, lengths, models["model"])
+            if args.exact_quartets:
+                db.add_quartet_exact_table(name, all_exact.reshape(len(files), len(labels), 6), labels, args.exact_quartets_window)
     if args.unequal_quartets or args.tree_quartets:
         # (as --quartets; the typed rows first, then the input tree's internodes, read in the tree's original units)
         eng = engine_mod
@@ -562,10 +589,19 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
         # (a tree without an internode and nothing typed: no row to compute or gather, the file says so)
         all_rows = (_gather_rows(rows.reshape(len(ids), 13 * len(labels)), len(files), rank, world, on_gpu) if labels
                     else np.zeros((len(files), 0)))
+        if args.exact_quartets:
+            exact = pipeline.exact_unequal_quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent,
+                                                          blen, leaf, T, args.device, lengths, model=models["model"],
+                                                          window_cap=args.exact_quartets_window)
+            all_exact = (_gather_rows(exact.reshape(len(ids), 6 * len(labels)), len(files), rank, world, on_gpu) if labels
+                         else np.zeros((len(files), 0)))
         if rank == 0:
-            db.write_unequal_quartet_db(os.path.join(args.output, 'phylogenetic-informativeness-unequal-quartets.sqlite'), files,
-                                        all_rows.reshape(len(files), len(labels), 13), labels, lengths, models["model"],
+            name = os.path.join(args.output, 'phylogenetic-informativeness-unequal-quartets.sqlite')
+            db.write_unequal_quartet_db(name, files, all_rows.reshape(len(files), len(labels), 13), labels, lengths, models["model"],
                                         clades=[(q[0], q[1]) for q in of_tree])
+            if args.exact_quartets:
+                db.add_quartet_exact_table(name, all_exact.reshape(len(files), len(labels), 6), labels, args.exact_quartets_window,
+                                           unequal=True)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -169,6 +169,38 @@ def write_quartet_db(db_name, names, rows, labels, quartets, model):
     conn.close()
 
 
+def add_quartet_exact_table(db_name, rows, labels, window_cap, unequal=False):
+    """--exact-quartets: the table quartet_exact and its `meta` rows, added to a quartet database that write_quartet_db or
+    write_unequal_quartet_db (unequal=True) has just written.  rows [L, n_q, 6] from pipeline.exact_quartet_tables
+    (p_correct, p_ac, p_ad, p_polytomy, window, tail_bound).  The equal-tip file stores p_incorrect = p_ac + p_ad, the
+    unequal one p_ac and p_ad; a pair that was not computed (window 0) has NULL probabilities."""
+    import numpy as np
+    conn = sqlite3.connect(db_name)
+    c = conn.cursor()
+    wrong = "p_ac FLOAT, p_ad FLOAT" if unequal else "p_incorrect FLOAT"
+    c.execute("CREATE TABLE quartet_exact (id INT, quartet TEXT, p_correct FLOAT, " + wrong + ", p_polytomy FLOAT, window INT, "
+              "tail_bound FLOAT, FOREIGN KEY(id) REFERENCES loci(id))")
+    keys = [r[0] for r in c.execute("SELECT id FROM loci ORDER BY id").fetchall()]
+    L, n_q = len(keys), len(labels)
+    rows = np.asarray(rows, dtype=np.float64).reshape(L, n_q, 6)
+    out = []
+    for l in range(L):
+        for q in range(n_q):
+            pc, p1, p2, rest, window, bound = rows[l, q].tolist()
+            if window == 0:
+                probs = (None,) * (4 if unequal else 3)
+            else:
+                probs = (pc, p1, p2, rest) if unequal else (pc, p1 + p2, rest)
+            out.append((keys[l], labels[q]) + probs + (int(window), bound))
+    c.executemany("INSERT INTO quartet_exact VALUES (" + ",".join("?" * (8 if unequal else 7)) + ")", out)
+    c.executemany("INSERT INTO meta VALUES (?,?)",
+                  [("exact", "characteristic function of the counts on a window x window torus: exact to tail_bound and rounding"),
+                   ("exact_window_cap", str(int(window_cap))), ("exact_tail_tolerance", "1e-12")])
+    conn.commit()
+    c.close()
+    conn.close()
+
+
 UNEQUAL_QUARTET_DDL = [
     "CREATE TABLE loci (id INTEGER PRIMARY KEY AUTOINCREMENT, locus TEXT)",
     "CREATE TABLE quartet (id INT, quartet TEXT, tip_a FLOAT, tip_b FLOAT, tip_c FLOAT, tip_d FLOAT, internode FLOAT, "

@@ -62,6 +62,10 @@ class UnequalQuartetOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("tips", _vp), ("internode", _vp)]
 
 
+class QuartetExactOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("window_cap", _i32), ("tail_tolerance", _f64)]
+
+
 class SimulateOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("replicate", _i32), ("seed", ctypes.c_uint64), ("locus_ids", _vp)]
 
@@ -143,6 +147,9 @@ SYMBOLS = [
     ("tphip_unequal_quartet_sites_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(UnequalQuartetOpts), _vp, _vp]),
     ("tphip_unequal_quartet_tables", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(UnequalQuartetOpts), _vp]),
     ("tphip_unequal_quartet_sites", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(UnequalQuartetOpts), _vp]),
+    ("tphip_quartet_exact_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(QuartetExactOpts), ctypes.POINTER(ctypes.c_size_t)]),
+    ("tphip_quartet_exact_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(QuartetExactOpts), _vp, _vp, ctypes.c_size_t, _vp]),
+    ("tphip_quartet_exact", ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(QuartetExactOpts), _vp]),
     ("tphip_simulate_columns_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp, _vp]),
     ("tphip_simulate_columns", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp]),
     ("tphip_parboot_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ParbootOpts), ctypes.POINTER(ctypes.c_size_t)]),
@@ -254,6 +261,28 @@ def pinned_empty(shape, dtype):
 
 
 _PINNED_HOLDERS = {}
+
+
+# Device buffers for callers that chain `_dev` calls without holding torch themselves (pipeline.exact_quartet_tables): torch
+# tensors on the plan's device, in torch's current stream there.
+def device_empty(shape, device, dtype=np.float64):
+    import torch
+    return torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=torch.device("cuda", int(device)))
+
+
+def device_array(a, device):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", int(device)))
+
+
+def host_array(t):
+    """numpy copy of a device buffer (waits for the work enqueued on its stream)."""
+    return t.cpu().numpy()
+
+
+def device_stream(device):
+    import torch
+    return torch.cuda.current_stream(int(device)).cuda_stream
 
 
 class Plan:
@@ -776,6 +805,43 @@ class Plan:
         """tphip_unequal_quartet_sites_dev on device tensors: d_sites [3, n_q, ncols]; enqueues, does not synchronise."""
         opts, keep = self._unequal_quartet_opts(quartets)
         _check(self._lib.tphip_unequal_quartet_sites_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
+
+    # ---- exact quartet resolution probabilities (csrc/exact_quartet_driver.hip) -------------------
+    @staticmethod
+    def _quartet_exact_opts(n_q, window_cap, tail_tolerance):
+        return QuartetExactOpts(struct_size=ctypes.sizeof(QuartetExactOpts), n_q=int(n_q), window_cap=int(window_cap),
+                                tail_tolerance=float(tail_tolerance))
+
+    def quartet_exact_workspace_bytes(self, n_q, window_cap=128):
+        """bytes of device workspace for quartet_exact_dev with n_q quartets and this cap."""
+        opts = self._quartet_exact_opts(n_q, window_cap, 0.0)
+        n = ctypes.c_size_t()
+        _check(self._lib.tphip_quartet_exact_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
+        return n.value
+
+    def quartet_exact(self, y, x1, x2, window_cap=128, tail_tolerance=0.0):
+        """The exact law of the quartet counts from the per-site planes (tphip_quartet_exact): y, x1, x2 [n_q, ncols] as
+        unequal_quartet_sites returns them; an equal-tip quartet passes quartet_sites' x for both (the same array: it is then
+        uploaded once).  Returns rows [L, n_q, 6]: p_correct, p_ac, p_ad, p_polytomy, window, tail_bound; a pair whose law
+        does not fit a window of window_cap (a power of two in 16..512) within tail_tolerance (0: 1e-12) has NaN in the four
+        probabilities and window 0."""
+        same = x2 is x1
+        y, x1 = _np(y, np.float64), _np(x1, np.float64)
+        x2 = x1 if same else _np(x2, np.float64)
+        if y.ndim != 2 or y.shape[1] != self.ncols or x1.shape != y.shape or x2.shape != y.shape:
+            raise TphipError("y, x1 and x2 must be [n_q, ncols] planes of one shape")
+        opts = self._quartet_exact_opts(y.shape[0], window_cap, tail_tolerance)
+        rows = np.zeros((self.nloci, y.shape[0], 6))
+        _check(self._lib.tphip_quartet_exact(self._h, y.ctypes.data, x1.ctypes.data, x2.ctypes.data, ctypes.byref(opts),
+                                             rows.ctypes.data))
+        return rows
+
+    def quartet_exact_dev(self, d_y, d_x1, d_x2, n_q, d_rows, d_ws, window_cap=128, tail_tolerance=0.0, stream=0):
+        """tphip_quartet_exact_dev on device tensors: d_y, d_x1, d_x2 [n_q, ncols] (views of a *_sites_dev buffer), d_rows
+        [L, n_q, 6]; enqueues, does not synchronise."""
+        opts = self._quartet_exact_opts(n_q, window_cap, tail_tolerance)
+        _check(self._lib.tphip_quartet_exact_dev(self._h, _ptr(d_y), _ptr(d_x1), _ptr(d_x2), ctypes.byref(opts), _ptr(d_rows),
+                                                 _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
 
     # ---- parametric bootstrap of site rates and PI rows (csrc/simulate_driver.hip) ---------------
     def _ids(self, locus_ids):

@@ -939,6 +939,76 @@ def unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, l
         plan.close()
 
 
+# exact_quartet_tables works through the quartets in tiles: the dense per-site planes of a tile ([2 or 3][tile][ncols] doubles)
+# and the exact call's workspace each stay within this many bytes of device memory
+EXACT_QUARTET_BYTES = 256 << 20
+
+
+def exact_quartet_tile(L, ncols, n_q, planes, window_cap):
+    """Quartets per tile: the most (up to the engine's 256) for which the planes and the workspace of the exact call (32 bytes
+    per (locus, quartet) pair and 24 per pair and tile of 512 frequencies at the cap) each fit EXACT_QUARTET_BYTES, and the
+    call's pairs its limit of 2^24; at least one."""
+    tiles = (window_cap * (window_cap // 2 + 1) + 511) // 512
+    fit = min(EXACT_QUARTET_BYTES // max(1, 8 * planes * ncols), EXACT_QUARTET_BYTES // max(1, L * (32 + 24 * tiles)),
+              (1 << 24) // max(1, L))
+    return int(max(1, min(256, n_q, fit)))
+
+
+def _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model, window_cap, unequal):
+    L, n_q = len(per_locus), len(quartets)
+    if L == 0 or n_q == 0:
+        return np.zeros((L, n_q, 6))
+    if model not in ("gtr", "f81"):
+        raise PipelineError("unknown model %r" % (model,))
+    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
+    if model == "gtr":
+        exch = np.asarray(exch, dtype=np.float64)
+        exch = np.tile(exch, (L, 1)) if exch.ndim == 1 else exch.reshape(L, 6)
+    else:
+        exch = None
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
+    ncols, planes = int(offsets[-1]), 3 if unequal else 2
+    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, [], [], correction=1.0, threshold=0,
+                    round_decimals=-1, device=device, model=model)
+    try:
+        tile = exact_quartet_tile(L, ncols, n_q, planes, window_cap)
+        stream = eng.device_stream(device)
+        d_rates = eng.device_array(np.concatenate(per_locus), device)
+        d_flat = eng.device_empty((planes * tile * ncols,), device)
+        d_ws = eng.device_empty((plan.quartet_exact_workspace_bytes(tile, window_cap),), device, np.uint8)
+        out = np.zeros((L, n_q, 6))
+        for q0 in range(0, n_q, tile):
+            part = quartets[q0:q0 + tile]
+            k = len(part)
+            d_sites = d_flat[:planes * k * ncols].reshape(planes, k, ncols)   # (a view: the last tile may be shorter)
+            (plan.unequal_quartet_sites_dev if unequal else plan.quartet_sites_dev)(d_rates, None, part, d_sites, stream)
+            d_rows = eng.device_empty((L, k, 6), device)
+            plan.quartet_exact_dev(d_sites[0], d_sites[1], d_sites[planes - 1], k, d_rows, d_ws, window_cap, 0.0, stream)
+            out[:, q0:q0 + k] = eng.host_array(d_rows)
+        return out
+    finally:
+        plan.close()
+
+
+def exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr", window_cap=128):
+    """Exact resolution probabilities beside quartet_tables: rows [L, n_q, 6] (p_correct, p_ac, p_ad, p_polytomy, window,
+    tail_bound) from the same final rates on the same no-rounding plan.  Per tile of quartets
+    (exact_quartet_tile) the per-site planes are written by quartet_sites_dev and read by quartet_exact_dev where they lie;
+    only the rows leave the device.  With equal tips p_ac = p_ad up to rounding (one noise plane serves both).  A pair whose
+    law does not fit window_cap has NaN probabilities and window 0.  A locus' rows depend on its rates, its model, the
+    quartet and window_cap only."""
+    return _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device,
+                                 np.asarray(quartets, dtype=np.float64).reshape(-1, 2), model, window_cap, False)
+
+
+def exact_unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr",
+                                 window_cap=128):
+    """exact_quartet_tables for quartets [n_q, 5] (Ta, Tb, Tc, Td, t_o) beside unequal_quartet_tables; a list longer than the
+    engine's 256 goes through in tiles like any other."""
+    return _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device,
+                                 np.asarray(quartets, dtype=np.float64).reshape(-1, 5), model, window_cap, True)
+
+
 def _tuples(names, per_locus, tables, T, times, intervals):
     n_t, n_i = len(times), len(intervals)
     out = []
