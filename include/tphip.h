@@ -342,7 +342,12 @@ int tphip_state_histogram(int32_t device, const uint8_t *states, int64_t ncols_t
  * [ntaxa][*out_npatterns] taxon-major (the buffer must hold ntaxa * ncols_total bytes), out_offsets [nloci+1] pattern
  * offsets per locus, out_weight [*out_npatterns] column counts (buffer of ncols_total doubles), out_map [ncols_total]
  * column -> pattern index (may be NULL).  Patterns of a locus are in hash order, deterministic for given input.
- * Exact: equality is decided on the full columns, hashes only group candidates.  Plan-less, host pointers. */
+ * Exact: equality is decided on the full columns, hashes only group candidates.  Guaranteed:
+ *   - columns that differ are NEVER merged into one pattern, whatever their hashes;
+ *   - the columns of a pattern are never split over several patterns, except when another pattern of the same locus
+ *     shares BOTH of the library's hashes with it (40 bits of the first and all 64 of the second, ~2^-104 per pair of
+ *     patterns); the counts then still add up to the locus' columns, so weighted likelihoods stay right.
+ * Plan-less, host pointers. */
 int tphip_compress_columns(int32_t device, const uint8_t *states, int64_t ncols_total, int32_t ntaxa,
                            const int64_t *locus_offsets, int64_t nloci, uint8_t *out_states, int64_t *out_offsets,
                            double *out_weight, int64_t *out_map, int64_t *out_npatterns);

@@ -20,13 +20,14 @@ static int compress_core(const uint8_t* d_s, int64_t ncols_total, int32_t ntaxa,
     uint64_t* d_key = tmp.get<uint64_t>(n);
     uint64_t* d_key2 = tmp.get<uint64_t>(n);
     uint64_t* d_h2 = tmp.get<uint64_t>(n);
+    uint64_t* d_h2_sorted = tmp.get<uint64_t>(n);
     uint32_t* d_col = tmp.get<uint32_t>(n);
     uint32_t* d_col2 = tmp.get<uint32_t>(n);
     int32_t* d_head = tmp.get<int32_t>(n);
     int64_t* d_incl = tmp.get<int64_t>(n);
     int64_t* d_newoff = keep.get<int64_t>((size_t)nloci + 1);
     int64_t* d_map = want_map ? keep.get<int64_t>(n) : nullptr;
-    if (!d_packed || !d_key || !d_key2 || !d_h2 || !d_col || !d_col2 || !d_head || !d_incl || !d_newoff || (want_map && !d_map))
+    if (!d_packed || !d_key || !d_key2 || !d_h2 || !d_h2_sorted || !d_col || !d_col2 || !d_head || !d_incl || !d_newoff || (want_map && !d_map))
         return fail(TPHIP_ERR_HIP, "hipMalloc failed");
     const unsigned blocks = (unsigned)((n + 255) / 256);
     pack_hash_kernel<<<dim3(blocks), dim3(256)>>>(d_s, ncols_total, ntaxa, nwords, d_off, nloci, d_packed, d_key, d_h2, d_col);
@@ -34,13 +35,22 @@ static int compress_core(const uint8_t* d_s, int64_t ncols_total, int32_t ntaxa,
     int locus_bits = 1;
     while (((int64_t)1 << locus_bits) < nloci) ++locus_bits;
     const int end_bit = std::min(64, kPatHashBits + locus_bits);
-    size_t tmp_sort = 0, tmp_scan = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, d_key, d_key2, d_col, d_col2, (int)n, 0, end_bit));
+    // Two stable passes: by the second hash, then by the key.  Within a key the positions are then ordered by hash 2 and, within
+    // that, by column, so equal columns stay adjacent even when another pattern of their locus shares the 40-bit key (sorted by
+    // the key alone, A B A B A would stay interleaved and head_flag_kernel, which looks at the predecessor only, would start
+    // five patterns).
+    size_t tmp_sort2 = 0, tmp_sort = 0, tmp_scan = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort2, d_h2, d_h2_sorted, d_col, d_col2, (int)n, 0, 64));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, d_key2, d_key, d_col2, d_col, (int)n, 0, end_bit));
     HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, d_head, d_incl, (int)n));
-    void* d_tmp = tmp.get<char>(std::max(tmp_sort, tmp_scan));
+    const size_t tmp_bytes = std::max(std::max(tmp_sort2, tmp_sort), tmp_scan);
+    void* d_tmp = tmp.get<char>(tmp_bytes);
     if (!d_tmp) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_sort, d_key, d_key2, d_col, d_col2, (int)n, 0, end_bit));
-    head_flag_kernel<<<dim3(blocks), dim3(256)>>>(d_key2, d_col2, d_h2, d_packed, nwords, ncols_total, d_head);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_sort2, d_h2, d_h2_sorted, d_col, d_col2, (int)n, 0, 64));
+    gather_key_kernel<<<dim3(blocks), dim3(256)>>>(d_key, d_col2, ncols_total, d_key2);   // the keys in hash-2 order
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_sort, d_key2, d_key, d_col2, d_col, (int)n, 0, end_bit));
+    head_flag_kernel<<<dim3(blocks), dim3(256)>>>(d_key, d_col, d_h2, d_packed, nwords, ncols_total, d_head);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_scan, d_head, d_incl, (int)n));
     int64_t npat = 0;
@@ -50,7 +60,7 @@ static int compress_core(const uint8_t* d_s, int64_t ncols_total, int32_t ntaxa,
     double* d_w = keep.get<double>((size_t)npat);
     if (!d_out || !d_count || !d_w) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
     HIP_TRY(hipMemset(d_count, 0, sizeof(int32_t) * (size_t)npat));
-    pattern_scatter_kernel<<<dim3(blocks), dim3(256)>>>(d_col2, d_head, d_incl, d_packed, nwords, ntaxa, ncols_total, npat, d_out,
+    pattern_scatter_kernel<<<dim3(blocks), dim3(256)>>>(d_col, d_head, d_incl, d_packed, nwords, ntaxa, ncols_total, npat, d_out,
                                                       d_count, d_map);
     pattern_offsets_kernel<<<dim3((unsigned)((nloci + 256) / 256)), dim3(256)>>>(d_off, nloci, ncols_total, d_incl, npat, d_newoff);
     count_to_weight_kernel<<<dim3((unsigned)((npat + 255) / 256)), dim3(256)>>>(d_count, npat, d_w);

@@ -7,16 +7,22 @@
 //
 //   pack_hash_kernel : one thread per column walks the taxa (coalesced byte rows), packs the normalised 4-bit state
 //                      masks eight to a word into a column-major row [col][nwords] and hashes the row twice;
-//                      sort key = (locus << 40) | 40 bits of hash 1, so that one radix sort groups equal columns
-//                      of the same locus next to each other while keeping the loci in order;
-//   (rocPRIM radix sort of (key, column) pairs -- stable, so equal columns stay in column order)
+//                      sort key = (locus << 40) | 40 bits of hash 1, so that the sort groups equal columns of the same
+//                      locus next to each other while keeping the loci in order;
+//   (two stable rocPRIM radix sorts of (.., column) pairs: by hash 2, then -- the keys brought along by gather_key_kernel --
+//    by the key.  Positions of one key are then in hash-2 order and, within one hash 2, in column order.  The 40 hash
+//    bits of the key are shared by two DISTINCT patterns of a locus with probability n^2 / 2^41 for n patterns (0.5 % at
+//    100 000); sorted by the key alone, their columns A B A B A would stay interleaved)
 //   head_flag_kernel : a sorted position starts a new pattern unless key, second hash AND the full packed row equal
-//                      its predecessor's (exact: a hash collision can only cost compression, never merge columns);
+//                      its predecessor's.  The comparison of the rows makes "never merge" unconditional.  A pattern is
+//                      split -- its columns come out as several patterns with the same states, the counts still adding
+//                      up, so likelihoods stay right but the patterns are no longer unique -- only when another pattern
+//                      of its locus shares the key AND all 64 bits of hash 2 and their columns interleave;
 //   (rocPRIM inclusive scan of the flags = pattern index + 1)
 //   scatter_kernel   : pattern p's states (unpacked back to taxon-major bytes), its count, and the column -> pattern map.
 //
 // HBM-bound byte/integer work: ntaxa bytes read + ntaxa/2 bytes written per column by the pack pass, then
-// O(ntaxa/2) bytes per column for the comparisons; the sort moves 12 bytes per column per radix pass.
+// O(ntaxa/2) bytes per column for the comparisons; the sorts move 12 bytes per column per radix pass.
 // Included by pattern_driver.hip only (a __global__ definition must live in one translation unit); the de-duplication inside
 // the stage-2 pass is in dedup_kernels.hpp.
 #pragma once
@@ -75,6 +81,13 @@ __global__ __launch_bounds__(256) void pack_hash_kernel(const uint8_t* states, i
     key[c] = (locus << kPatHashBits) | (h1 & ((1ull << kPatHashBits) - 1));
     hash2[c] = h2;
     col_index[c] = (uint32_t)c;
+}
+
+// key_by_pos[i] = key of the column at sorted position i (between the two sort passes)
+__global__ __launch_bounds__(256) void gather_key_kernel(const uint64_t* key, const uint32_t* col_sorted, int64_t ncols,
+                                                        uint64_t* key_by_pos) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < ncols) key_by_pos[i] = key[col_sorted[i]];
 }
 
 __global__ __launch_bounds__(256) void head_flag_kernel(const uint64_t* key_sorted, const uint32_t* col_sorted,

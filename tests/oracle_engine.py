@@ -16,7 +16,7 @@ def state_histogram(states, locus_offsets, device=0):
     hist = np.zeros((L, 16), np.int64)
     for l in range(L):
         blk = states[:, locus_offsets[l]:locus_offsets[l + 1]].ravel()
-        blk = np.where(blk == 0, 15, blk & 15)
+        blk = np.where((blk & 15) == 0, 15, blk & 15)   # as the kernel: the low nibble, 0 read as 15
         hist[l] = np.bincount(blk, minlength=16)[:16]
     return hist
 
