@@ -80,10 +80,8 @@ int sim_prepare(tphip_plan* p) {
         s.self = d->leaf_taxon[n] >= 0 ? d->leaf_taxon[n] : ~slot[(size_t)n];
         s.t = d->parent[n] < 0 ? 0.0 : d->branch_len[n];
     }
-    const int32_t words = (nint + 15) / 16;
-    int32_t block = kSimMaxBlock;
-    while (block > kSimMinBlock && (size_t)words * (size_t)block * sizeof(uint32_t) > kSimLdsBytes) block >>= 1;
-    if ((size_t)words * (size_t)block * sizeof(uint32_t) > kSimLdsBytes)
+    int32_t words = 0, block = 0;
+    if (!sim_launch_shape(nint, &words, &block))
         return fail(TPHIP_ERR_INVALID, "tree has " + std::to_string(nint) + " internal nodes: the simulation kernel keeps the 2-bit states of at "
                                        "most 10240 per column (64 columns in 160 KiB of LDS)");
     HIP_TRY(hipSetDevice(p->device));
@@ -125,8 +123,8 @@ int sim_launch(const tphip_plan* p, const double* d_rates, const uint8_t* d_mask
     S.replicate = replicate;
     S.key0 = (uint32_t)seed ^ kSimKeyTag;
     S.key1 = (uint32_t)(seed >> 32);
-    const size_t lds = (size_t)p->sim_words * (size_t)p->sim_block * sizeof(uint32_t);
-    if (lds > 48 * 1024)
+    const size_t lds = sim_lds_bytes(p->sim_words, p->sim_block);
+    if (lds > kSimLdsDefaultBytes)
         HIP_TRY(hipFuncSetAttribute((const void*)simulate_columns_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     simulate_columns_kernel<<<dim3((unsigned)p->n_pi_chunks, (unsigned)(kSimChunk / p->sim_block)), dim3((unsigned)p->sim_block), lds, st>>>(S);
     HIP_TRY(hipGetLastError());

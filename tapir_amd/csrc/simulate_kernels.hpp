@@ -20,14 +20,13 @@
 #include "gtr_model.hpp"
 #include "philox4x32.hpp"
 #include "pi_rate.hpp"
+#include "simulate_launch_shape.hpp"
 #include "transition_row.hpp"
 
 namespace tphip {
 
 constexpr int kSimChunk = 1024;          // the plan's PI chunks (pi_kernels.hpp: kPiChunk): a workgroup never straddles a locus
-constexpr int kSimMaxBlock = 256;
-constexpr int kSimMinBlock = 64;
-constexpr size_t kSimLdsBytes = 160 * 1024;
+// kSimMaxBlock, kSimMinBlock, kSimLdsBytes: simulate_launch_shape.hpp
 constexpr uint32_t kSimKeyTag = 0x73696D75u;   // "simu": the stream is not the site bootstrap's
 constexpr int32_t kSimMaxNodes = 1 << 17;      // (d >> 1) has 16 bits of the counter
 constexpr int32_t kSimMaxReplicate = 1 << 16;  // b has the other 16

@@ -14,6 +14,8 @@ Restated from the definition in DESIGN.md section 3.7 alone, sharing no code wit
 
 The GPU's expm1 and eigen-system differ from numpy's in the last bits, so a draw that falls within 1e-12 c3 of a boundary
 c_k is *undecided*: the mirror reports, per cell, whether every draw on the path from the root was decided.
+
+simulate() goes locus by locus; simulate_all_loci() is the same definition with all loci advanced together, for large trees.
 """
 import numpy as np
 
@@ -133,6 +135,73 @@ def simulate(parent, blen, leaf, ntaxa, offsets, models, rates, locus_ids=None, 
                                     b=b, seed=seed, mask=None if mask is None else mask[:, a:e]))
     return dict(states=np.concatenate([p["states"] for p in parts], axis=1), sure=np.concatenate([p["sure"] for p in parts], axis=1),
                 draws=sum(p["draws"] for p in parts), undecided=sum(p["undecided"] for p in parts))
+
+
+def simulate_all_loci(parent, blen, leaf, ntaxa, offsets, models, rates, locus_ids=None, b=0, seed=1, mask=None):
+    """simulate() with every locus advanced together, one pass over the tree for the whole plan and one Philox call per pair of
+    nodes: for trees of thousands of nodes, where simulate()'s per-locus, per-node calls take minutes.  The same definition
+    and the same keys; the GTR row is summed by einsum instead of a matrix product, which may move a probability by an ulp
+    and with it only a draw that is undecided anyway (tests/test_simulate.py holds the two functions to each other)."""
+    parent, leaf = np.asarray(parent), np.asarray(leaf)
+    blen = np.asarray(blen, np.float64)
+    rates = np.asarray(rates, np.float64)
+    offsets = np.asarray(offsets, np.int64)
+    L, n, nn = len(offsets) - 1, rates.size, len(parent)
+    loc = np.repeat(np.arange(L), np.diff(offsets))
+    ids = np.arange(L) if locus_ids is None else np.array([int(v) for v in locus_ids], object)
+    f81 = models[0]["f81"]
+    pi = np.stack([m["pi"] for m in models])[loc]
+    kappa = np.array([m["kappa"] for m in models])[loc]
+    if not f81:
+        lam = np.stack([m["lam"] for m in models])[loc]
+        U = np.stack([m["U"] for m in models])[loc]
+        Ui = np.stack([m["Ui"] for m in models])[loc]
+    ctr = np.empty((n, 4), np.uint64)
+    ctr[:, 0] = np.arange(n) - offsets[loc]
+    ctr[:, 2] = np.array([int(v) & 0xFFFFFFFF for v in ids], np.uint64)[loc]
+    ctr[:, 3] = np.array([(int(v) >> 32) & 0xFFFFFFFF for v in ids], np.uint64)[loc]
+    key = np.array([(int(seed) & 0xFFFFFFFF) ^ KEY_TAG, (int(seed) >> 32) & 0xFFFFFFFF], np.uint64)
+    bad = ~(rates >= 0.0) | np.isinf(rates)
+    r = np.where(bad, 0.0, rates)
+    cols = np.arange(n)
+    node_state, node_sure = {}, {}
+    states = np.empty((ntaxa, n), np.uint8)
+    sure = np.ones((ntaxa, n), bool)
+    undecided, x, x_of = 0, None, -1
+    for d in range(nn - 1, -1, -1):
+        if x_of != d >> 1:
+            ctr[:, 1] = int(b) | ((d >> 1) << 16)
+            x, x_of = bsr.philox4x32_10(ctr, key).astype(np.uint64), d >> 1
+        lo, hi = (x[:, 2], x[:, 3]) if d & 1 else (x[:, 0], x[:, 1])
+        u = (((hi << np.uint64(32)) | lo) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+        if parent[d] < 0:
+            p, up = pi, np.ones(n, bool)
+        else:
+            s = r * blen[d] / kappa
+            px = node_state[parent[d]]
+            up = node_sure[parent[d]]
+            if f81:
+                w = -np.expm1(-s)
+                p = w[:, None] * pi
+                p[cols, px] += 1.0 - w
+            else:
+                p = np.einsum("nk,nkj->nj", U[cols, px] * np.expm1(s[:, None] * lam), Ui)
+                p[cols, px] += 1.0
+        st, dec = select(p, u)
+        undecided += int((~dec).sum())
+        if leaf[d] < 0:
+            node_state[d], node_sure[d] = st.astype(np.int8), up & dec
+            continue
+        cell = (1 << st).astype(np.uint8)
+        ok = up & dec
+        if mask is not None:
+            m = np.where(mask[leaf[d]] == 0, 15, mask[leaf[d]]).astype(np.uint8)
+            through = ~np.isin(m, [1, 2, 4, 8])
+            cell = np.where(through, m, cell)
+            ok |= through
+        states[leaf[d]] = np.where(bad, 15, cell)
+        sure[leaf[d]] = ok | bad
+    return dict(states=states, sure=sure, draws=nn * n, undecided=undecided)
 
 
 def caterpillar(ntaxa):

@@ -11,6 +11,7 @@ Bounds (stated by the definition, none tuned to the kernels):
                   replicates: mean (B + 2) 2^-52 relative, sd 8 B 2^-52 max |rate| absolute, NaN exactly on the culled columns
   summary         the bounds of test_gpu_bootstrap.py::test_summary_against_numpy
 """
+import functools
 import json
 import os
 import sqlite3
@@ -26,6 +27,8 @@ pytestmark = pytest.mark.gpu
 U = 2.0 ** -52
 SIZES = [1, 63, 64, 65, 1025]            # a lone column, the wave boundaries, a PI-chunk boundary
 IDS = [0, 5, 2 ** 33 + 11, 7, 2 ** 40 + 1]
+BIG_SIZES = [1, 63, 64, 65, 129, 257, 1025]      # and the boundaries of blocks of 128 and 256 threads
+BIG_IDS = IDS + [2 ** 63 - 1, 12]
 MASK_CODES = np.array([1, 2, 4, 8, 15, 0, 5, 10, 14], np.uint8)
 # (replicate, seed, with mask)
 RUNS = [(0, 1, True), (1, 2 ** 40 + 7, False), (4095, 1, True), (1, 1, False)]
@@ -38,6 +41,13 @@ def _engine():
     return engine
 
 
+# Yule trees at the edges of the launch shape (simulate_launch_shape.hpp, tests/test_sim_launch.py), by internal nodes = taxa - 1:
+# 769 the first launch above 48 KiB of LDS, 2561 the first block of 128, 5121 the first block of 64, 10240 the last tree taken
+BIG_TREES = {"yule770": 770, "yule2562": 2562, "yule5122": 5122, "yule10241": 10241}
+BIG_RUNS = [0, 1]            # of RUNS: one with the mask, one without
+
+
+@functools.lru_cache(maxsize=None)
 def tree_arrays(name):
     """(ntaxa, parent, blen, leaf)"""
     if name == "two":
@@ -47,9 +57,10 @@ def tree_arrays(name):
     if name == "caterpillar17":       # 33 nodes: an odd count, 16 internal nodes below the root: the packed states cross a word
         return (17,) + sim.caterpillar(17)
     from tapir_amd import synth
-    root, names = synth.yule_tree(70, 4)
+    ntaxa = BIG_TREES.get(name, 70)
+    root, names = synth.yule_tree(ntaxa, 4)
     pin = synth.plan_inputs(root, names)
-    return 70, pin["parent"], pin["blen"], pin["leaf"]
+    return ntaxa, pin["parent"], pin["blen"], pin["leaf"]
 
 
 def locus_models(kind, L):
@@ -65,19 +76,23 @@ def locus_models(kind, L):
 def byte_case(tree, kind):
     """The inputs of the byte comparison: every rate of the list in every locus that has room for them."""
     ntaxa, parent, blen, leaf = tree_arrays(tree)
-    off = np.concatenate([[0], np.cumsum(SIZES)]).astype(np.int64)
-    pi, exch, models = locus_models(kind, len(SIZES))
+    sizes, ids = (BIG_SIZES, BIG_IDS) if tree in BIG_TREES else (SIZES, IDS)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    pi, exch, models = locus_models(kind, len(sizes))
     rates = np.empty(off[-1])
     for l, m in enumerate(models):
         pattern = np.array([0.0, 1e-9, 0.01, 1.0, 1e4 * m["kappa"], np.nan, -1.0])
-        rates[off[l]:off[l + 1]] = pattern[(np.arange(SIZES[l]) + l) % len(pattern)]
+        rates[off[l]:off[l + 1]] = pattern[(np.arange(sizes[l]) + l) % len(pattern)]
     mask = np.random.default_rng(5).choice(MASK_CODES, size=(ntaxa, int(off[-1])))
-    return dict(ntaxa=ntaxa, parent=parent, blen=blen, leaf=leaf, off=off, pi=pi, exch=exch, models=models, rates=rates, mask=mask)
+    return dict(ntaxa=ntaxa, parent=parent, blen=blen, leaf=leaf, off=off, pi=pi, exch=exch, models=models, rates=rates, mask=mask,
+                ids=ids, big=tree in BIG_TREES)
 
 
 def mirror(c, b, seed, with_mask):
-    return sim.simulate(c["parent"], c["blen"], c["leaf"], c["ntaxa"], c["off"], c["models"], c["rates"], locus_ids=IDS, b=b,
-                        seed=seed, mask=c["mask"] if with_mask else None)
+    """(the big trees: every locus advanced together, simulate_reference.simulate_all_loci -- seconds where simulate takes minutes)"""
+    run = sim.simulate_all_loci if c["big"] else sim.simulate
+    return run(c["parent"], c["blen"], c["leaf"], c["ntaxa"], c["off"], c["models"], c["rates"], locus_ids=c["ids"], b=b, seed=seed,
+               mask=c["mask"] if with_mask else None)
 
 
 def _sim_plan(engine, c, kind, **kw):
@@ -86,18 +101,23 @@ def _sim_plan(engine, c, kind, **kw):
 
 # ---- 1. bytes against the mirror ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["gtr", "f81"])
-@pytest.mark.parametrize("tree", ["two", "trifurcation", "caterpillar17", "yule70"])
+@pytest.mark.parametrize("tree", ["two", "trifurcation", "caterpillar17", "yule70"] + sorted(BIG_TREES, key=BIG_TREES.get))
 def test_bytes_equal_the_mirror(tree, kind):
+    """The four small trees: loci of SIZES columns, all four RUNS.  The Yule trees of BIG_TREES: loci of BIG_SIZES columns and the
+    two runs of BIG_RUNS; with them every launch shape of the simulation has produced bytes -- more than 48 KiB of LDS (769
+    internal nodes), blocks of 128 (2561) and of 64 threads (5121), and the largest tree taken (10240: 160 KiB).  The mirror alone
+    has no undecided draw on any of these inputs (tests/test_simulate.py runs it on the first of them)."""
     engine = _engine()
     c = byte_case(tree, kind)
+    runs = [RUNS[k] for k in BIG_RUNS] if c["big"] else RUNS
     plan = _sim_plan(engine, c, kind)
     try:
-        got = [plan.simulate_columns(c["rates"], mask=c["mask"] if m else None, replicate=b, seed=seed, locus_ids=IDS)
-               for b, seed, m in RUNS]
+        got = [plan.simulate_columns(c["rates"], mask=c["mask"] if m else None, replicate=b, seed=seed, locus_ids=c["ids"])
+               for b, seed, m in runs]
     finally:
         plan.close()
     draws = undecided = 0
-    for (b, seed, m), g in zip(RUNS, got):
+    for (b, seed, m), g in zip(runs, got):
         ref = mirror(c, b, seed, m)
         draws += ref["draws"]
         undecided += ref["undecided"]
@@ -108,7 +128,22 @@ def test_bytes_equal_the_mirror(tree, kind):
         assert wrong == 0
     print("%s %s: %d draws, %d undecided" % (tree, kind, draws, undecided))
     assert undecided <= 1e-6 * draws
-    assert not np.array_equal(got[1], got[3])      # another seed, same replicate: other bytes
+    if not c["big"]:
+        assert not np.array_equal(got[1], got[3])      # another seed, same replicate: other bytes
+
+
+def test_a_tree_of_10241_internal_nodes_is_refused():
+    """One internal node more than 64 columns' packed states fit into 160 KiB: the plan is made, the simulation refuses it."""
+    engine = _engine()
+    parent, blen, leaf = sim.caterpillar(10242)         # (made in no time; a Yule tree of this size takes seconds to draw)
+    plan = engine.Plan(10242, parent, blen, leaf, [0, 64], [[0.25] * 4], [[1.0] * 6], 5, [], [])
+    try:
+        with pytest.raises(engine.TphipError) as e:
+            plan.simulate_columns(np.full(64, 0.1))
+    finally:
+        plan.close()
+    print(str(e.value))
+    assert "10241 internal nodes" in str(e.value) and "10240" in str(e.value)
 
 
 # ---- 2. neighbours and launches ----------------------------------------------------------------------------------

@@ -94,3 +94,25 @@ def test_parser_accepts_and_fills_defaults(tmp_path):
     assert args.bootstrap == 50   # the two bootstraps may be combined
     plain = cli.get_args(_argv(tmp_path))
     assert plain.parametric_bootstrap == 0 and plain.parametric_bootstrap_seed is None
+
+
+@pytest.mark.parametrize("kind", ["gtr", "f81"])
+def test_all_loci_together_equal_locus_by_locus(kind):
+    """simulate_all_loci (what the byte comparison of the large trees uses) against simulate on the inputs of that comparison:
+    yule70 with the loci, stream ids, rates and mask of the large trees, and the first of the large trees cut to its first four
+    loci.  No draw is undecided in either, so the bytes must be the same."""
+    import test_gpu_simulate as tgs
+    c = tgs.byte_case("yule70", kind)
+    big = tgs.byte_case("yule770", kind)
+    cut = dict(big, off=big["off"][:5], models=big["models"][:4], rates=big["rates"][:int(big["off"][4])], ids=big["ids"][:4],
+               mask=big["mask"][:, :int(big["off"][4])])
+    for name, case, ids in (("yule70", c, c["ids"]), ("yule770, four loci", cut, cut["ids"])):
+        for b, seed, m in [tgs.RUNS[k] for k in tgs.BIG_RUNS]:
+            args = (case["parent"], case["blen"], case["leaf"], case["ntaxa"], case["off"], case["models"], case["rates"])
+            kw = dict(locus_ids=ids, b=b, seed=seed, mask=case["mask"] if m else None)
+            one, all_ = sim.simulate(*args, **kw), sim.simulate_all_loci(*args, **kw)
+            print("%s %s b=%d mask=%s: %d cells, %d differ; undecided %d and %d of %d draws"
+                  % (name, kind, b, m, one["states"].size, (one["states"] != all_["states"]).sum(), one["undecided"], all_["undecided"],
+                     one["draws"]))
+            assert one["undecided"] == 0 and all_["undecided"] == 0 and one["draws"] == all_["draws"]
+            assert np.array_equal(one["states"], all_["states"]) and one["sure"].all() and all_["sure"].all()
