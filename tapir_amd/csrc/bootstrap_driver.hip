@@ -271,23 +271,16 @@ int tphip_pi_resample(tphip_plan* p, const double* rates, const int32_t* nres, c
     if (nrows == 0) return TPHIP_OK;
     if (!rows || (n && (!rates || !counts))) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
-    double* d_r = S.get<double>(n);
-    int32_t* d_n = nres ? S.get<int32_t>(n) : nullptr;
-    uint16_t* d_c = S.get<uint16_t>(n * (size_t)nrep);
-    double* d_rows = S.get<double>(nrows);
+    Staging S;
+    const double* d_r = S.in(rates, n);
+    const int32_t* d_n = S.in(nres, n);
+    const uint16_t* d_c = S.in(counts, n * (size_t)nrep);
+    double* d_rows = S.out(rows, nrows);
     const size_t ws_bytes = kBsAlign + std::min(bs_integ_bytes(p, p->ncols), std::max(kBsPreferredCap, bs_integ_bytes(p, p->max_locus_cols)));
-    char* ws = S.get<char>(ws_bytes);
-    if (!d_r || (nres && !d_n) || !d_c || !d_rows || !ws) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    if (n) {
-        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
-        if (nres) HIP_TRY(hipMemcpy(d_n, nres, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_c, counts, sizeof(uint16_t) * n * (size_t)nrep, hipMemcpyHostToDevice));
-    }
+    char* ws = S.scratch<char>(ws_bytes);
+    if (S.rc) return S.rc;
     int rc = tphip_pi_resample_dev(p, d_r, d_n, d_c, nrep, d_rows, ws, ws_bytes, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(rows, d_rows, sizeof(double) * nrows, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 int tphip_pi_bootstrap(tphip_plan* p, const double* rates, const int32_t* nres, const tphip_bootstrap_opts* opts, double* summary,
@@ -302,22 +295,15 @@ int tphip_pi_bootstrap(tphip_plan* p, const double* rates, const int32_t* nres, 
     HIP_TRY(hipSetDevice(p->device));
     size_t mn = 0, pf = 0;
     bs_workspace(p, o.replicates, &mn, &pf);
-    Scratch S;
-    double* d_r = S.get<double>(n);
-    int32_t* d_n = nres ? S.get<int32_t>(n) : nullptr;
-    double* d_sum = S.get<double>(L * 4 * Wb);
-    double* d_rows = rows ? S.get<double>(L * B * Wb) : nullptr;
-    char* ws = S.get<char>(pf);
-    if (!d_r || (nres && !d_n) || !d_sum || (rows && !d_rows) || !ws) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    if (n) {
-        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
-        if (nres) HIP_TRY(hipMemcpy(d_n, nres, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    }
+    Staging S;
+    const double* d_r = S.in(rates, n);
+    const int32_t* d_n = S.in(nres, n);
+    double* d_sum = S.out(summary, L * 4 * Wb);
+    double* d_rows = S.out(rows, L * B * Wb);
+    char* ws = S.scratch<char>(pf);
+    if (S.rc) return S.rc;
     rc = tphip_pi_bootstrap_dev(p, d_r, d_n, opts, d_sum, d_rows, ws, pf, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(summary, d_sum, sizeof(double) * L * 4 * Wb, hipMemcpyDeviceToHost));
-    if (rows) HIP_TRY(hipMemcpy(rows, d_rows, sizeof(double) * L * B * Wb, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 int tphip_bootstrap_counts(int32_t device, uint64_t seed, int64_t locus_id, int64_t n, int64_t rep0, int32_t nrep, uint16_t* counts_out) {
@@ -364,15 +350,12 @@ int tphip_summarize_rows(int32_t device, const double* rows, int64_t nloci, int3
     if (nsum && (!rows || !summary)) return fail(TPHIP_ERR_INVALID, "null host pointer");
     if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
     HIP_TRY(hipSetDevice(device));
-    Scratch S;
-    double* d_rows = S.get<double>(nrows);
-    double* d_sum = S.get<double>(nsum);
-    if (!d_rows || !d_sum) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    if (nrows) HIP_TRY(hipMemcpy(d_rows, rows, sizeof(double) * nrows, hipMemcpyHostToDevice));
+    Staging S;
+    const double* d_rows = S.in(rows, nrows);
+    double* d_sum = S.out(summary, nsum);
+    if (S.rc) return S.rc;
     int rc = tphip_summarize_rows_dev(device, d_rows, nloci, B, Wb, level, d_sum, nullptr);
-    if (rc) return rc;
-    if (nsum) HIP_TRY(hipMemcpy(summary, d_sum, sizeof(double) * nsum, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 }  // extern "C"

@@ -108,23 +108,16 @@ int tphip_quartet_exact(tphip_plan* p, const double* y, const double* x1, const 
     if (nrows == 0) return TPHIP_OK;
     if (!rows || (plane && (!y || !x1 || !x2))) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
+    Staging S;
     const size_t ws_bytes = eq_workspace_bytes(p, o);
-    double* d_y = S.get<double>(plane);
-    double* d_x1 = S.get<double>(plane);
-    double* d_x2 = x2 == x1 ? d_x1 : S.get<double>(plane);   // an equal-tip quartet: one noise plane serves both
-    double* d_rows = S.get<double>(nrows);
-    char* ws = S.get<char>(ws_bytes);
-    if (!d_y || !d_x1 || !d_x2 || !d_rows || !ws) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    if (plane) {
-        HIP_TRY(hipMemcpy(d_y, y, sizeof(double) * plane, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_x1, x1, sizeof(double) * plane, hipMemcpyHostToDevice));
-        if (d_x2 != d_x1) HIP_TRY(hipMemcpy(d_x2, x2, sizeof(double) * plane, hipMemcpyHostToDevice));
-    }
+    const double* d_y = S.in(y, plane);
+    const double* d_x1 = S.in(x1, plane);
+    const double* d_x2 = x2 == x1 ? d_x1 : S.in(x2, plane);   // an equal-tip quartet: one noise plane serves both
+    double* d_rows = S.out(rows, nrows);
+    char* ws = S.scratch<char>(ws_bytes);
+    if (S.rc) return S.rc;
     rc = tphip_quartet_exact_dev(p, d_y, d_x1, d_x2, opts, d_rows, ws, ws_bytes, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(rows, d_rows, sizeof(double) * nrows, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "exact_quartet_window.hpp"
+#include "wave_sum.hpp"
 
 namespace tphip {
 
@@ -63,12 +64,6 @@ struct EqParams {
 
 __host__ __device__ inline int32_t exact_tiles(int32_t m) { return (m * (m / 2 + 1) + kEqTile - 1) / kEqTile; }
 
-__device__ __forceinline__ double eq_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ---- moments and window ----------------------------------------------------------------------------------------------
 // One wave per pair.  Lane l takes the locus' columns l, l + 64, ... in order; the six sums go over the wave by a butterfly
 // (every lane ends with the same bits).  E D1 = sum (y - x1), Var D1 = sum [(y + x1) - (y - x1)^2], likewise D2 with x2 and
@@ -91,12 +86,12 @@ __global__ __launch_bounds__(kEqMomentBlock) void exact_moment_kernel(EqParams P
         v2 += fmax(0.0, fma(-d2, d2, y + b));
         ve += fmax(0.0, fma(-de, de, a + b));
     }
-    m1 = eq_wave_sum(m1);
-    m2 = eq_wave_sum(m2);
-    me = eq_wave_sum(me);
-    v1 = eq_wave_sum(v1);
-    v2 = eq_wave_sum(v2);
-    ve = eq_wave_sum(ve);
+    m1 = wave_sum(m1);
+    m2 = wave_sum(m2);
+    me = wave_sum(me);
+    v1 = wave_sum(v1);
+    v2 = wave_sum(v2);
+    ve = wave_sum(ve);
     if (threadIdx.x != 0) return;
     EqMoment r;
     r.c1 = (int32_t)rint(m1);
@@ -258,7 +253,7 @@ __global__ __launch_bounds__(kEqBlock) void exact_spectrum_kernel(EqParams P) {
         }
 #pragma unroll
         for (int w = 0; w < 3; ++w) {
-            const double v = eq_wave_sum(acc[w]);
+            const double v = wave_sum(acc[w]);
             if (lane == 0) red[3 * wave + w] = v;
         }
         __syncthreads();

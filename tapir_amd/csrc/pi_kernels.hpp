@@ -21,6 +21,7 @@
 #include "site_rate_params.hpp"
 #include "pi_rate.hpp"
 #include "tphip.h"
+#include "wave_sum.hpp"
 
 namespace tphip {
 
@@ -605,12 +606,6 @@ __global__ __launch_bounds__(kCompactChunkBlock) void compact_scatter_kernel(con
             }
         }
     }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 __global__ __launch_bounds__(kPiBlock) void pi_partial_kernel(PiParams P) {

@@ -18,6 +18,7 @@
 
 #include "gtr_model.hpp"
 #include "pi_rate.hpp"
+#include "quartet_common.hpp"
 #include "transition_row.hpp"
 
 namespace tphip {
@@ -102,14 +103,6 @@ __device__ __forceinline__ void quartet_signal_noise(const LocusModel& m, const 
     x = sx;
 }
 
-__device__ __forceinline__ bool quartet_live(double r) { return isfinite(r) && r != 0.0; }   // as nansum: NaN and 0 add exactly 0
-
-__device__ __forceinline__ double quartet_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // One workgroup per 1024-column chunk of a locus, a thread four columns (column = base + j * 256 + thread, as
 // pi_partial_kernel).  The locus' model is wave-uniform: it is read through the scalar cache into SGPRs, once per wave.
 // Quartets go through in tiles of kQtTile: per tile a thread walks its columns and, per column, the tile's quartets in
@@ -123,9 +116,9 @@ __global__ __launch_bounds__(kQtBlock, kQtWavesPerSimd) void quartet_partial_ker
     __shared__ double acc[kQtTile * kQtSums][kQtBlock];
     __shared__ double red[kQtBatch * kQtSums][kQtBlock / 64];
     const int chunk = blockIdx.x;
-    const int locus = P.pi.chunk_locus[chunk];
-    const int64_t lo = P.pi.locus_offsets[locus], hi = P.pi.locus_offsets[locus + 1];
-    const int64_t base = lo + (int64_t)P.pi.chunk_index[chunk] * kQtChunk;
+    const QuartetChunk ch = quartet_chunk<kQtChunk>(P.pi);
+    const int locus = ch.locus;
+    const int64_t hi = ch.hi, base = ch.base;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const LocusModel& model = P.models[locus];
     double r[kQtColsPerThread];
@@ -159,7 +152,7 @@ __global__ __launch_bounds__(kQtBlock, kQtWavesPerSimd) void quartet_partial_ker
             }
         }
         for (int w = 0; w < nk * kQtSums; ++w) {
-            const double v = quartet_wave_sum(acc[w][threadIdx.x]);
+            const double v = wave_sum(acc[w][threadIdx.x]);
             if (lane == 0) red[t0 * kQtSums + w][wave] = v;
         }
     }
@@ -171,10 +164,9 @@ __global__ __launch_bounds__(kQtBlock, kQtWavesPerSimd) void quartet_partial_ker
 // Dense per-site values: sites[0][q][col] = y, sites[1][q][col] = x; a thread is one column at a time and walks the batch's
 // quartets with the same matrix reuse.  Culled and zero-rate columns get exactly 0.
 __global__ __launch_bounds__(kQtBlock, kQtWavesPerSimd) void quartet_sites_kernel(QuartetParams P, QuartetBatch B) {
-    const int chunk = blockIdx.x;
-    const int locus = P.pi.chunk_locus[chunk];
-    const int64_t lo = P.pi.locus_offsets[locus], hi = P.pi.locus_offsets[locus + 1];
-    const int64_t base = lo + (int64_t)P.pi.chunk_index[chunk] * kQtChunk;
+    const QuartetChunk ch = quartet_chunk<kQtChunk>(P.pi);
+    const int locus = ch.locus;
+    const int64_t hi = ch.hi, base = ch.base;
     const LocusModel& model = P.models[locus];
     const bool f81 = P.f81 != 0;
 #pragma unroll 1
@@ -199,26 +191,7 @@ __global__ __launch_bounds__(kQtBlock, kQtWavesPerSimd) void quartet_sites_kerne
 }
 
 // ---- resolution probabilities: bivariate normal with continuity correction ------------------------------------------
-// positive nodes and their weights of the 64-point Gauss-Legendre rule on [-1, 1]
-__device__ const double kGl64X[32] = {
-    0.024350292663424432509, 0.07299312178779903945, 0.12146281929612055447, 0.16964442042399281804,
-    0.21742364374000708415, 0.26468716220876741637, 0.31132287199021095616, 0.35722015833766811595,
-    0.4022701579639916037, 0.44636601725346408798, 0.48940314570705295748, 0.53127946401989454566,
-    0.57189564620263403428, 0.61115535517239325025, 0.64896547125465733986, 0.68523631305423324256,
-    0.71988185017161082685, 0.75281990726053189661, 0.78397235894334140761, 0.81326531512279755974,
-    0.84062929625258036275, 0.86599939815409281976, 0.88931544599511410585, 0.91052213707850280576,
-    0.92956917213193957582, 0.94641137485840281606, 0.96100879965205371892, 0.97332682778991096374,
-    0.98333625388462595693, 0.99101337147674432074, 0.99634011677195527935, 0.99930504173577213946};
-__device__ const double kGl64W[32] = {
-    0.048690957009139720383, 0.048575467441503426935, 0.04834476223480295717, 0.047999388596458307728,
-    0.047540165714830308662, 0.046968182816210017325, 0.046284796581314417296, 0.04549162792741814448,
-    0.04459055816375656306, 0.043583724529323453377, 0.042473515123653589007, 0.04126256324262352861,
-    0.039953741132720341387, 0.038550153178615629129, 0.03705512854024004604, 0.035472213256882383811,
-    0.033805161837141609392, 0.032057928354851553585, 0.030234657072402478868, 0.028339672614259483228,
-    0.026377469715054658672, 0.024352702568710873338, 0.022270173808383254159, 0.020134823153530209372,
-    0.017951715775697343085, 0.015726030476024719322, 0.013463047896718642598, 0.011168139460131128819,
-    0.008846759826363947723, 0.0065044579689783628561, 0.0041470332605624676353, 0.0017832807216964329473};
-
+// (the 64-point Gauss-Legendre rule: kGl64X / kGl64W of quartet_common.hpp)
 __device__ __forceinline__ double quartet_bvn_integrand(double h, double k, double theta) {
     const double s = sin(theta);
     if (h == k) return exp(-(k * k) / (1.0 + s));          // smooth up to rho = 1

@@ -187,19 +187,13 @@ int tphip_simulate_columns(tphip_plan* p, const double* rates, const uint8_t* ma
     const size_t n = (size_t)p->ncols, cells = (size_t)p->ntaxa * n;
     if (n && (!rates || !states_out)) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
-    double* d_r = S.get<double>(n);
-    uint8_t* d_m = mask ? S.get<uint8_t>(cells) : nullptr;
-    uint8_t* d_o = S.get<uint8_t>(cells);
-    if (!d_r || (mask && !d_m) || !d_o) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    if (n) {
-        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
-        if (mask) HIP_TRY(hipMemcpy(d_m, mask, cells, hipMemcpyHostToDevice));
-    }
+    Staging S;
+    const double* d_r = S.in(rates, n);
+    const uint8_t* d_m = S.in(mask, cells);
+    uint8_t* d_o = S.out(states_out, cells);
+    if (S.rc) return S.rc;
     rc = tphip_simulate_columns_dev(p, d_r, d_m, opts, d_o, nullptr);
-    if (rc) return rc;
-    if (n) HIP_TRY(hipMemcpy(states_out, d_o, cells, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 int tphip_parboot_workspace_bytes(const tphip_plan* p, const tphip_parboot_opts* opts, size_t* bytes) {
@@ -273,27 +267,17 @@ int tphip_pi_parametric_bootstrap(tphip_plan* p, const double* rates, const uint
     if (!summary || (n && !rates)) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(p->device));
     const size_t ws_bytes = parboot_layout(p, o.replicates).total;
-    Scratch S;
-    double* d_r = S.get<double>(n);
-    uint8_t* d_s = S.get<uint8_t>(cells);
-    double* d_sum = S.get<double>(L * 4 * Wb);
-    double* d_rows = rows ? S.get<double>(L * B * Wb) : nullptr;
-    double* d_mean = rate_mean ? S.get<double>(n) : nullptr;
-    double* d_sd = rate_sd ? S.get<double>(n) : nullptr;
-    char* ws = S.get<char>(ws_bytes);
-    if (!d_r || !d_s || !d_sum || (rows && !d_rows) || (rate_mean && !d_mean) || (rate_sd && !d_sd) || !ws)
-        return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    if (n) {
-        HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_s, states_observed, cells, hipMemcpyHostToDevice));
-    }
+    Staging S;
+    const double* d_r = S.in(rates, n);
+    const uint8_t* d_s = S.in(states_observed, cells);
+    double* d_sum = S.out(summary, L * 4 * Wb);
+    double* d_rows = S.out(rows, L * B * Wb);
+    double* d_mean = S.out(rate_mean, n);
+    double* d_sd = S.out(rate_sd, n);
+    char* ws = S.scratch<char>(ws_bytes);
+    if (S.rc) return S.rc;
     rc = tphip_pi_parametric_bootstrap_dev(p, d_r, d_s, opts, d_sum, d_rows, d_mean, d_sd, ws, ws_bytes, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(summary, d_sum, sizeof(double) * L * 4 * Wb, hipMemcpyDeviceToHost));
-    if (rows) HIP_TRY(hipMemcpy(rows, d_rows, sizeof(double) * L * B * Wb, hipMemcpyDeviceToHost));
-    if (rate_mean && n) HIP_TRY(hipMemcpy(rate_mean, d_mean, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (rate_sd && n) HIP_TRY(hipMemcpy(rate_sd, d_sd, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 }  // extern "C"

@@ -345,18 +345,14 @@ int tphip_corrected_rates(tphip_plan* p, const double* rates, const int32_t* nre
     if (p->ncols == 0) return TPHIP_OK;
     if (!rates || !out) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(p->device));
-    Scratch S;
+    Staging S;
     const size_t n = (size_t)p->ncols;
-    double* d_r = S.get<double>(n);
-    double* d_o = S.get<double>(n);
-    int32_t* d_n = nres ? S.get<int32_t>(n) : nullptr;
-    if (!d_r || !d_o || (nres && !d_n)) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * n, hipMemcpyHostToDevice));
-    if (nres) HIP_TRY(hipMemcpy(d_n, nres, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    const double* d_r = S.in(rates, n);
+    double* d_o = S.out(out, n);
+    const int32_t* d_n = S.in(nres, n);
+    if (S.rc) return S.rc;
     int rc = tphip_corrected_rates_dev(p, d_r, d_n, d_o, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, d_o, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 int tphip_townsend_pi_dense_dev(int32_t device, const double* d_rates, int64_t n, const double* d_times, int32_t n_times,
@@ -424,17 +420,13 @@ int tphip_quad_townsend(int32_t device, const double* rates, int64_t n, double a
     if (n == 0) return TPHIP_OK;
     if (!rates || !integral || !abserr) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(device));
-    Scratch S;
-    double* d_r = S.get<double>((size_t)n);
-    double* d_i = S.get<double>((size_t)n);
-    double* d_e = S.get<double>((size_t)n);
-    if (!d_r || !d_i || !d_e) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_r, rates, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    Staging S;
+    const double* d_r = S.in(rates, (size_t)n);
+    double* d_i = S.out(integral, (size_t)n);
+    double* d_e = S.out(abserr, (size_t)n);
+    if (S.rc) return S.rc;
     int rc = tphip_quad_townsend_dev(device, d_r, n, a, b, integ_mode, d_i, d_e, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(integral, d_i, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(abserr, d_e, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 int tphip_eval_columns_dev(tphip_plan* p, const uint8_t* d_s, const double* d_u, double* d_f, double* d_g, double* d_h,
@@ -476,18 +468,13 @@ int tphip_state_histogram(int32_t device, const uint8_t* states, int64_t ncols_t
     if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
     if (!states || !locus_offsets || !hist || nloci < 1 || ntaxa < 1 || ncols_total < 0) return fail(TPHIP_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(device));
-    Scratch S;
-    const size_t nb = (size_t)ncols_total * (size_t)ntaxa;
-    uint8_t* d_s = S.get<uint8_t>(nb);
-    int64_t* d_o = S.get<int64_t>((size_t)nloci + 1);
-    int64_t* d_h = S.get<int64_t>(16 * (size_t)nloci);
-    if (!d_s || !d_o || !d_h) return fail(TPHIP_ERR_HIP, "hipMalloc failed");
-    HIP_TRY(hipMemcpy(d_s, states, nb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_o, locus_offsets, sizeof(int64_t) * ((size_t)nloci + 1), hipMemcpyHostToDevice));
+    Staging S;
+    const uint8_t* d_s = S.in(states, (size_t)ncols_total * (size_t)ntaxa);
+    const int64_t* d_o = S.in(locus_offsets, (size_t)nloci + 1);
+    int64_t* d_h = S.out(hist, 16 * (size_t)nloci);
+    if (S.rc) return S.rc;
     int rc = tphip_state_histogram_dev(device, d_s, ncols_total, ntaxa, d_o, nloci, d_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(hist, d_h, sizeof(int64_t) * 16 * (size_t)nloci, hipMemcpyDeviceToHost));
-    return TPHIP_OK;
+    return rc ? rc : S.finish();
 }
 
 }  // extern "C"

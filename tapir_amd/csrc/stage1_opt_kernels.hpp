@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gtr_model.hpp"
+#include "wave_sum.hpp"
 
 namespace tphip {
 namespace s1 {
@@ -50,11 +51,6 @@ struct CandArrays {
     double* out;      // [cap] log-likelihoods
 };
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ inline double wave_max(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));

@@ -110,6 +110,41 @@ struct Scratch {
     }
 };
 
+// The device side of a host-pointer convenience: declare the inputs and outputs, check rc, make the _dev call, finish().
+// After a failure (rc != 0: TPHIP_ERR_HIP, "hipMalloc failed" for an allocation) nothing more is allocated or copied.
+struct Staging {
+    Scratch S;
+    struct Download { void* host; const void* dev; size_t bytes; };
+    std::vector<Download> downloads;
+    int rc = TPHIP_OK;
+    // device buffer of `count` elements, its contents undefined (a workspace)
+    template <typename T> T* scratch(size_t count) {
+        T* d = rc ? nullptr : S.get<T>(count);
+        if (!d && !rc) rc = fail(TPHIP_ERR_HIP, "hipMalloc failed");
+        return d;
+    }
+    // device copy of host[count]; a null host pointer gives a null device pointer, count 0 copies nothing
+    template <typename T> T* in(const T* host, size_t count) {
+        T* d = host ? scratch<T>(count) : nullptr;
+        if (d && count) rc = upload(d, host, sizeof(T) * count);
+        return d;
+    }
+    // device buffer that finish() copies to host[count]; a null host pointer gives a null device pointer
+    template <typename T> T* out(T* host, size_t count) {
+        T* d = host ? scratch<T>(count) : nullptr;
+        if (d && count) downloads.push_back({host, d, sizeof(T) * count});
+        return d;
+    }
+    int upload(void* d, const void* host, size_t bytes) {
+        HIP_TRY(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+        return TPHIP_OK;
+    }
+    int finish() {
+        for (const Download& o : downloads) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
+        return TPHIP_OK;
+    }
+};
+
 struct tphip_host_buffers;
 struct tphip_saved_desc;
 

@@ -21,6 +21,7 @@
 
 #include "gtr_model.hpp"
 #include "pi_rate.hpp"
+#include "quartet_common.hpp"
 #include "transition_row.hpp"
 
 namespace tphip {
@@ -49,14 +50,6 @@ struct UnequalQuartetParams {
     double* sites;               // [3][n_q][ncols]
     int64_t ncols;
 };
-
-__device__ __forceinline__ bool uquartet_live(double r) { return isfinite(r) && r != 0.0; }   // as nansum: NaN and 0 add exactly 0
-
-__device__ __forceinline__ double uquartet_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // (y, x1, x2) of one live site.  C and D are held whole (32 doubles); of A, B and N only what all rows of a matrix share
 // (transition_exps: three numbers each), and row u of each is made where u needs it.  Per u: n C (16 products), R_u (16
@@ -138,9 +131,9 @@ __global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_partial_ke
     __shared__ double rate[kUqColsPerThread][kUqBlock];
     __shared__ double red[kUqBatch * kUqSums][kUqBlock / 64];
     const int chunk = blockIdx.x;
-    const int locus = P.pi.chunk_locus[chunk];
-    const int64_t lo = P.pi.locus_offsets[locus], hi = P.pi.locus_offsets[locus + 1];
-    const int64_t base = lo + (int64_t)P.pi.chunk_index[chunk] * kUqChunk;
+    const QuartetChunk ch = quartet_chunk<kUqChunk>(P.pi);
+    const int locus = ch.locus;
+    const int64_t hi = ch.hi, base = ch.base;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const LocusModel& model = P.models[locus];
 #pragma unroll
@@ -158,7 +151,7 @@ __global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_partial_ke
 #pragma unroll 1
         for (int j = 0; j < kUqColsPerThread; ++j) {
             const double r = rate[j][threadIdx.x];
-            if (!uquartet_live(r)) continue;
+            if (!quartet_live(r)) continue;
             double y, x1, x2;
             uquartet_signal_noise(model, f81, r, ta, tb, tc, td, to, y, x1, x2);
             s[0] += y;
@@ -173,7 +166,7 @@ __global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_partial_ke
         }
 #pragma unroll
         for (int w = 0; w < kUqSums; ++w) {
-            const double v = uquartet_wave_sum(s[w]);
+            const double v = wave_sum(s[w]);
             if (lane == 0) red[q * kUqSums + w][wave] = v;
         }
     }
@@ -185,10 +178,9 @@ __global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_partial_ke
 // Dense per-site values: sites[0][q][col] = y, sites[1][q][col] = x1, sites[2][q][col] = x2; a thread is one column at a
 // time and walks the batch's quartets.  Culled and zero-rate columns get exactly 0.
 __global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_sites_kernel(UnequalQuartetParams P, UnequalQuartetBatch B) {
-    const int chunk = blockIdx.x;
-    const int locus = P.pi.chunk_locus[chunk];
-    const int64_t lo = P.pi.locus_offsets[locus], hi = P.pi.locus_offsets[locus + 1];
-    const int64_t base = lo + (int64_t)P.pi.chunk_index[chunk] * kUqChunk;
+    const QuartetChunk ch = quartet_chunk<kUqChunk>(P.pi);
+    const int locus = ch.locus;
+    const int64_t hi = ch.hi, base = ch.base;
     const LocusModel& model = P.models[locus];
     const bool f81 = P.f81 != 0;
     const size_t plane = (size_t)P.n_q * (size_t)P.ncols;
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_sites_kern
         const int64_t col = base + j * kUqBlock + threadIdx.x;
         if (col >= hi) continue;
         const double r = finalize_rate(P.pi, col);
-        const bool live = uquartet_live(r);
+        const bool live = quartet_live(r);
 #pragma unroll 1
         for (int q = 0; q < P.nq; ++q) {
             double y = 0.0, x1 = 0.0, x2 = 0.0;
@@ -211,25 +203,7 @@ __global__ __launch_bounds__(kUqBlock, kUqWavesPerSimd) void uquartet_sites_kern
 }
 
 // ---- resolution probabilities: bivariate normal with continuity correction ------------------------------------------
-// positive nodes and their weights of the 64-point Gauss-Legendre rule on [-1, 1] (the rule and constants of section 3.6)
-__device__ const double kUqGl64X[32] = {
-    0.024350292663424432509, 0.07299312178779903945, 0.12146281929612055447, 0.16964442042399281804,
-    0.21742364374000708415, 0.26468716220876741637, 0.31132287199021095616, 0.35722015833766811595,
-    0.4022701579639916037, 0.44636601725346408798, 0.48940314570705295748, 0.53127946401989454566,
-    0.57189564620263403428, 0.61115535517239325025, 0.64896547125465733986, 0.68523631305423324256,
-    0.71988185017161082685, 0.75281990726053189661, 0.78397235894334140761, 0.81326531512279755974,
-    0.84062929625258036275, 0.86599939815409281976, 0.88931544599511410585, 0.91052213707850280576,
-    0.92956917213193957582, 0.94641137485840281606, 0.96100879965205371892, 0.97332682778991096374,
-    0.98333625388462595693, 0.99101337147674432074, 0.99634011677195527935, 0.99930504173577213946};
-__device__ const double kUqGl64W[32] = {
-    0.048690957009139720383, 0.048575467441503426935, 0.04834476223480295717, 0.047999388596458307728,
-    0.047540165714830308662, 0.046968182816210017325, 0.046284796581314417296, 0.04549162792741814448,
-    0.04459055816375656306, 0.043583724529323453377, 0.042473515123653589007, 0.04126256324262352861,
-    0.039953741132720341387, 0.038550153178615629129, 0.03705512854024004604, 0.035472213256882383811,
-    0.033805161837141609392, 0.032057928354851553585, 0.030234657072402478868, 0.028339672614259483228,
-    0.026377469715054658672, 0.024352702568710873338, 0.022270173808383254159, 0.020134823153530209372,
-    0.017951715775697343085, 0.015726030476024719322, 0.013463047896718642598, 0.011168139460131128819,
-    0.008846759826363947723, 0.0065044579689783628561, 0.0041470332605624676353, 0.0017832807216964329473};
+// (the rule and constants of section 3.6: kGl64X / kGl64W of quartet_common.hpp)
 
 // h != k: (h - k)^2 / (2 cos^2) + h k / (1 + sin) is (h^2 + k^2 - 2 h k sin) / (2 cos^2) without that numerator's
 // cancellation near theta = pi / 2
@@ -246,8 +220,8 @@ __device__ __forceinline__ double uquartet_bvn_upper(double h, double k, double 
     const double half = 0.5 * asin(rho);
     double sum = 0.0;
     for (int i = 0; i < 32; ++i) {
-        const double d = half * kUqGl64X[i];
-        sum += kUqGl64W[i] * (uquartet_bvn_integrand(h, k, half - d) + uquartet_bvn_integrand(h, k, half + d));
+        const double d = half * kGl64X[i];
+        sum += kGl64W[i] * (uquartet_bvn_integrand(h, k, half - d) + uquartet_bvn_integrand(h, k, half + d));
     }
     const double tail = (0.5 * erfc(h * 0.70710678118654752440)) * (0.5 * erfc(k * 0.70710678118654752440));
     return fmax(0.0, tail + half * sum * 0.15915494309189533577);   // 1 / (2 pi); rho < 0: the two terms cancel, never below 0

@@ -5,6 +5,7 @@ This replaces, for every locus at once, what `worker()` does per locus in the re
 PI arithmetic.  There is deliberately no CPU fallback: if the shared library is missing, or no GPU is
 visible, every entry point raises.
 """
+import collections
 import ctypes
 import os
 
@@ -230,6 +231,18 @@ def _ptr(a):
     return a.data_ptr()
 
 
+def _nbytes(t):
+    """Byte size of a device tensor (a workspace)."""
+    return t.numel() * t.element_size()
+
+
+def _size_out(fn, *args):
+    """fn(*args, &n) of a *_workspace_bytes entry point: n."""
+    n = ctypes.c_size_t()
+    _check(fn(*args, ctypes.byref(n)))
+    return n.value
+
+
 class _Pinned:
     def __init__(self, ptr):
         self.ptr = ptr
@@ -344,6 +357,12 @@ class Plan:
         self.op_counts = dict(zip(("tip_set", "tip_mul", "branch", "push", "pop_mul"), oc.tolist()))
         self.op_counts["cherry"] = int(lib.tphip_plan_cherry_count(self._h))
 
+    def _rates_nres(self, rates, nres=None):
+        """rates as float64 [ncols] and nres as int32 (or None): what the calls on per-column rates take."""
+        rates = _np(rates, np.float64)
+        assert rates.shape == (self.ncols,)
+        return rates, None if nres is None else _np(nres, np.int32)
+
     def close(self):
         if self._h:
             self._lib.tphip_plan_destroy(self._h)
@@ -370,9 +389,7 @@ class Plan:
     def pi_tables(self, rates, nres=None):
         """rates: float64 [ncols] raw rates (rounding, /correction and cull are applied by the kernel).
         Returns tables [L, W]."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
+        rates, nres = self._rates_nres(rates, nres)
         tables = np.empty((self.nloci, self.width))
         _check(self._lib.tphip_pi_tables(self._h, rates.ctypes.data, _ptr(nres), tables.ctypes.data))
         return tables
@@ -479,9 +496,7 @@ class Plan:
 
     def corrected_rates(self, rates, nres=None):
         """parse_site_rates (+ cull when nres is given) as the PI stage applies them: round4(rate) / correction."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
+        rates, nres = self._rates_nres(rates, nres)
         out = np.empty(self.ncols)
         _check(self._lib.tphip_corrected_rates(self._h, rates.ctypes.data, _ptr(nres), out.ctypes.data))
         return out
@@ -618,17 +633,14 @@ class Plan:
     # ---- device-pointer path (torch tensors resident in HBM; nothing is copied or synchronised) --
     def run_dev(self, d_states, d_rate, d_subst, d_lnl, d_flag, d_nres, d_tables, d_ws, stream=0):
         _check(self._lib.tphip_run_dev(self._h, _ptr(d_states), _ptr(d_rate), _ptr(d_subst), _ptr(d_lnl), _ptr(d_flag),
-                                       _ptr(d_nres), _ptr(d_tables), _ptr(d_ws), d_ws.numel() * d_ws.element_size(),
-                                       stream))
+                                       _ptr(d_nres), _ptr(d_tables), _ptr(d_ws), _nbytes(d_ws), stream))
 
     def site_rates_dev(self, d_states, d_rate, d_subst, d_lnl, d_flag, d_nres, d_ws, stream=0):
         _check(self._lib.tphip_site_rates_dev(self._h, _ptr(d_states), _ptr(d_rate), _ptr(d_subst), _ptr(d_lnl),
-                                              _ptr(d_flag), _ptr(d_nres), _ptr(d_ws),
-                                              d_ws.numel() * d_ws.element_size(), stream))
+                                              _ptr(d_flag), _ptr(d_nres), _ptr(d_ws), _nbytes(d_ws), stream))
 
     def pi_tables_dev(self, d_rates, d_nres, d_tables, d_ws, stream=0):
-        _check(self._lib.tphip_pi_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), _ptr(d_tables), _ptr(d_ws),
-                                             d_ws.numel() * d_ws.element_size(), stream))
+        _check(self._lib.tphip_pi_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), _ptr(d_tables), _ptr(d_ws), _nbytes(d_ws), stream))
 
     # ---- site bootstrap of the PI rows (csrc/bootstrap_driver.hip) ------------------------------
     def _bootstrap_opts(self, replicates, seed, level, locus_ids):
@@ -665,9 +677,7 @@ class Plan:
         lo, hi; [lo, hi] covers `level`) and, with return_rows, the replicate rows [L, B, Wb] as a second array.
         locus_ids: the generator's stream id per locus (default: the plan's locus index); a locus gives the same rows
         whatever plan it is part of as long as its id, the seed and its rates are the same."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
+        rates, nres = self._rates_nres(rates, nres)
         opts, ids = self._bootstrap_opts(replicates, seed, level, locus_ids)
         Wb = self.bootstrap_width
         summary = np.zeros((self.nloci, 4, Wb))
@@ -679,9 +689,7 @@ class Plan:
     def pi_resample(self, rates, nres, counts):
         """The weighted-sum core on caller-supplied counts (tphip_pi_resample): counts uint16 [nrep, ncols] over the plan's
         columns -> rows [L, nrep, Wb], rows[l, b] = sum over the locus' columns of counts[b, i] * (site i's PI values)."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
+        rates, nres = self._rates_nres(rates, nres)
         counts = _np(counts, np.uint16)
         if counts.ndim != 2 or counts.shape[1] != self.ncols:
             raise TphipError("counts must be uint16 [nrep, ncols]")
@@ -694,16 +702,18 @@ class Plan:
                          stream=0, ws_bytes=None):
         """tphip_pi_bootstrap_dev on device tensors (d_nres / d_rows may be None); ws_bytes: use only that much of d_ws."""
         opts, ids = self._bootstrap_opts(replicates, seed, level, locus_ids)
-        nbytes = d_ws.numel() * d_ws.element_size() if ws_bytes is None else int(ws_bytes)
+        nbytes = _nbytes(d_ws) if ws_bytes is None else int(ws_bytes)
         _check(self._lib.tphip_pi_bootstrap_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_summary),
                                                 _ptr(d_rows), _ptr(d_ws), nbytes, stream))
 
     def pi_resample_dev(self, d_rates, d_nres, d_counts, nrep, d_rows, d_ws, stream=0):
         """tphip_pi_resample_dev on device tensors: d_counts int16/uint16 [nrep, ncols], d_rows [L, nrep, Wb]."""
         _check(self._lib.tphip_pi_resample_dev(self._h, _ptr(d_rates), _ptr(d_nres), _ptr(d_counts), int(nrep), _ptr(d_rows),
-                                               _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
+                                               _ptr(d_ws), _nbytes(d_ws), stream))
 
-    # ---- quartet signal and noise (csrc/quartet_driver.hip) -------------------------------------
+    # ---- quartet signal and noise: equal tips (csrc/quartet_driver.hip), unequal tips (csrc/unequal_quartet_driver.hip) ----
+    # One implementation per kind of call over a family `fam` (_QuartetFamily below: options builder, symbol prefix, row width,
+    # per-site planes); the public methods name the family.
     @staticmethod
     def _quartet_opts(quartets):
         """quartets: [n_q, 2] rows (T, t_o).  Returns the options and the arrays they point into (keep them alive)."""
@@ -712,48 +722,6 @@ class Plan:
         opts = QuartetOpts(struct_size=ctypes.sizeof(QuartetOpts), n_q=len(q), tip=tip.ctypes.data, internode=internode.ctypes.data)
         return opts, (tip, internode)
 
-    def quartet_workspace_bytes(self, quartets):
-        """bytes of device workspace for quartet_tables_dev with these quartets."""
-        opts, keep = self._quartet_opts(quartets)
-        n = ctypes.c_size_t()
-        _check(self._lib.tphip_quartet_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
-        return n.value
-
-    def quartet_tables(self, rates, nres, quartets):
-        """Signal and noise of the quartets ((a:T, b:T), (c:T, d:T)) with internode t_o under the plan's models
-        (tphip_quartet_tables).  rates / nres as for pi_tables; quartets [n_q, 2] rows (T, t_o) in the tree's original time
-        units.  Returns rows [L, n_q, 8]: Y, X, Yy, Xx, XY, p_correct, p_incorrect, p_polytomy."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
-        opts, keep = self._quartet_opts(quartets)
-        rows = np.zeros((self.nloci, opts.n_q, 8))
-        _check(self._lib.tphip_quartet_tables(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), rows.ctypes.data))
-        return rows
-
-    def quartet_sites(self, rates, nres, quartets):
-        """The per-site values behind quartet_tables (tphip_quartet_sites): [2, n_q, ncols], signal y then noise x; exactly
-        0 for a culled or zero-rate column."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
-        opts, keep = self._quartet_opts(quartets)
-        sites = np.zeros((2, opts.n_q, self.ncols))
-        _check(self._lib.tphip_quartet_sites(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), sites.ctypes.data))
-        return sites
-
-    def quartet_tables_dev(self, d_rates, d_nres, quartets, d_rows, d_ws, stream=0):
-        """tphip_quartet_tables_dev on device tensors (d_nres may be None): d_rows [L, n_q, 8]; enqueues, does not synchronise."""
-        opts, keep = self._quartet_opts(quartets)
-        _check(self._lib.tphip_quartet_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_rows),
-                                                  _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
-
-    def quartet_sites_dev(self, d_rates, d_nres, quartets, d_sites, stream=0):
-        """tphip_quartet_sites_dev on device tensors: d_sites [2, n_q, ncols]; enqueues, does not synchronise."""
-        opts, keep = self._quartet_opts(quartets)
-        _check(self._lib.tphip_quartet_sites_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
-
-    # ---- quartets with unequal tips (csrc/unequal_quartet_driver.hip) ----------------------------
     @staticmethod
     def _unequal_quartet_opts(quartets):
         """quartets: [n_q, 5] rows (Ta, Tb, Tc, Td, t_o).  Returns the options and the arrays they point into (keep them alive)."""
@@ -763,48 +731,80 @@ class Plan:
                                   internode=internode.ctypes.data)
         return opts, (tips, internode)
 
+    def _quartet_workspace_bytes(self, fam, quartets):
+        opts, keep = fam.opts(quartets)
+        return _size_out(getattr(self._lib, fam.prefix + "_workspace_bytes"), self._h, ctypes.byref(opts))
+
+    def _quartet_tables(self, fam, rates, nres, quartets):
+        rates, nres = self._rates_nres(rates, nres)
+        opts, keep = fam.opts(quartets)
+        rows = np.zeros((self.nloci, opts.n_q, fam.row))
+        _check(getattr(self._lib, fam.prefix + "_tables")(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), rows.ctypes.data))
+        return rows
+
+    def _quartet_sites(self, fam, rates, nres, quartets):
+        rates, nres = self._rates_nres(rates, nres)
+        opts, keep = fam.opts(quartets)
+        sites = np.zeros((fam.planes, opts.n_q, self.ncols))
+        _check(getattr(self._lib, fam.prefix + "_sites")(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), sites.ctypes.data))
+        return sites
+
+    def _quartet_tables_dev(self, fam, d_rates, d_nres, quartets, d_rows, d_ws, stream):
+        opts, keep = fam.opts(quartets)
+        _check(getattr(self._lib, fam.prefix + "_tables_dev")(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_rows),
+                                                              _ptr(d_ws), _nbytes(d_ws), stream))
+
+    def _quartet_sites_dev(self, fam, d_rates, d_nres, quartets, d_sites, stream):
+        opts, keep = fam.opts(quartets)
+        _check(getattr(self._lib, fam.prefix + "_sites_dev")(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
+
+    def quartet_workspace_bytes(self, quartets):
+        """bytes of device workspace for quartet_tables_dev with these quartets."""
+        return self._quartet_workspace_bytes(_EQUAL_TIPS, quartets)
+
+    def quartet_tables(self, rates, nres, quartets):
+        """Signal and noise of the quartets ((a:T, b:T), (c:T, d:T)) with internode t_o under the plan's models
+        (tphip_quartet_tables).  rates / nres as for pi_tables; quartets [n_q, 2] rows (T, t_o) in the tree's original time
+        units.  Returns rows [L, n_q, 8]: Y, X, Yy, Xx, XY, p_correct, p_incorrect, p_polytomy."""
+        return self._quartet_tables(_EQUAL_TIPS, rates, nres, quartets)
+
+    def quartet_sites(self, rates, nres, quartets):
+        """The per-site values behind quartet_tables (tphip_quartet_sites): [2, n_q, ncols], signal y then noise x; exactly
+        0 for a culled or zero-rate column."""
+        return self._quartet_sites(_EQUAL_TIPS, rates, nres, quartets)
+
+    def quartet_tables_dev(self, d_rates, d_nres, quartets, d_rows, d_ws, stream=0):
+        """tphip_quartet_tables_dev on device tensors (d_nres may be None): d_rows [L, n_q, 8]; enqueues, does not synchronise."""
+        self._quartet_tables_dev(_EQUAL_TIPS, d_rates, d_nres, quartets, d_rows, d_ws, stream)
+
+    def quartet_sites_dev(self, d_rates, d_nres, quartets, d_sites, stream=0):
+        """tphip_quartet_sites_dev on device tensors: d_sites [2, n_q, ncols]; enqueues, does not synchronise."""
+        self._quartet_sites_dev(_EQUAL_TIPS, d_rates, d_nres, quartets, d_sites, stream)
+
     def unequal_quartet_workspace_bytes(self, quartets):
         """bytes of device workspace for unequal_quartet_tables_dev with these quartets."""
-        opts, keep = self._unequal_quartet_opts(quartets)
-        n = ctypes.c_size_t()
-        _check(self._lib.tphip_unequal_quartet_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
-        return n.value
+        return self._quartet_workspace_bytes(_UNEQUAL_TIPS, quartets)
 
     def unequal_quartet_tables(self, rates, nres, quartets):
         """Signal and noise of the quartets ((a:Ta, b:Tb), (c:Tc, d:Td)) with internode t_o under the plan's models
         (tphip_unequal_quartet_tables).  rates / nres as for pi_tables; quartets [n_q, 5] rows (Ta, Tb, Tc, Td, t_o) in the
         tree's original time units.  Returns rows [L, n_q, 13]: the sums of y, x1, x2, y^2, x1^2, x2^2, y x1, y x2, x1 x2, then
         p_correct, p_ac, p_ad, p_polytomy."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
-        opts, keep = self._unequal_quartet_opts(quartets)
-        rows = np.zeros((self.nloci, opts.n_q, 13))
-        _check(self._lib.tphip_unequal_quartet_tables(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), rows.ctypes.data))
-        return rows
+        return self._quartet_tables(_UNEQUAL_TIPS, rates, nres, quartets)
 
     def unequal_quartet_sites(self, rates, nres, quartets):
         """The per-site values behind unequal_quartet_tables (tphip_unequal_quartet_sites): [3, n_q, ncols], signal y, then
         the noise x1 (pattern ijij) and x2 (ijji); exactly 0 for a culled or zero-rate column."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
-        nres = None if nres is None else _np(nres, np.int32)
-        opts, keep = self._unequal_quartet_opts(quartets)
-        sites = np.zeros((3, opts.n_q, self.ncols))
-        _check(self._lib.tphip_unequal_quartet_sites(self._h, rates.ctypes.data, _ptr(nres), ctypes.byref(opts), sites.ctypes.data))
-        return sites
+        return self._quartet_sites(_UNEQUAL_TIPS, rates, nres, quartets)
 
     def unequal_quartet_tables_dev(self, d_rates, d_nres, quartets, d_rows, d_ws, stream=0):
         """tphip_unequal_quartet_tables_dev on device tensors (d_nres may be None): d_rows [L, n_q, 13]; enqueues, does not
         synchronise."""
-        opts, keep = self._unequal_quartet_opts(quartets)
-        _check(self._lib.tphip_unequal_quartet_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_rows),
-                                                          _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
+        self._quartet_tables_dev(_UNEQUAL_TIPS, d_rates, d_nres, quartets, d_rows, d_ws, stream)
 
     def unequal_quartet_sites_dev(self, d_rates, d_nres, quartets, d_sites, stream=0):
         """tphip_unequal_quartet_sites_dev on device tensors: d_sites [3, n_q, ncols]; enqueues, does not synchronise."""
-        opts, keep = self._unequal_quartet_opts(quartets)
-        _check(self._lib.tphip_unequal_quartet_sites_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_sites), stream))
+        self._quartet_sites_dev(_UNEQUAL_TIPS, d_rates, d_nres, quartets, d_sites, stream)
 
     # ---- exact quartet resolution probabilities (csrc/exact_quartet_driver.hip) -------------------
     @staticmethod
@@ -815,9 +815,7 @@ class Plan:
     def quartet_exact_workspace_bytes(self, n_q, window_cap=128):
         """bytes of device workspace for quartet_exact_dev with n_q quartets and this cap."""
         opts = self._quartet_exact_opts(n_q, window_cap, 0.0)
-        n = ctypes.c_size_t()
-        _check(self._lib.tphip_quartet_exact_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
-        return n.value
+        return _size_out(self._lib.tphip_quartet_exact_workspace_bytes, self._h, ctypes.byref(opts))
 
     def quartet_exact(self, y, x1, x2, window_cap=128, tail_tolerance=0.0):
         """The exact law of the quartet counts from the per-site planes (tphip_quartet_exact): y, x1, x2 [n_q, ncols] as
@@ -841,7 +839,7 @@ class Plan:
         [L, n_q, 6]; enqueues, does not synchronise."""
         opts = self._quartet_exact_opts(n_q, window_cap, tail_tolerance)
         _check(self._lib.tphip_quartet_exact_dev(self._h, _ptr(d_y), _ptr(d_x1), _ptr(d_x2), ctypes.byref(opts), _ptr(d_rows),
-                                                 _ptr(d_ws), d_ws.numel() * d_ws.element_size(), stream))
+                                                 _ptr(d_ws), _nbytes(d_ws), stream))
 
     # ---- parametric bootstrap of site rates and PI rows (csrc/simulate_driver.hip) ---------------
     def _ids(self, locus_ids):
@@ -858,8 +856,7 @@ class Plan:
         uint8 [ntaxa, ncols] observed alignment whose cells that are not a single base (gaps, ambiguity codes) are copied
         through.  Returns uint8 [ntaxa, ncols].  A column's bytes depend on seed, its locus' stream id (locus_ids, default the
         locus index), its index in the locus, replicate, its rate, the model, the tree and its mask only."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
+        rates, _ = self._rates_nres(rates)
         if mask is not None:
             mask = _np(mask, np.uint8)
             assert mask.shape == (self.ntaxa, self.ncols), (mask.shape, self.ntaxa, self.ncols)
@@ -887,9 +884,7 @@ class Plan:
     def parboot_workspace_bytes(self, replicates, seed=1, level=0.95):
         """bytes of device workspace for pi_parametric_bootstrap_dev."""
         opts, _ = self._parboot_opts(replicates, seed, level, None)
-        n = ctypes.c_size_t()
-        _check(self._lib.tphip_parboot_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(n)))
-        return n.value
+        return _size_out(self._lib.tphip_parboot_workspace_bytes, self._h, ctypes.byref(opts))
 
     def pi_parametric_bootstrap(self, rates, states, replicates=100, seed=1, level=0.95, locus_ids=None, return_rows=False,
                                 return_rate_moments=False):
@@ -898,8 +893,7 @@ class Plan:
         re-estimated and the PI row recomputed; the locus' model and the tree are held fixed.  Returns summary [L, 4, Wb]
         (mean, sd, lo, hi); with return_rows the replicate rows [L, B, Wb]; with return_rate_moments (rate_mean, rate_sd) of
         every column's final rate over the replicates, NaN for culled columns -- in that order."""
-        rates = _np(rates, np.float64)
-        assert rates.shape == (self.ncols,)
+        rates, _ = self._rates_nres(rates)
         if states is not None:
             states = _np(states, np.uint8)
             assert states.shape == (self.ntaxa, self.ncols), (states.shape, self.ntaxa, self.ncols)
@@ -922,7 +916,7 @@ class Plan:
                                     level=0.95, locus_ids=None, stream=0, ws_bytes=None):
         """tphip_pi_parametric_bootstrap_dev on device tensors (d_rows / d_rate_mean / d_rate_sd may be None)."""
         opts, ids = self._parboot_opts(replicates, seed, level, locus_ids)
-        nbytes = d_ws.numel() * d_ws.element_size() if ws_bytes is None else int(ws_bytes)
+        nbytes = _nbytes(d_ws) if ws_bytes is None else int(ws_bytes)
         _check(self._lib.tphip_pi_parametric_bootstrap_dev(self._h, _ptr(d_rates), _ptr(d_states), ctypes.byref(opts), _ptr(d_summary),
                                                            _ptr(d_rows), _ptr(d_rate_mean), _ptr(d_rate_sd), _ptr(d_ws), nbytes, stream))
 
@@ -945,6 +939,12 @@ class Plan:
         n = _i64()
         _check(self._lib.tphip_last_round_count(self._h, ctypes.byref(n)))
         return n.value
+
+
+# what Plan's five calls of a signal / noise family differ in
+_QuartetFamily = collections.namedtuple("_QuartetFamily", "opts prefix row planes")
+_EQUAL_TIPS = _QuartetFamily(Plan._quartet_opts, "tphip_quartet", 8, 2)
+_UNEQUAL_TIPS = _QuartetFamily(Plan._unequal_quartet_opts, "tphip_unequal_quartet", 13, 3)
 
 
 class _DeviceCache:

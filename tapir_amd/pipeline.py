@@ -7,6 +7,7 @@ batch (taxon-major state masks + CSR locus offsets), one call into the HIP engin
 `<alignment>.rates` JSON files (schema of models_and_rates.bf:1018-1104 plus `corrected_rates`,
 tapir/compute.py:40-43) and worker()-shaped result tuples for tapir_amd.db.
 """
+import contextlib
 import os
 import sys
 
@@ -770,17 +771,45 @@ def run_rate_files(rate_files, leaf_names, parent, blen, leaf, T, times, interva
     return (tuples, tables) if return_tables else tuples
 
 
-def _tables_for_rates(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device, integ_mode):
-    """PI tables for already-final rates (NaN = culled): tphip_pi_tables with no rounding/correction/cull."""
+@contextlib.contextmanager
+def _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device, integ_mode=None, pi=None,
+                      exch=None, model=None):
+    """The plan for already-final per-locus rates (NaN = culled) -- no rounding, no correction, no cull -- with the
+    concatenated rates and the loci's offsets; closed on leaving.  The PI stage does not look at the models (model None:
+    placeholders); the quartet stages pass the loci's pi / exch / model as _locus_models returns them."""
     offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
     rates = np.concatenate(per_locus) if per_locus else np.zeros(0)
     L = len(per_locus)
-    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, np.full((L, 4), 0.25), np.ones((L, 6)), T, times,
-                    intervals, correction=1.0, threshold=0, round_decimals=-1, integ_mode=integ_mode, device=device)
+    kw = {} if integ_mode is None else dict(integ_mode=integ_mode)
+    if model is not None:
+        kw["model"] = model
+    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, np.full((L, 4), 0.25) if model is None else pi,
+                    np.ones((L, 6)) if model is None else exch, T, times, intervals, correction=1.0, threshold=0,
+                    round_decimals=-1, device=device, **kw)
     try:
-        return plan.pi_tables(rates, None)
+        yield plan, rates, offsets
     finally:
         plan.close()
+
+
+def _locus_models(L, pi, exch, model):
+    """pi [L, 4] and exch [L, 6] (one row of six serves every locus) of the quartet stages' plans; exch None under "f81"."""
+    if model not in ("gtr", "f81"):
+        raise PipelineError("unknown model %r" % (model,))
+    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
+    if model == "gtr":
+        exch = np.asarray(exch, dtype=np.float64)
+        exch = np.tile(exch, (L, 1)) if exch.ndim == 1 else exch.reshape(L, 6)
+    else:
+        exch = None
+    return pi, exch
+
+
+def _tables_for_rates(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device, integ_mode):
+    """PI tables for already-final rates (NaN = culled): tphip_pi_tables with no rounding/correction/cull."""
+    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device,
+                           integ_mode) as (plan, rates, _):
+        return plan.pi_tables(rates, None)
 
 
 def bootstrap_tables(eng, per_locus, leaf_names, parent, blen, leaf, T, intervals, device, integ_mode, locus_ids,
@@ -791,18 +820,12 @@ def bootstrap_tables(eng, per_locus, leaf_names, parent, blen, leaf, T, interval
     being touched.  locus_ids: the generator's stream id per locus -- the command line passes the global file indices, so
     a locus' bands do not depend on which rank, or which loci beside it, it was computed with.  The locus' model (and under
     eb the fitted prior) are held fixed: the bands are conditional on them."""
-    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
-    rates = np.concatenate(per_locus) if per_locus else np.zeros(0)
-    L = len(per_locus)
-    if L == 0:
+    if len(per_locus) == 0:
         return np.zeros((0, 4, T + len(intervals)))
-    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, np.full((L, 4), 0.25), np.ones((L, 6)), T, [],
-                    intervals, correction=1.0, threshold=0, round_decimals=-1, integ_mode=integ_mode, device=device)
-    try:
+    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], intervals, device,
+                           integ_mode) as (plan, rates, _):
         return plan.pi_bootstrap(rates, None, replicates=replicates, seed=seed, level=level,
                                  locus_ids=np.asarray(locus_ids, dtype=np.int64))
-    finally:
-        plan.close()
 
 
 PARBOOT_BLOCK_COLS = 1 << 24   # columns per plan of parametric_bootstrap_tables
@@ -892,22 +915,10 @@ def quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, 
     L = len(per_locus)
     if L == 0:
         return np.zeros((0, len(quartets), 8))
-    if model not in ("gtr", "f81"):
-        raise PipelineError("unknown model %r" % (model,))
-    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
-    if model == "gtr":
-        exch = np.asarray(exch, dtype=np.float64)
-        exch = np.tile(exch, (L, 1)) if exch.ndim == 1 else exch.reshape(L, 6)
-    else:
-        exch = None
-    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
-    rates = np.concatenate(per_locus)
-    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, [], [], correction=1.0, threshold=0,
-                    round_decimals=-1, device=device, model=model)
-    try:
+    pi, exch = _locus_models(L, pi, exch, model)
+    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], [], device, pi=pi, exch=exch,
+                           model=model) as (plan, rates, _):
         return plan.quartet_tables(rates, None, quartets)
-    finally:
-        plan.close()
 
 
 def unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr"):
@@ -920,23 +931,11 @@ def unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, l
     L = len(per_locus)
     if L == 0 or len(quartets) == 0:
         return np.zeros((L, len(quartets), 13))
-    if model not in ("gtr", "f81"):
-        raise PipelineError("unknown model %r" % (model,))
-    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
-    if model == "gtr":
-        exch = np.asarray(exch, dtype=np.float64)
-        exch = np.tile(exch, (L, 1)) if exch.ndim == 1 else exch.reshape(L, 6)
-    else:
-        exch = None
-    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
-    rates = np.concatenate(per_locus)
-    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, [], [], correction=1.0, threshold=0,
-                    round_decimals=-1, device=device, model=model)
-    try:
+    pi, exch = _locus_models(L, pi, exch, model)
+    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], [], device, pi=pi, exch=exch,
+                           model=model) as (plan, rates, _):
         return np.concatenate([plan.unequal_quartet_tables(rates, None, quartets[q0:q0 + 256])
                                for q0 in range(0, len(quartets), 256)], axis=1)
-    finally:
-        plan.close()
 
 
 # exact_quartet_tables works through the quartets in tiles: the dense per-site planes of a tile ([2 or 3][tile][ncols] doubles)
@@ -958,22 +957,13 @@ def _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, le
     L, n_q = len(per_locus), len(quartets)
     if L == 0 or n_q == 0:
         return np.zeros((L, n_q, 6))
-    if model not in ("gtr", "f81"):
-        raise PipelineError("unknown model %r" % (model,))
-    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
-    if model == "gtr":
-        exch = np.asarray(exch, dtype=np.float64)
-        exch = np.tile(exch, (L, 1)) if exch.ndim == 1 else exch.reshape(L, 6)
-    else:
-        exch = None
-    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
-    ncols, planes = int(offsets[-1]), 3 if unequal else 2
-    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, [], [], correction=1.0, threshold=0,
-                    round_decimals=-1, device=device, model=model)
-    try:
+    pi, exch = _locus_models(L, pi, exch, model)
+    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], [], device, pi=pi, exch=exch,
+                           model=model) as (plan, rates, offsets):
+        ncols, planes = int(offsets[-1]), 3 if unequal else 2
         tile = exact_quartet_tile(L, ncols, n_q, planes, window_cap)
         stream = eng.device_stream(device)
-        d_rates = eng.device_array(np.concatenate(per_locus), device)
+        d_rates = eng.device_array(rates, device)
         d_flat = eng.device_empty((planes * tile * ncols,), device)
         d_ws = eng.device_empty((plan.quartet_exact_workspace_bytes(tile, window_cap),), device, np.uint8)
         out = np.zeros((L, n_q, 6))
@@ -986,8 +976,6 @@ def _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, le
             plan.quartet_exact_dev(d_sites[0], d_sites[1], d_sites[planes - 1], k, d_rows, d_ws, window_cap, 0.0, stream)
             out[:, q0:q0 + k] = eng.host_array(d_rows)
         return out
-    finally:
-        plan.close()
 
 
 def exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr", window_cap=128):

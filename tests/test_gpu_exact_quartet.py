@@ -118,7 +118,7 @@ def test_device_calls_chain_without_leaving_the_device():
         plan.quartet_exact_dev(d_sites[0], d_sites[1], d_sites[2], 6, d_rows, ws, stream=stream)
         torch.cuda.synchronize()
         assert np.array_equal(d_rows.cpu().numpy(), host)
-        with pytest.raises(engine.TphipError, match="workspace smaller"):
+        with pytest.raises(engine.TphipError, match="libtphip error 1: ws_bytes: workspace smaller"):
             plan.quartet_exact_dev(d_sites[0], d_sites[1], d_sites[2], 6, d_rows, ws[:64])
         for bad, message in ((dict(window_cap=48), "window_cap must be a power of two"), (dict(window_cap=1024), "window_cap must be"),
                              (dict(tail_tolerance=2.0), "tail_tolerance must be in"), (dict(tail_tolerance=-1e-3), "tail_tolerance must be in")):

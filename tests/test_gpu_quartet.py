@@ -15,7 +15,8 @@ Bounds (stated by the definition, none tuned to the kernels):
                   restatement is held against scipy on the same arguments in the same test -- against mpmath within 1e-9 of
                   |rho| = 1, where scipy answers for the singular case)
   bit identity    of a locus' row: alone against among its neighbours, n_q = 1 against the same quartet inside the list of
-                  17, the host-pointer call against the _dev call
+                  17, 130 and 256 quartets (three and four launches) against shorter calls cut at a launch boundary and
+                  across it, the host-pointer call against the _dev call
 """
 import json
 import math
@@ -42,6 +43,10 @@ Q17 = [(0.0, 1e-3), (0.0, 3.0), (20.0, 3.0), (20.0, 5.0), (50.0, 5.0), (50.0, 10
        (1e-2, 50.0), (1.0, 1.0), (300.0, 0.5), (20.0, 5.0), (3.0, 0.01), (3.0, 0.01), (64.0, 1e-3), (0.0, 50.0)]
 QLISTS = {1: [Q17[5]], 3: Q17[3:6], 17: Q17}
 TWIN_Q = [0, 3, 6, 11, 15]          # quartets of the twin's sample (indices into Q17)
+# 256 distinct quartets (every t_o differs: 257 is prime); neighbours 2 k, 2 k + 1 share T, so matrices are reused inside a
+# launch and never across the launch boundaries at 64, 128 and 192
+Q256 = [(((k // 2) % 13) * 2.5 * (1.0 + (k // 26) / 16.0), 10.0 ** (-3.0 + 4.5 * ((k * 37) % 257) / 256.0)) for k in range(256)]
+assert len(set(Q256)) == 256
 
 
 def _engine():
@@ -235,6 +240,17 @@ def test_rows_do_not_depend_on_neighbours_or_on_the_quartet_list(cases, kind):
             assert np.array_equal(one[:, 0], full[:, q]), q
             assert np.array_equal(plan.quartet_sites(rates, nres, [Q17[q]])[:, 0], full_sites[:, q]), q
         assert np.array_equal(full[:, 3], full[:, 12])             # the same quartet twice in the list
+        # 130 distinct quartets are three launches of 64: every row and site against the two shorter calls that cut the list
+        # at the first launch boundary, and 60..70 against a call of those eleven (other positions of a batch)
+        big = plan.quartet_tables(rates, nres, Q256[:130])
+        big_sites = plan.quartet_sites(rates, nres, Q256[:130])
+        for a, b in ((0, 64), (64, 130), (60, 71)):
+            assert np.array_equal(plan.quartet_tables(rates, nres, Q256[a:b]), big[:, a:b]), (a, b)
+            assert np.array_equal(plan.quartet_sites(rates, nres, Q256[a:b]), big_sites[:, a:b]), (a, b)
+        most = plan.quartet_tables(rates, nres, Q256)              # the longest list: four full launches
+        assert most.shape == (len(c["sizes"]), 256, 8)
+        assert np.array_equal(most[:, :130], big)
+        assert np.array_equal(most[:, 192:], plan.quartet_tables(rates, nres, Q256[192:]))
     finally:
         plan.close()
     L = len(c["sizes"])
@@ -245,7 +261,7 @@ def test_rows_do_not_depend_on_neighbours_or_on_the_quartet_list(cases, kind):
         finally:
             part.close()
         assert np.array_equal(rows, full[ids]), ids
-    print("%s: rows bit-identical alone / among neighbours / in a list of 1 or 17" % kind)
+    print("%s: rows bit-identical alone / among neighbours / in a list of 1, 17, 130 or 256" % kind)
 
 
 def test_host_and_device_calls_agree(cases):
@@ -265,7 +281,7 @@ def test_host_and_device_calls_agree(cases):
         plan.quartet_sites_dev(d_r, d_n, Q17, d_sites)
         torch.cuda.synchronize()
         assert np.array_equal(d_rows.cpu().numpy(), host) and np.array_equal(d_sites.cpu().numpy(), host_sites)
-        with pytest.raises(engine.TphipError, match="workspace smaller"):
+        with pytest.raises(engine.TphipError, match="libtphip error 4: workspace smaller"):
             plan.quartet_tables_dev(d_r, d_n, Q17, d_rows, ws[:64])
     finally:
         plan.close()

@@ -13,7 +13,8 @@ Bounds (stated by the definition, none tuned to the kernels):
   sums            against math.fsum of the GPU's own per-site values: (n_l + 64) 2^-52 relative (non-negative terms)
   probabilities   against the restatement fed the GPU's sums: 1e-13 absolute
   bit identity    of a locus' row: alone against among its neighbours, one quartet alone against inside the list, the
-                  repeated quartet twice, 130 quartets (three launches) against single calls, host against _dev
+                  repeated quartet twice, 130 quartets (three launches) against single calls, 130 and 256 distinct quartets
+                  against shorter calls cut at a launch boundary and across it, host against _dev
 """
 import json
 import os
@@ -273,6 +274,19 @@ def test_rows_do_not_depend_on_neighbours_or_on_the_quartet_list(cases, kind):
         for q in (14, 63, 64, 65, 127, 128, 129):                  # both sides of the launches' boundaries, and the last
             assert np.array_equal(plan.unequal_quartet_tables(rates, nres, [q130[q]])[:, 0], big[:, q]), q
             assert np.array_equal(plan.unequal_quartet_sites(rates, nres, [q130[q]])[:, 0], big_sites[:, q]), q
+        # 130 distinct quartets: every row and site against the two shorter calls that cut the list at the first launch
+        # boundary, and 60..70 against a call of those eleven (other positions of a batch)
+        d256 = [tuple(rng.uniform(0.0, 120.0, 4)) + (float(rng.uniform(0.01, 30.0)),) for k in range(256)]
+        assert len(set(d256)) == 256
+        big = plan.unequal_quartet_tables(rates, nres, d256[:130])
+        big_sites = plan.unequal_quartet_sites(rates, nres, d256[:130])
+        for a, b in ((0, 64), (64, 130), (60, 71)):
+            assert np.array_equal(plan.unequal_quartet_tables(rates, nres, d256[a:b]), big[:, a:b]), (a, b)
+            assert np.array_equal(plan.unequal_quartet_sites(rates, nres, d256[a:b]), big_sites[:, a:b]), (a, b)
+        most = plan.unequal_quartet_tables(rates, nres, d256)      # the longest list: four full launches
+        assert most.shape == (len(c["sizes"]), 256, 13)
+        assert np.array_equal(most[:, :130], big)
+        assert np.array_equal(most[:, 192:], plan.unequal_quartet_tables(rates, nres, d256[192:]))
     finally:
         plan.close()
     L = len(c["sizes"])
@@ -303,7 +317,7 @@ def test_host_and_device_calls_agree(cases):
         plan.unequal_quartet_sites_dev(d_r, d_n, Q14, d_sites)
         torch.cuda.synchronize()
         assert np.array_equal(d_rows.cpu().numpy(), host) and np.array_equal(d_sites.cpu().numpy(), host_sites)
-        with pytest.raises(engine.TphipError, match="workspace smaller"):
+        with pytest.raises(engine.TphipError, match="libtphip error 1: ws_bytes: workspace smaller"):
             plan.unequal_quartet_tables_dev(d_r, d_n, Q14, d_rows, ws[:64])
     finally:
         plan.close()
