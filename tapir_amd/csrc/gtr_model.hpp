@@ -8,6 +8,10 @@
 // exp(Q t) = U diag(exp(lam t)) U^-1 via the symmetrised matrix S = D^1/2 Q D^-1/2 (D = diag(pi)) and a
 // cyclic Jacobi iteration.  Eigenvalue 0 is moved to slot 0 and made exact: lam[0] = 0, U[:,0] = 1,
 // U^-1[0,:] = pi.  The kernels rely on that structure (one exp less per branch, no derivative terms).
+// The three kept vectors are projected against sqrt(pi) and re-orthonormalised: where Q is nearly reducible a second
+// eigenvalue lam_1 comes near 0 and Jacobi's vector for it carries about eps |S| / |lam_1| of Jacobi's stationary
+// vector, which slot 0 no longer holds; left in, it puts that much absolute error on the entries of P across the
+// blocks, which are themselves of size |lam_1| t (tests/test_model_spectra.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

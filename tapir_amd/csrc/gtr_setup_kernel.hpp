@@ -47,13 +47,35 @@ __global__ void gtr_setup_kernel(const double* __restrict__ pi_in, const double*
     for (int k = 1; k < 4; ++k) if (A[k][k] > A[z][z]) z = k;
     int order[4] = {z, 0, 0, 0};
     for (int k = 0, o = 1; k < 4; ++k) if (k != z) order[o++] = k;
+    // Slot 0 holds the exact stationary pair (1, pi), i.e. sq in S's basis, not Jacobi's own vector for it.  The kept
+    // vectors are orthogonal to Jacobi's, not to sq: where a second eigenvalue comes near 0 they carry eps |S| / |lam_1| of
+    // it.  Modified Gram-Schmidt with sq (a unit vector) first removes it.  A component within kKeep of its own
+    // rounding scale is left alone, a projection doing no better: on a well separated spectrum the vectors stay bit for
+    // bit as Jacobi left them.
+    const double kKeep = 8 * 2.220446049250313e-16;
     LocusModel m;
+    double W[3][4];
     for (int o = 1; o < 4; ++o) {
         int k = order[o];
+        double* w = W[o - 1];
+        for (int i = 0; i < 4; ++i) w[i] = V[i][k];
+        for (int b = 0; b < o; ++b) {
+            const double* base = b == 0 ? sq : W[b - 1];
+            double d = 0, scale = 0;   // what d is rounded against: its own terms along sq, 1 between two unit vectors
+            for (int i = 0; i < 4; ++i) { d += base[i] * w[i]; scale += fabs(base[i] * w[i]); }
+            if (fabs(d) > kKeep * (b == 0 ? scale : 1.0))
+                for (int i = 0; i < 4; ++i) w[i] -= d * base[i];
+        }
+        double n = 0;
+        for (int i = 0; i < 4; ++i) n += w[i] * w[i];
+        if (fabs(n - 1.0) > kKeep) {
+            n = 1.0 / sqrt(n);
+            for (int i = 0; i < 4; ++i) w[i] *= n;
+        }
         m.lam[o - 1] = A[k][k];
         for (int i = 0; i < 4; ++i) {
-            m.U[i * 3 + (o - 1)] = V[i][k] / sq[i];
-            m.Ui[(o - 1) * 4 + i] = V[i][k] * sq[i];
+            m.U[i * 3 + (o - 1)] = w[i] / sq[i];
+            m.Ui[(o - 1) * 4 + i] = w[i] * sq[i];
         }
     }
     for (int i = 0; i < 4; ++i) m.pi[i] = pi[i];
