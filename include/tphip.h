@@ -423,6 +423,72 @@ int tphip_eb_posterior(tphip_plan *plan, const uint8_t *states, const tphip_eb_o
 int tphip_eb_posterior_dev(tphip_plan *plan, const uint8_t *d_states, const tphip_eb_opts *opts, const double *cat_rate,
                            const double *cat_weight, const double *scale, double *d_rate, double *d_rate_sd,
                            double *d_lnl, int32_t *d_nres, void *stream);
+/* tphip_eb_posterior with the category posterior besides: post[k * ncols + c] = p_ck = w_k L_c(mu rho_k) / m_c
+ * ([ncat][ncols], category-major; the same clamp at log(1e-10); every column sums to 1 within rounding; under use_patterns a
+ * column repeated in its locus reads its representative's p).  rate, rate_sd, lnl and nres are those of tphip_eb_posterior,
+ * bit for bit. */
+int tphip_eb_posterior_table(tphip_plan *plan, const uint8_t *states, const tphip_eb_opts *opts, const double *cat_rate,
+                             const double *cat_weight, const double *scale, double *post, double *rate, double *rate_sd,
+                             double *lnl, int32_t *nres);
+int tphip_eb_posterior_table_dev(tphip_plan *plan, const uint8_t *d_states, const tphip_eb_opts *opts,
+                                 const double *cat_rate, const double *cat_weight, const double *scale, double *d_post,
+                                 double *d_rate, double *d_rate_sd, double *d_lnl, int32_t *d_nres, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The empirical-Bayes rate posterior carried into the per-locus PI rows (an extension).  PI(t) = 16 s^2 t e^(-4st) is not
+ * linear in s, so the profile at a site's posterior mean rate is not the posterior expectation of the profile.  Given the
+ * fitted scale mu_l and categories (rho_lk, w_lk), k < K, a site of locus l has one of K rates only:
+ *   r_lk      = the plan's finalisation (the round_decimals round trip, then /correction, as tphip_corrected_rates
+ *               treats a column's rate) of the raw rate (kappa_l mu_l) rho_lk;
+ *   P_l[k][w] = the per-site values of the PI tables and the bootstrap at r_lk, w < Wb = T + n_i (tphip_bootstrap_width):
+ *               16 r^2 t e^(-4rt) at t = 0..T-1, then the interval integrals under the plan's integ_mode;
+ *   live      = nres[c] >= threshold, the cull of tphip_pi_tables (nres NULL: every column); a culled column
+ *               contributes nothing below.
+ * A posterior draw of the locus' row is sum_k N_k P_l[k][.], N_k = the live sites drawn into category k.
+ *
+ * Analytic moments per locus and entry, analytic[l][0][w] = mean, analytic[l][1][w] = sd:
+ *   expected_counts[l][k] = n_lk = sum over live c of p_ck (a fixed-order sum per locus),
+ *   mean[w] = sum_k n_lk P_l[k][w],
+ *   var[w]  = sum over live c of ( sum_k p_ck P_l[k][w]^2 - (sum_k p_ck P_l[k][w])^2 ), every site's term >= 0 (it is
+ *             evaluated in the centred form sum_k p_ck (P_l[k][w] - a_c)^2, a_c = sum_k p_ck P_l[k][w]),  sd = sqrt(var).
+ *
+ * Draws: replicate b < B, 2 <= B <= 4096.  Generator: Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter =
+ * (j, b, locus_id & 0xffffffff, locus_id >> 32); word i of block j serves the column at index 4j + i WITHIN ITS LOCUS --
+ * the column, not its pattern (repeats draw independently), and every column, culled or not (the stream does not move with
+ * the cull).  With x that 32-bit word and c_k the fp64 running sum p_c0 + ... + p_ck added in that order, the drawn category
+ * is the number of k <= K - 2 with (x + 0.5) 2^-32 >= c_k.  counts[l][b][k] = N_b[k] = the live columns drawn into k;
+ * rows[l][b][w] = X_b[w] = sum_k N_b[k] P_l[k][w], added in ascending k.  summary[l][4][Wb] = mean, sd, lo, hi over the B
+ * rows, by tphip_summarize_rows_dev.
+ *
+ * Determinism: a locus' category rows, counts and replicate rows depend on its columns, its model, (mu, rho, w), the seed,
+ * the locus id and b only -- not on the other loci, on B, on the workspace size, on blocking or on the GPU count.
+ * Everything is conditional on the fitted (mu_l, alpha_l), the model and the tree: the bands say nothing about the
+ * uncertainty of those.
+ *
+ * post is tphip_eb_posterior_table's [ncat][ncols].  In the _dev call post, nres, scale [nloci] and cat_rate [nloci][ncat]
+ * are DEVICE arrays; it enqueues on `stream` and does not synchronise when opts.locus_ids is NULL (with locus_ids set: as
+ * tphip_pi_bootstrap_dev).  d_rows [nloci][B][Wb] and d_counts [nloci][B][ncat] (int32) may be NULL.  Any workspace >=
+ * *min_bytes gives the same bits; *preferred_bytes (<= about 1 GiB, or the minimum) takes more loci per block.
+ * Errors: TPHIP_ERR_INVALID for B outside 2..4096, level outside (0, 1), ncat outside 2..16. */
+typedef struct tphip_posterior_pi_opts {
+    uint32_t struct_size;      /* sizeof(tphip_posterior_pi_opts) of the caller */
+    int32_t replicates;        /* B, 2..4096 */
+    double level;              /* coverage of [lo, hi], in (0, 1) */
+    uint64_t seed;
+    const int64_t *locus_ids;  /* HOST [nloci] stream id per locus, NULL = the plan's locus index; read before the call returns */
+    int32_t ncat;              /* K, 2..16: the categories of post and cat_rate */
+} tphip_posterior_pi_opts;
+
+int tphip_posterior_pi_workspace_bytes(const tphip_plan *plan, const tphip_posterior_pi_opts *opts, size_t *min_bytes,
+                                       size_t *preferred_bytes);
+int tphip_posterior_pi_dev(tphip_plan *plan, const double *d_post, const int32_t *d_nres, const double *d_scale,
+                           const double *d_cat_rate, const tphip_posterior_pi_opts *opts, double *d_analytic,
+                           double *d_expected_counts, double *d_summary, double *d_rows, int32_t *d_counts,
+                           void *d_workspace, size_t workspace_bytes, void *stream);
+/* host-pointer twin: the library allocates its own workspace */
+int tphip_posterior_pi(tphip_plan *plan, const double *post, const int32_t *nres, const double *scale,
+                       const double *cat_rate, const tphip_posterior_pi_opts *opts, double *analytic,
+                       double *expected_counts, double *summary, double *rows, int32_t *counts);
 
 /* ------------------------------------------------------------------------------------------------
  * Site bootstrap of the per-locus PI rows (an extension: the reference reports the rows without an error bar).

@@ -13,7 +13,10 @@ and noise in another file of its own, phylogenetic-informativeness-quartets.sqli
 tree's internodes, in phylogenetic-informativeness-unequal-quartets.sqlite), --exact-quartets / --exact-quartets-window (the
 exact resolution probabilities beside the normal approximation: a table quartet_exact in those quartet files),
 --parametric-bootstrap / --parametric-bootstrap-seed / --parametric-bootstrap-level (the rates re-estimated on simulated
-alignments: bands in phylogenetic-informativeness-parametric-bootstrap.sqlite, per-site moments in NAME.rates-bootstrap.json).
+alignments: bands in phylogenetic-informativeness-parametric-bootstrap.sqlite, per-site moments in NAME.rates-bootstrap.json),
+--posterior-pi / --posterior-pi-seed / --posterior-pi-level (with --rate-estimator eb: the posterior of the sites' rate
+categories carried into the PI profile, analytic mean and sd and the band of the posterior draws in
+phylogenetic-informativeness-posterior.sqlite; conditional on the fitted scale and shape; nothing else changes).
 
 Several GPUs: launch it with `python -m torch.distributed.run --nproc-per-node G bin/tapir_compute.py ...` (one process
 per GPU).  The files are dealt round-robin over the ranks (what `Pool.map(worker, params)` did over cores,
@@ -120,6 +123,14 @@ def get_args(argv=None):
                      help="seed of the simulation (default 1); needs --parametric-bootstrap")
     new.add_argument('--parametric-bootstrap-level', type=float, default=None,
                      help="coverage of the band [lo, hi], in (0, 1) (default 0.95); needs --parametric-bootstrap")
+    new.add_argument('--posterior-pi', type=int, default=0, metavar='B',
+                     help="B in 2..4096, with --rate-estimator eb: the posterior of every site's rate category carried into the "
+                          "locus' PI profile and interval integrals -- their posterior mean and sd (analytic) and the band of B "
+                          "posterior draws go into phylogenetic-informativeness-posterior.sqlite.  Conditional on the fitted "
+                          "scale and shape, the model and the tree.  0 = off")
+    new.add_argument('--posterior-pi-seed', type=int, default=None, help="seed of the draws (default 1); needs --posterior-pi")
+    new.add_argument('--posterior-pi-level', type=float, default=None,
+                     help="coverage of the band [lo, hi], in (0, 1) (default 0.95); needs --posterior-pi")
     new.add_argument('--quartets', type=_quartets, default=None, metavar='T:to[,T:to...]',
                      help="signal and noise of four-taxon trees ((a:T,b:T),(c:T,d:T)) with an internode of length to, both in "
                           "the tree's time units (floats; to > 0, T >= 0, T + to <= tree depth): per locus the expected numbers "
@@ -229,6 +240,23 @@ def get_args(argv=None):
             args.eb_alpha_bounds = (0.2, 50.0)
         if not 0 < args.eb_alpha_bounds[0] < args.eb_alpha_bounds[1]:
             parser.error("--eb-alpha-bounds must be LO,HI with 0 < LO < HI")
+    if args.posterior_pi == 0:
+        for flag, value in (('--posterior-pi-seed', args.posterior_pi_seed), ('--posterior-pi-level', args.posterior_pi_level)):
+            if value is not None:
+                parser.error("{0} needs --posterior-pi".format(flag))
+    else:
+        if args.rate_estimator != 'eb':
+            parser.error("--posterior-pi carries the empirical-Bayes rate posterior: it needs --rate-estimator eb")
+        if not 2 <= args.posterior_pi <= 4096:
+            parser.error("--posterior-pi must be in 2..4096")
+        if args.posterior_pi_seed is None:
+            args.posterior_pi_seed = 1
+        if not 0 <= args.posterior_pi_seed < 2 ** 64:
+            parser.error("--posterior-pi-seed must be in 0..2^64-1")
+        if args.posterior_pi_level is None:
+            args.posterior_pi_level = 0.95
+        if not 0.0 < args.posterior_pi_level < 1.0:
+            parser.error("--posterior-pi-level must be in (0, 1)")
     return args
 
 
@@ -468,6 +496,7 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
                                                    alpha_bounds=args.eb_alpha_bounds))
             tables = out["final_tables"]
             models = out.get("models")
+            ebfit = out.get("eb")
             stored = bool(out.get("during_write_done"))
             sqlite_seconds = LAST_TIMINGS.get("sqlite")
             LAST_TIMINGS.clear()
@@ -475,9 +504,9 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
             if stored:
                 LAST_TIMINGS["sqlite"] = sqlite_seconds
         else:
-            pis, tables, models = [], np.zeros((0, W)), None
+            pis, tables, models, ebfit = [], np.zeros((0, W)), None, None
     else:
-        models = None
+        models = ebfit = None
         if rank == 0:
             print("Estimating PI for files (--site-rate option):")
         files = base.get_files(args.alignments, '*.rates')
@@ -545,6 +574,31 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
             db.write_bootstrap_db(os.path.join(args.output, 'phylogenetic-informativeness-parametric-bootstrap.sqlite'), files,
                                   all_pboot.reshape(len(files), 4, Wb), T, args.times, args.intervals, args.parametric_bootstrap,
                                   args.parametric_bootstrap_seed, args.parametric_bootstrap_level, method="parametric")
+    if args.posterior_pi:
+        # (as the parametric bootstrap: after the main database, every rank on its own loci with the fits of its own run, stream
+        # ids = global file indices, the alignments re-read; bands, categories and fits travel as one row per locus)
+        eng = engine_mod
+        if eng is None:
+            from . import engine as eng
+        Wb, K = T + len(args.intervals), args.eb_categories
+        ids = list(tdist.shard_loci(len(files), rank, world))
+        pmodels = models if models is not None else dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)),
+                                                         model="gtr" if args.site_model == 'locus' else "f81")
+        fit = ebfit if ebfit is not None else dict(alpha=np.zeros(0), scale=np.zeros(0), categories=K)
+        post = pipeline.posterior_pi_tables(
+            eng, mine, [p[1] for p in pis], pmodels, fit, leaf_names, parent, blen, leaf, T, args.intervals, correction,
+            args.threshold, -1 if args.full_precision_rates else 4, args.device, integ_mode, ids, args.posterior_pi,
+            args.posterior_pi_seed, args.posterior_pi_level, subsets=subset_pi)
+        packed = np.concatenate([post["bands"].reshape(len(ids), 4 * Wb), post["category_rate"].reshape(len(ids), K),
+                                 post["expected_sites"].reshape(len(ids), K),
+                                 np.asarray(fit["alpha"], dtype=np.float64).reshape(len(ids), 1),
+                                 np.asarray(fit["scale"], dtype=np.float64).reshape(len(ids), 1)], axis=1)
+        all_post = _gather_rows(packed, len(files), rank, world, on_gpu)
+        if rank == 0:
+            db.write_posterior_db(os.path.join(args.output, 'phylogenetic-informativeness-posterior.sqlite'), files,
+                                  all_post[:, :4 * Wb].reshape(len(files), 4, Wb), all_post[:, 4 * Wb:4 * Wb + K],
+                                  all_post[:, 4 * Wb + K:4 * Wb + 2 * K], all_post[:, 4 * Wb + 2 * K], all_post[:, 4 * Wb + 2 * K + 1],
+                                  T, args.times, args.intervals, args.posterior_pi, args.posterior_pi_seed, args.posterior_pi_level)
     if args.quartets:
         # (as the bootstrap: an opt-in stage after the main database, from every rank's final rates; rows travel like the PI rows)
         eng = engine_mod

@@ -210,6 +210,17 @@ int launch_posterior(tphip_plan* p, const PosteriorParams& E, hipStream_t st) {
     return TPHIP_OK;
 }
 
+// the posterior-table variant: the same launch with the categories' f_k + log w_k stored at logp [K][ncols]
+int launch_posterior_table(tphip_plan* p, const PosteriorParams& E, double* logp, hipStream_t st) {
+    if (p->n_site_chunks <= 0) return TPHIP_OK;
+    PosteriorTableParams T;
+    static_cast<PosteriorParams&>(T) = E;
+    T.logp = logp;
+    const size_t lds = site_lds_bytes(p->prog.stack_depth);
+    HIP_TRY(launch_site_posterior_table_kernel(site_variant(p->nwords), p->model, dim3((unsigned)p->n_site_chunks), lds, st, T));
+    return TPHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -284,6 +295,53 @@ int tphip_eb_posterior_dev(tphip_plan* p, const uint8_t* d_states, const tphip_e
     HIP_TRY(hipMemcpyAsync(d_nres, W.prep.nres, sizeof(int32_t) * (size_t)p->ncols, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipGetLastError());
     return TPHIP_OK;
+}
+
+// tphip_eb_posterior_dev with the category posterior besides: the table variant of the mixture kernel
+// leaves f_k + log w_k in d_post, eb_finish_kernel gives rate / sd / lnl as above, and the normalisation (a kernel of
+// posterior_pi_driver.hip) turns d_post into p_ck in place, repeats copying their representatives.
+int tphip_eb_posterior_table_dev(tphip_plan* p, const uint8_t* d_states, const tphip_eb_opts* o, const double* cat_rate,
+                                 const double* cat_weight, const double* scale, double* d_post, double* d_rate, double* d_rate_sd,
+                                 double* d_lnl, int32_t* d_nres, void* stream) {
+    int rc = eb_check(p, o, cat_rate, cat_weight, scale);
+    if (rc) return rc;
+    if (!d_states || !d_post || !d_rate || !d_rate_sd || !d_lnl || !d_nres) return fail(TPHIP_ERR_INVALID, "null device pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (p->nloci == 0 || p->n_pi_chunks <= 0) return TPHIP_OK;
+    EbWorkspace W;
+    rc = eb_setup(p, d_states, o, cat_rate, cat_weight, scale, st, W);
+    if (rc) return rc;
+    rc = launch_posterior_table(p, W.E, d_post, st);
+    if (rc) return rc;
+    eb_finish_kernel<<<dim3((unsigned)p->n_pi_chunks), dim3(256), 0, st>>>(p->d_offsets.p, p->d_pi_chunk_locus.p, p->d_pi_chunk_index.p,
+                                                                          p->d_models.p, W.prep.dup_of, W.X.u, W.E.f, W.E.mean,
+                                                                          W.E.second, d_rate, d_rate_sd, d_lnl);
+    HIP_TRY(hipMemcpyAsync(d_nres, W.prep.nres, sizeof(int32_t) * (size_t)p->ncols, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipGetLastError());
+    return tphip_internal_posterior_normalize(p, W.prep.dup_of, W.E.f, d_post, o->ncat, stream);
+}
+
+int tphip_eb_posterior_table(tphip_plan* p, const uint8_t* states, const tphip_eb_opts* o, const double* cat_rate,
+                             const double* cat_weight, const double* scale, double* post, double* rate, double* rate_sd, double* lnl,
+                             int32_t* nres) {
+    int rc = eb_check(p, o, cat_rate, cat_weight, scale);
+    if (rc) return rc;
+    if (!states || !post || !rate || !rate_sd || !lnl || !nres) return fail(TPHIP_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t nc = (size_t)p->ncols, K = (size_t)o->ncat;
+    Staging S;
+    const uint8_t* d_s = S.in(states, nc * (size_t)p->ntaxa);
+    double* d_p = S.out(post, K * nc);
+    double* d_r = S.out(rate, nc);
+    double* d_sd = S.out(rate_sd, nc);
+    double* d_l = S.out(lnl, nc);
+    int32_t* d_n = S.out(nres, nc);
+    if (S.rc) return S.rc;
+    rc = tphip_eb_posterior_table_dev(p, d_s, o, cat_rate, cat_weight, scale, d_p, d_r, d_sd, d_l, d_n, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return S.finish();
 }
 
 int tphip_eb_start_scale_dev(tphip_plan* p, const uint8_t* d_states, double* scale, void* stream) {

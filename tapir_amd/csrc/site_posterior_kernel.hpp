@@ -26,8 +26,11 @@
 
 namespace tphip {
 
-template <int NW, int MODEL>
-__device__ __forceinline__ void site_posterior_body(const PosteriorParams& E) {
+// TABLE = true is the posterior-table variant: besides the moments it stores every category's
+// f_k + log w_k at logp[k * ncols_total + col] (category-major: a wave's lanes write neighbouring columns).  It is a
+// template parameter so that the TABLE = false instantiations keep their code (profiles/r21_device_asm_unchanged.txt).
+template <int NW, int MODEL, bool TABLE = false>
+__device__ __forceinline__ void site_posterior_body(const PosteriorParams& E, double* __restrict__ logp = nullptr) {
     extern __shared__ double lds[];
     double* wtab = lds;
     double* mtab = lds + 64;
@@ -80,6 +83,9 @@ __device__ __forceinline__ void site_posterior_body(const PosteriorParams& E) {
             double fk, gk, hk;
             evaluate_column<NW, false, Regs>(P, R, wtab, etab, stack, col, pk, exp(uk), fk, gk, hk);
             fk += logw[k];
+            if constexpr (TABLE) {
+                if (active) logp[(int64_t)k * P.ncols_total + col] = fk;
+            }
             if (fk > top) {
                 const double r = exp(top - fk);   // exp(-inf) = 0 on the first category
                 z *= r; a *= r; b *= r; m1 *= r; m2 *= r;
@@ -118,5 +124,20 @@ TPHIP_POSTERIOR_KERNEL(2, TPHIP_MODEL_F81)
 TPHIP_POSTERIOR_KERNEL(8, TPHIP_MODEL_F81)
 TPHIP_POSTERIOR_KERNEL(kStreamWords, TPHIP_MODEL_F81)
 #undef TPHIP_POSTERIOR_KERNEL
+
+// the posterior-table variant: six more overloads, for the reason above
+template <int NW, int MODEL>
+struct PosteriorTableArgs : PosteriorTableParams {};
+#define TPHIP_POSTERIOR_TABLE_KERNEL(NW, MODEL)                                                               \
+    __global__ __launch_bounds__(kSiteBlock) void eval_columns_kernel(PosteriorTableArgs<NW, MODEL> E) {      \
+        site_posterior_body<NW, MODEL, true>(E, E.logp);                                                      \
+    }
+TPHIP_POSTERIOR_TABLE_KERNEL(2, TPHIP_MODEL_GTR)
+TPHIP_POSTERIOR_TABLE_KERNEL(8, TPHIP_MODEL_GTR)
+TPHIP_POSTERIOR_TABLE_KERNEL(kStreamWords, TPHIP_MODEL_GTR)
+TPHIP_POSTERIOR_TABLE_KERNEL(2, TPHIP_MODEL_F81)
+TPHIP_POSTERIOR_TABLE_KERNEL(8, TPHIP_MODEL_F81)
+TPHIP_POSTERIOR_TABLE_KERNEL(kStreamWords, TPHIP_MODEL_F81)
+#undef TPHIP_POSTERIOR_TABLE_KERNEL
 
 }  // namespace tphip

@@ -26,7 +26,14 @@ struct PosteriorParams {
     double* second;             // [ncols] posterior second moment of rho
 };
 
+// The posterior-table variant stores, besides the moments, each category's f_k + log w_k.
+struct PosteriorTableParams : PosteriorParams {
+    double* logp;               // [K][ncols] category-major
+};
+
 // variant: 2 / 8 = packed words in registers, kStreamWords = streamed words (more than 64 tips)
 hipError_t launch_site_posterior_kernel(int variant, int model, dim3 grid, size_t lds_bytes, hipStream_t st, const PosteriorParams& E);
+hipError_t launch_site_posterior_table_kernel(int variant, int model, dim3 grid, size_t lds_bytes, hipStream_t st,
+                                              const PosteriorTableParams& E);
 
 }  // namespace tphip

@@ -97,6 +97,30 @@ hipError_t launch_site_posterior_kernel(int variant, int model, dim3 grid, size_
     return hipErrorInvalidValue;
 }
 
+// The posterior-table variant of the mixture kernels: six more eval_columns_kernel overloads.
+template <int NW, int MODEL>
+static hipError_t launch_posterior_table(dim3 grid, size_t lds_bytes, hipStream_t st, const PosteriorTableParams& E) {
+    PosteriorTableArgs<NW, MODEL> A;
+    static_cast<PosteriorTableParams&>(A) = E;
+    eval_columns_kernel<<<grid, dim3(kSiteBlock), lds_bytes, st>>>(A);
+    return hipGetLastError();
+}
+
+template <int MODEL>
+static hipError_t launch_posterior_table_model(int variant, dim3 grid, size_t lds_bytes, hipStream_t st, const PosteriorTableParams& E) {
+    if (variant == 2) return launch_posterior_table<2, MODEL>(grid, lds_bytes, st, E);
+    if (variant == 8) return launch_posterior_table<8, MODEL>(grid, lds_bytes, st, E);
+    if (variant == kStreamWords) return launch_posterior_table<kStreamWords, MODEL>(grid, lds_bytes, st, E);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_site_posterior_table_kernel(int variant, int model, dim3 grid, size_t lds_bytes, hipStream_t st,
+                                              const PosteriorTableParams& E) {
+    if (model == TPHIP_MODEL_F81) return launch_posterior_table_model<TPHIP_MODEL_F81>(variant, grid, lds_bytes, st, E);
+    if (model == TPHIP_MODEL_GTR) return launch_posterior_table_model<TPHIP_MODEL_GTR>(variant, grid, lds_bytes, st, E);
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_scan_counts_kernel(hipStream_t st, const int32_t* count, int64_t nloci, int32_t chunk_cols, int64_t* prefix,
                                      int64_t* slice_prefix, const ScanClasses* C) {
     if (C) scan_classes_kernel<<<dim3(1), dim3(1024), 0, st>>>(count, nloci, chunk_cols, prefix, slice_prefix, *C);

@@ -286,6 +286,9 @@ __attribute__((visibility("hidden"))) int tphip_internal_compress_dev(const uint
                                                                     int64_t** d_newoff, double** d_w, int64_t* npat);
 __attribute__((visibility("hidden"))) int tphip_internal_eb_prepare(tphip_plan* p, const uint8_t* d_states, const EbPrep* B,
                                                                   int32_t use_patterns, double* d_start, void* stream);
+// posterior_pi_driver.hip, for tphip_eb_posterior_table: d_post holds f_k + log w_k of the representatives on entry
+__attribute__((visibility("hidden"))) int tphip_internal_posterior_normalize(tphip_plan* p, const int32_t* d_dup_of, const double* d_f,
+                                                                           double* d_post, int32_t K, void* stream);
 __attribute__((visibility("hidden"))) int tphip_internal_store_pi(tphip_plan* p, const double* pi);
 __attribute__((visibility("hidden"))) int tphip_internal_set_models_dev(tphip_plan* p, const double* d_pi, const double* d_exch,
                                                                       void* stream);

@@ -132,6 +132,67 @@ def write_bootstrap_db(db_name, names, summary, T, times, intervals, replicates,
     conn.close()
 
 
+POSTERIOR_DDL = [
+    "CREATE TABLE loci (id INTEGER PRIMARY KEY AUTOINCREMENT, locus TEXT)",
+    "CREATE TABLE net_posterior (id INT, time INT, mean FLOAT, sd FLOAT, lo FLOAT, hi FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE discrete_posterior (id INT, time INT, mean FLOAT, sd FLOAT, lo FLOAT, hi FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE interval_posterior (id INT, interval TEXT, mean FLOAT, sd FLOAT, lo FLOAT, hi FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE category (id INT, k INT, rate FLOAT, expected_sites FLOAT, FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE meta (key TEXT PRIMARY KEY, value TEXT)",
+]
+
+
+def write_posterior_db(db_name, names, bands, category_rate, expected_sites, alpha, scale, T, times, intervals, replicates, seed,
+                       level):
+    """phylogenetic-informativeness-posterior.sqlite (--posterior-pi), a file of its own laid out like the bootstrap file; the main
+    database stays byte for byte what it is without the flag.  bands [L, 4, T + n_i] = mean, sd, lo, hi per locus
+    (pipeline.posterior_pi_tables): mean and sd are the analytic moments of the locus' PI row under the empirical-Bayes rate
+    posterior, lo and hi the quantiles of the `replicates` posterior draws.  category_rate and expected_sites [L, K]: the final
+    rate of every gamma category and the expected number of informative sites in it.  meta: replicates, seed, level,
+    categories, and alpha_<id> / scale_<id> per locus -- everything is conditional on that fit."""
+    import numpy as np
+    if os.path.exists(db_name):
+        os.remove(db_name)
+    conn = sqlite3.connect(db_name)
+    c = conn.cursor()
+    for stmt in POSTERIOR_DDL:
+        c.execute(stmt)
+    L, n_t, n_i = len(names), len(times), len(intervals)
+    bands = np.asarray(bands, dtype=np.float64).reshape(L, 4, T + n_i)
+    category_rate = np.asarray(category_rate, dtype=np.float64).reshape(L, -1)
+    expected_sites = np.asarray(expected_sites, dtype=np.float64).reshape(L, -1)
+    K = category_rate.shape[1]
+    c.executemany("INSERT INTO loci(locus) VALUES (?)", [(locus_name(n),) for n in names])
+    keys = np.asarray([r[0] for r in c.execute("SELECT id FROM loci ORDER BY id").fetchall()], dtype=np.int64)
+
+    def stats(block):   # [L, 4, k] -> four flat columns, locus by locus
+        return [block[:, j, :].reshape(-1).tolist() for j in range(4)]
+
+    if L and T:
+        c.executemany("INSERT INTO net_posterior VALUES (?,?,?,?,?,?)",
+                      zip(np.repeat(keys, T).tolist(), np.tile(np.arange(T), L).tolist(), *stats(bands[:, :, :T])))
+    if L and n_t:
+        tt = np.asarray(times, dtype=np.int64)
+        c.executemany("INSERT INTO discrete_posterior VALUES (?,?,?,?,?,?)",
+                      zip(np.repeat(keys, n_t).tolist(), np.tile(tt, L).tolist(), *stats(bands[:, :, tt])))
+    if L and n_i:
+        labels = ["{0}-{1}".format(a, b) for a, b in intervals]
+        c.executemany("INSERT INTO interval_posterior VALUES (?,?,?,?,?,?)",
+                      zip(np.repeat(keys, n_i).tolist(), labels * L, *stats(bands[:, :, T:])))
+    if L and K:
+        c.executemany("INSERT INTO category VALUES (?,?,?,?)",
+                      zip(np.repeat(keys, K).tolist(), np.tile(np.arange(K), L).tolist(), category_rate.reshape(-1).tolist(),
+                          expected_sites.reshape(-1).tolist()))
+    c.executemany("INSERT INTO meta VALUES (?,?)", [("replicates", str(int(replicates))), ("seed", str(int(seed))),
+                                                    ("level", repr(float(level))), ("categories", str(int(K)))])
+    c.executemany("INSERT INTO meta VALUES (?,?)",
+                  [("alpha_%d" % k, repr(float(a))) for k, a in zip(keys.tolist(), np.asarray(alpha, dtype=np.float64).reshape(-1))] +
+                  [("scale_%d" % k, repr(float(s))) for k, s in zip(keys.tolist(), np.asarray(scale, dtype=np.float64).reshape(-1))])
+    conn.commit()
+    c.close()
+    conn.close()
+
+
 QUARTET_DDL = [
     "CREATE TABLE loci (id INTEGER PRIMARY KEY AUTOINCREMENT, locus TEXT)",
     "CREATE TABLE quartet (id INT, quartet TEXT, tip FLOAT, internode FLOAT, signal FLOAT, noise FLOAT, p_correct FLOAT, "

@@ -113,6 +113,24 @@ class _Calls:
         torch.cuda.synchronize(dev)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
+    def posterior_table(self, alpha, ncat, scale):
+        """posterior() with the category posterior p[K, ncols] besides ("post"); it stays on the device (a torch tensor, with
+        "nres_dev" beside it) when the engine works on device pointers, for posterior_pi below."""
+        rates, weights = gamma_tables(alpha, ncat)
+        if self.d_states is None:
+            return self.plan.eb_posterior_table(self.states, rates, weights, scale, use_patterns=self.use_patterns)
+        import torch
+        dev, n = self.d_states.device, self.states.shape[1]
+        out = {k: torch.empty(n, dtype=torch.float64, device=dev) for k in ("rate", "sd", "lnl")}
+        out["nres"] = torch.empty(n, dtype=torch.int32, device=dev)
+        post = torch.empty((int(ncat), n), dtype=torch.float64, device=dev)
+        self.plan.eb_posterior_table_dev(self.d_states, rates, weights, scale, post, out["rate"], out["sd"], out["lnl"], out["nres"],
+                                         use_patterns=self.use_patterns)
+        torch.cuda.synchronize(dev)
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+        host["post"], host["nres_dev"] = post, out["nres"]
+        return host
+
     def fit_scale(self, alpha, ncat, scale):
         rates, weights = gamma_tables(alpha, ncat)
         if self.d_states is not None:
@@ -168,14 +186,46 @@ def fit(plan, states, start=None, ncat=DEFAULT_CATEGORIES, alpha=None, alpha_bou
                 evaluations=calls.evaluations)
 
 
-def estimate(plan, states, ncat=DEFAULT_CATEGORIES, alpha=None, alpha_bounds=ALPHA_BOUNDS, use_patterns=True):
+def posterior_table(plan, states, alpha, scale, ncat=DEFAULT_CATEGORIES, use_patterns=True):
+    """The per-column posterior at given (alpha[L], scale[L]) with the category posterior p[K, ncols] as "post" (DESIGN section
+    3.10); "post" is a device tensor when the engine works on device pointers (see posterior_pi)."""
+    return _Calls(plan, states, use_patterns).posterior_table(np.asarray(alpha, np.float64).reshape(-1), ncat, scale)
+
+
+def posterior_pi(plan, table, alpha, scale, replicates, seed=1, level=0.95, locus_ids=None):
+    """The rate posterior of posterior_table / estimate(table=True) carried into the PI rows (Plan.posterior_pi; conditional on
+    the fitted alpha and scale): dict(analytic [L, 2, Wb], expected_counts [L, K], summary [L, 4, Wb]).  A table on the device
+    is read where it lies; only the small per-locus results come back."""
+    post = table["post"]
+    K = int(post.shape[0])
+    rho, _ = gamma_tables(alpha, K)
+    if isinstance(post, np.ndarray):
+        return plan.posterior_pi(post, table["nres"], scale, rho, replicates=replicates, seed=seed, level=level, locus_ids=locus_ids)
+    import torch
+    dev, L, Wb = post.device, int(plan.nloci), int(plan.bootstrap_width)
+    out = dict(analytic=torch.zeros((L, 2, Wb), dtype=torch.float64, device=dev),
+               expected_counts=torch.zeros((L, K), dtype=torch.float64, device=dev),
+               summary=torch.zeros((L, 4, Wb), dtype=torch.float64, device=dev))
+    ws = torch.empty(plan.posterior_pi_workspace_bytes(K, replicates, seed, level)[1], dtype=torch.uint8, device=dev)
+    d_scale = torch.from_numpy(np.ascontiguousarray(scale, np.float64)).to(dev)
+    d_rho = torch.from_numpy(np.ascontiguousarray(rho, np.float64)).to(dev)
+    plan.posterior_pi_dev(post, table["nres_dev"], d_scale, d_rho, K, out["analytic"], out["expected_counts"], out["summary"], None,
+                          None, ws, replicates, seed=seed, level=level, locus_ids=locus_ids)
+    torch.cuda.synchronize(dev)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def estimate(plan, states, ncat=DEFAULT_CATEGORIES, alpha=None, alpha_bounds=ALPHA_BOUNDS, use_patterns=True, table=False):
     """The whole estimator for the loci of `plan`: the engine's start scales, the fit of (mu, alpha) per locus, then the
     per-column posterior; the alignment is uploaded once.
-    Returns dict(rate, sd, lnl, nres [ncols]; alpha, scale, locus_lnl [L]; rounds, evaluations)."""
+    Returns dict(rate, sd, lnl, nres [ncols]; alpha, scale, locus_lnl [L]; rounds, evaluations); with table=True also
+    "post", the category posterior p[K, ncols] (kept on the device when the engine can: see posterior_table)."""
     calls = _Calls(plan, states, use_patterns)
     f = fit(plan, states, None, ncat=ncat, alpha=alpha, alpha_bounds=alpha_bounds, use_patterns=use_patterns, calls=calls)
-    post = calls.posterior(f["alpha"], ncat, f["scale"])
+    post = calls.posterior_table(f["alpha"], ncat, f["scale"]) if table else calls.posterior(f["alpha"], ncat, f["scale"])
     out = dict(rate=post["rate"], sd=post["sd"], lnl=post["lnl"], nres=post["nres"])
+    if table:
+        out.update({k: post[k] for k in ("post", "nres_dev") if k in post})
     out.update(alpha=f["alpha"], scale=f["scale"], locus_lnl=f["locus_lnl"], rounds=f["rounds"], evaluations=f["evaluations"],
                categories=int(ncat))
     return out

@@ -55,6 +55,11 @@ class BootstrapOpts(ctypes.Structure):
                 ("locus_ids", _vp)]
 
 
+class PosteriorPiOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("replicates", _i32), ("level", _f64), ("seed", ctypes.c_uint64),
+                ("locus_ids", _vp), ("ncat", _i32)]
+
+
 class QuartetOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("tip", _vp), ("internode", _vp)]
 
@@ -130,6 +135,12 @@ SYMBOLS = [
     ("tphip_eb_fit_scale_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tphip_eb_posterior", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tphip_eb_posterior_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tphip_eb_posterior_table", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts)] + [_vp] * 8),
+    ("tphip_eb_posterior_table_dev", ctypes.c_int, [_vp, _vp, ctypes.POINTER(EbOpts)] + [_vp] * 9),
+    ("tphip_posterior_pi_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(PosteriorPiOpts), ctypes.POINTER(ctypes.c_size_t),
+                                                          ctypes.POINTER(ctypes.c_size_t)]),
+    ("tphip_posterior_pi_dev", ctypes.c_int, [_vp] * 5 + [ctypes.POINTER(PosteriorPiOpts)] + [_vp] * 6 + [ctypes.c_size_t, _vp]),
+    ("tphip_posterior_pi", ctypes.c_int, [_vp] * 5 + [ctypes.POINTER(PosteriorPiOpts)] + [_vp] * 5),
     ("tphip_bootstrap_width", _i32, [_vp]),
     ("tphip_bootstrap_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(BootstrapOpts), ctypes.POINTER(ctypes.c_size_t),
                                                        ctypes.POINTER(ctypes.c_size_t)]),
@@ -493,6 +504,85 @@ class Plan:
         opts, cr, cw, sc = self._eb_args(cat_rate, cat_weight, scale, use_patterns)
         _check(self._lib.tphip_eb_posterior_dev(self._h, _ptr(d_states), ctypes.byref(opts), cr.ctypes.data, cw.ctypes.data,
                                                 sc.ctypes.data, _ptr(d_rate), _ptr(d_sd), _ptr(d_lnl), _ptr(d_nres), stream))
+
+    # ---- the EB rate posterior carried into the PI rows (csrc/posterior_pi_driver.hip) ----
+    def eb_posterior_table(self, states, cat_rate, cat_weight, scale, use_patterns=True):
+        """eb_posterior with the category posterior besides (tphip_eb_posterior_table): post [K, ncols], p_ck."""
+        states = _np(states, np.uint8)
+        opts, cr, cw, sc = self._eb_args(cat_rate, cat_weight, scale, use_patterns)
+        post = np.zeros((cr.shape[1], self.ncols))
+        rate, sd, lnl = np.empty(self.ncols), np.empty(self.ncols), np.empty(self.ncols)
+        nres = np.empty(self.ncols, dtype=np.int32)
+        _check(self._lib.tphip_eb_posterior_table(self._h, states.ctypes.data, ctypes.byref(opts), cr.ctypes.data, cw.ctypes.data,
+                                                  sc.ctypes.data, post.ctypes.data, rate.ctypes.data, sd.ctypes.data,
+                                                  lnl.ctypes.data, nres.ctypes.data))
+        return dict(post=post, rate=rate, sd=sd, lnl=lnl, nres=nres)
+
+    def eb_posterior_table_dev(self, d_states, cat_rate, cat_weight, scale, d_post, d_rate, d_sd, d_lnl, d_nres, use_patterns=True,
+                               stream=0):
+        opts, cr, cw, sc = self._eb_args(cat_rate, cat_weight, scale, use_patterns)
+        _check(self._lib.tphip_eb_posterior_table_dev(self._h, _ptr(d_states), ctypes.byref(opts), cr.ctypes.data, cw.ctypes.data,
+                                                      sc.ctypes.data, _ptr(d_post), _ptr(d_rate), _ptr(d_sd), _ptr(d_lnl),
+                                                      _ptr(d_nres), stream))
+
+    def _posterior_pi_opts(self, ncat, replicates, seed, level, locus_ids):
+        ids = None
+        if locus_ids is not None:
+            ids = _np(locus_ids, np.int64).reshape(-1)
+            if ids.size != self.nloci:
+                raise TphipError("locus_ids must have one entry per locus of the plan")
+        opts = PosteriorPiOpts(struct_size=ctypes.sizeof(PosteriorPiOpts), replicates=int(replicates), level=float(level),
+                               seed=int(seed) & 0xFFFFFFFFFFFFFFFF, locus_ids=_ptr(ids), ncat=int(ncat))
+        return opts, ids
+
+    def posterior_pi_workspace_bytes(self, ncat, replicates, seed=1, level=0.95):
+        """(min, preferred) bytes of device workspace for posterior_pi_dev; any size >= min gives the same bits."""
+        opts, _ = self._posterior_pi_opts(ncat, replicates, seed, level, None)
+        mn, pf = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(self._lib.tphip_posterior_pi_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(mn), ctypes.byref(pf)))
+        return mn.value, pf.value
+
+    def posterior_pi(self, post, nres, scale, cat_rate, replicates=200, seed=1, level=0.95, locus_ids=None, return_rows=False,
+                     return_counts=False):
+        """The EB rate posterior carried into the PI rows (tphip_posterior_pi), conditional on the fitted scale and prior.
+        post [K, ncols] from eb_posterior_table, nres [ncols] or None (no cull), scale [L], cat_rate [L, K].
+        Returns dict(analytic [L, 2, Wb] = mean, sd; expected_counts [L, K]; summary [L, 4, Wb] = mean, sd, lo, hi over the
+        `replicates` draws) and, on request, rows [L, B, Wb] and counts int32 [L, B, K]."""
+        cr = _np(cat_rate, np.float64)
+        if cr.ndim != 2 or cr.shape[0] != self.nloci:
+            raise TphipError("cat_rate must be [nloci][ncat]")
+        K = int(cr.shape[1])
+        post = _np(post, np.float64)
+        if post.shape != (K, self.ncols):
+            raise TphipError("post must be [ncat, ncols]")
+        sc = _np(scale, np.float64).reshape(-1)
+        if sc.shape != (self.nloci,):
+            raise TphipError("scale must be [nloci]")
+        if nres is not None:
+            nres = _np(nres, np.int32)
+            if nres.shape != (self.ncols,):
+                raise TphipError("nres must be [ncols]")
+        opts, ids = self._posterior_pi_opts(K, replicates, seed, level, locus_ids)
+        Wb, B = self.bootstrap_width, int(replicates)
+        out = dict(analytic=np.zeros((self.nloci, 2, Wb)), expected_counts=np.zeros((self.nloci, K)),
+                   summary=np.zeros((self.nloci, 4, Wb)))
+        if return_rows:
+            out["rows"] = np.zeros((self.nloci, max(B, 0), Wb))
+        if return_counts:
+            out["counts"] = np.zeros((self.nloci, max(B, 0), K), dtype=np.int32)
+        _check(self._lib.tphip_posterior_pi(self._h, post.ctypes.data, _ptr(nres), sc.ctypes.data, cr.ctypes.data, ctypes.byref(opts),
+                                            out["analytic"].ctypes.data, out["expected_counts"].ctypes.data,
+                                            out["summary"].ctypes.data, _ptr(out.get("rows")), _ptr(out.get("counts"))))
+        return out
+
+    def posterior_pi_dev(self, d_post, d_nres, d_scale, d_cat_rate, ncat, d_analytic, d_expected, d_summary, d_rows, d_counts, d_ws,
+                         replicates, seed=1, level=0.95, locus_ids=None, stream=0, ws_bytes=None):
+        """tphip_posterior_pi_dev on device tensors (d_nres / d_rows / d_counts may be None); ws_bytes: use only that much of d_ws."""
+        opts, ids = self._posterior_pi_opts(ncat, replicates, seed, level, locus_ids)
+        nbytes = _nbytes(d_ws) if ws_bytes is None else int(ws_bytes)
+        _check(self._lib.tphip_posterior_pi_dev(self._h, _ptr(d_post), _ptr(d_nres), _ptr(d_scale), _ptr(d_cat_rate), ctypes.byref(opts),
+                                                _ptr(d_analytic), _ptr(d_expected), _ptr(d_summary), _ptr(d_rows), _ptr(d_counts),
+                                                _ptr(d_ws), nbytes, stream))
 
     def corrected_rates(self, rates, nres=None):
         """parse_site_rates (+ cull when nres is given) as the PI stage applies them: round4(rate) / correction."""

@@ -895,6 +895,75 @@ def parametric_bootstrap_tables(eng, alignments, per_locus, models, leaf_names, 
     return summary, moments
 
 
+# posterior_pi_tables works through the loci in blocks whose category posterior ([K][columns] doubles) stays within this many
+# bytes of device memory
+POSTERIOR_PI_BYTES = 256 << 20
+
+
+def posterior_pi_tables(eng, alignments, per_locus, models, ebfit, leaf_names, parent, blen, leaf, T, intervals, correction,
+                        threshold, round_decimals, device, integ_mode, locus_ids, replicates, seed=1, level=0.95, subsets=None):
+    """The empirical-Bayes rate posterior carried into the PI rows, beside bootstrap_tables: per locus
+    the analytic mean and sd of the net-PI profile and of the interval integrals under the posterior of the sites' rate
+    categories, and the band [lo, hi] of `replicates` posterior draws.  Returns dict(bands [L, 4, T + n_i] = mean, sd, lo, hi;
+    category_rate [L, K] = the categories' final rates; expected_sites [L, K] = the informative sites expected in each).
+
+    alignments: the loci's NEXUS files, re-read here and sliced for `subsets` as parametric_bootstrap_tables does (a column's
+    posterior depends on the column and the locus' fit only).  per_locus: the run's final rates (their lengths are checked).
+    models: run_alignments' out["models"]; ebfit: its out["eb"] (alpha, scale, categories).  The plans carry the run's real
+    correction, threshold and round_decimals.  The loci go through in blocks whose [K][columns] table fits
+    POSTERIOR_PI_BYTES; a locus' results depend on nothing beside it, so the blocking changes no bit.  locus_ids: the
+    generator's stream ids -- the command line passes the global file indices.  Everything is conditional on the fitted
+    (scale, alpha), the model and the tree: the bands carry the posterior of the sites' rates, not the uncertainty of the fit."""
+    from . import eb
+    subsets = subsets or {}
+    L, Wb = len(alignments), T + len(intervals)
+    K = int(ebfit["categories"]) if L else 0
+    out = dict(bands=np.zeros((L, 4, Wb)), category_rate=np.zeros((L, K)), expected_sites=np.zeros((L, K)))
+    if L == 0:
+        return out
+    model = models["model"]
+    pi = np.asarray(models["pi"], dtype=np.float64).reshape(L, 4)
+    exch = None if model == "f81" else np.asarray(models["exch"], dtype=np.float64).reshape(L, 6)
+    alpha = np.asarray(ebfit["alpha"], dtype=np.float64).reshape(L)
+    scale = np.asarray(ebfit["scale"], dtype=np.float64).reshape(L)
+    ids = np.asarray(locus_ids, dtype=np.int64)
+    block_cols = max(1, POSTERIOR_PI_BYTES // (8 * K))
+    l0 = 0
+    while l0 < L:
+        l1, cols = l0, 0
+        while l1 < L and (l1 == l0 or cols + len(per_locus[l1]) <= block_cols):
+            cols += len(per_locus[l1])
+            l1 += 1
+        states, off = load_alignments(alignments[l0:l1], leaf_names)
+        blocks = []
+        for k, a in enumerate(alignments[l0:l1]):
+            blk = states[:, off[k]:off[k + 1]]
+            base = os.path.basename(a)
+            if base in subsets:
+                blk = blk[:, subsets[base][0]:subsets[base][1]]
+            if blk.shape[1] != len(per_locus[l0 + k]):
+                raise PipelineError("{0}: {1} columns, but {2} final rates".format(base, blk.shape[1], len(per_locus[l0 + k])))
+            blocks.append(blk)
+        states = np.ascontiguousarray(np.concatenate(blocks, axis=1))
+        offsets = np.concatenate([[0], np.cumsum([b.shape[1] for b in blocks])]).astype(np.int64)
+        plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi[l0:l1], None if exch is None else exch[l0:l1], T, [],
+                        intervals, correction=correction, threshold=threshold, round_decimals=round_decimals,
+                        integ_mode=integ_mode, device=device, model=model)
+        try:
+            table = eb.posterior_table(plan, states, alpha[l0:l1], scale[l0:l1], ncat=K)
+            res = eb.posterior_pi(plan, table, alpha[l0:l1], scale[l0:l1], replicates, seed=seed, level=level, locus_ids=ids[l0:l1])
+            kappa = np.asarray(plan.models()[3], dtype=np.float64)
+        finally:
+            plan.close()
+        out["bands"][l0:l1, :2] = res["analytic"]
+        out["bands"][l0:l1, 2:] = res["summary"][:, 2:]
+        out["expected_sites"][l0:l1] = res["expected_counts"]
+        raw = (kappa * scale[l0:l1])[:, None] * eb.gamma_tables(alpha[l0:l1], K)[0]
+        out["category_rate"][l0:l1] = (compute.round_like_hyphy(raw, round_decimals) if round_decimals >= 0 else raw) / correction
+        l0 = l1
+    return out
+
+
 def _write_rate_moments_file(path, mean, sd):
     """NAME.rates-bootstrap.json: mean and sd of every site's final rate over the parametric replicates, null for culled sites."""
     import json
