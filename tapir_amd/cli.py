@@ -29,6 +29,7 @@ models_and_rates.bf:405-897) runs on the GPU too (tapir_amd/stage1.py) unless th
 with --exchangeabilities / --subs-model, or a fixed model is chosen with --site-model jc / f81.
 """
 import argparse
+import dataclasses
 import os
 import sys
 
@@ -176,27 +177,10 @@ def get_args(argv=None):
         if given and args.site_rates and args.site_model == 'locus' and args.exchangeabilities is None:
             parser.error("{0} needs the loci's substitution model, which --site-rates does not read: "
                          "add --site-model jc, --site-model f81 or --exchangeabilities".format(flag))
-    if args.bootstrap == 0:
-        for flag, value in (('--bootstrap-seed', args.bootstrap_seed), ('--bootstrap-level', args.bootstrap_level)):
-            if value is not None:
-                parser.error("{0} needs --bootstrap".format(flag))
-    else:
-        if not 2 <= args.bootstrap <= 4096:
-            parser.error("--bootstrap must be in 2..4096")
-        if args.bootstrap_seed is None:
-            args.bootstrap_seed = 1
-        if not 0 <= args.bootstrap_seed < 2 ** 64:
-            parser.error("--bootstrap-seed must be in 0..2^64-1")
-        if args.bootstrap_level is None:
-            args.bootstrap_level = 0.95
-        if not 0.0 < args.bootstrap_level < 1.0:
-            parser.error("--bootstrap-level must be in (0, 1)")
-    if args.parametric_bootstrap == 0:
-        for flag, value in (('--parametric-bootstrap-seed', args.parametric_bootstrap_seed),
-                            ('--parametric-bootstrap-level', args.parametric_bootstrap_level)):
-            if value is not None:
-                parser.error("{0} needs --parametric-bootstrap".format(flag))
-    else:
+    if args.bootstrap and not 2 <= args.bootstrap <= 4096:
+        parser.error("--bootstrap must be in 2..4096")
+    _seed_and_level(parser, args, '--bootstrap')
+    if args.parametric_bootstrap:
         if not 2 <= args.parametric_bootstrap <= 4096:
             parser.error("--parametric-bootstrap must be in 2..4096")
         if args.site_rates:
@@ -205,14 +189,7 @@ def get_args(argv=None):
             parser.error("--parametric-bootstrap re-estimates maximum-likelihood rates: it cannot be combined with --rate-estimator eb")
         if args.gamma_categories > 1:
             parser.error("--parametric-bootstrap has no rate mixture: it cannot be combined with --gamma-categories above 1")
-        if args.parametric_bootstrap_seed is None:
-            args.parametric_bootstrap_seed = 1
-        if not 0 <= args.parametric_bootstrap_seed < 2 ** 64:
-            parser.error("--parametric-bootstrap-seed must be in 0..2^64-1")
-        if args.parametric_bootstrap_level is None:
-            args.parametric_bootstrap_level = 0.95
-        if not 0.0 < args.parametric_bootstrap_level < 1.0:
-            parser.error("--parametric-bootstrap-level must be in (0, 1)")
+    _seed_and_level(parser, args, '--parametric-bootstrap')
     if args.site_model != 'locus':
         for flag, given in (('--exchangeabilities', args.exchangeabilities is not None), ('--subs-model', bool(args.subs_model)),
                             # (with a quartet flag: the model of that stage)
@@ -240,24 +217,31 @@ def get_args(argv=None):
             args.eb_alpha_bounds = (0.2, 50.0)
         if not 0 < args.eb_alpha_bounds[0] < args.eb_alpha_bounds[1]:
             parser.error("--eb-alpha-bounds must be LO,HI with 0 < LO < HI")
-    if args.posterior_pi == 0:
-        for flag, value in (('--posterior-pi-seed', args.posterior_pi_seed), ('--posterior-pi-level', args.posterior_pi_level)):
-            if value is not None:
-                parser.error("{0} needs --posterior-pi".format(flag))
-    else:
+    if args.posterior_pi:
         if args.rate_estimator != 'eb':
             parser.error("--posterior-pi carries the empirical-Bayes rate posterior: it needs --rate-estimator eb")
         if not 2 <= args.posterior_pi <= 4096:
             parser.error("--posterior-pi must be in 2..4096")
-        if args.posterior_pi_seed is None:
-            args.posterior_pi_seed = 1
-        if not 0 <= args.posterior_pi_seed < 2 ** 64:
-            parser.error("--posterior-pi-seed must be in 0..2^64-1")
-        if args.posterior_pi_level is None:
-            args.posterior_pi_level = 0.95
-        if not 0.0 < args.posterior_pi_level < 1.0:
-            parser.error("--posterior-pi-level must be in (0, 1)")
+    _seed_and_level(parser, args, '--posterior-pi')
     return args
+
+
+def _seed_and_level(parser, args, flag):
+    """The seed and level of a replicate stage (--bootstrap, --parametric-bootstrap, --posterior-pi), after the stage's own
+    checks: given without the stage they are an error, with it they get their defaults and their ranges are held."""
+    name = flag[2:].replace('-', '_')
+    seed, level = getattr(args, name + '_seed'), getattr(args, name + '_level')
+    if not getattr(args, name):
+        for what, value in (('seed', seed), ('level', level)):
+            if value is not None:
+                parser.error("{0}-{1} needs {0}".format(flag, what))
+        return
+    setattr(args, name + '_seed', 1 if seed is None else seed)
+    if not 0 <= getattr(args, name + '_seed') < 2 ** 64:
+        parser.error("{0}-seed must be in 0..2^64-1".format(flag))
+    setattr(args, name + '_level', 0.95 if level is None else level)
+    if not 0.0 < getattr(args, name + '_level') < 1.0:
+        parser.error("{0}-level must be in (0, 1)".format(flag))
 
 
 def _six_floats(string):
@@ -402,6 +386,88 @@ def main(argv=None, engine_mod=None):
             pool.close()
 
 
+class _ProbeDb:
+    """phylogenetic-informativeness.sqlite: opened at the first call, committed and closed by close(), its seconds in
+    LAST_TIMINGS["sqlite"].  Whole on one thread (sqlite objects live and die on the thread that made them): the main one,
+    or the one run_alignments hands store() or add() / close() to while the `.rates` files are written."""
+
+    def __init__(self, name, run):
+        self.name, self.run, self.conn, self.seconds = name, run, None, 0.0
+
+    def _timed(self, fn, *rows):
+        import time
+        t0 = time.perf_counter()
+        if self.conn is None:
+            self.conn, self.c = db.create_probe_db(self.name)
+        fn(self.conn, self.c, *rows)
+        self.seconds += time.perf_counter() - t0
+
+    def add(self, names, tables):   # rows block by block, in file order (pipeline._run_streamed), or all at once
+        self._timed(db.insert_tables, names, tables, self.run.T, self.run.times, self.run.intervals)
+
+    def store(self, pis):   # tapir_compute.py's last step
+        self._timed(db.insert_pi_data, pis)
+        self.close()
+
+    def close(self):
+        self._timed(lambda conn, c: (conn.commit(), c.close(), conn.close()))
+        LAST_TIMINGS["sqlite"] = self.seconds
+
+
+@dataclasses.dataclass
+class _Stage:
+    """What the opt-in stages after the main database work on, in one process: every rank takes its own loci (`mine`, the
+    global file indices `ids`: the generators' stream ids, so nothing depends on the world size) with their final rates and
+    the models and fits of its own run; rank 0 writes the stage's database."""
+    args: object
+    rank: int
+    world: int
+    on_gpu: bool
+    eng: object
+    run: pipeline.Run
+    files: list
+    mine: list
+    ids: list
+    per_locus: list
+    models: dict
+    ebfit: dict
+    subsets: dict
+
+    def gather(self, rows):
+        """[n_local, ...] rows of this rank's files -> [nfiles, ...] in file order: the one collective of a stage (none when
+        a row is empty: a tree without an internode and nothing typed)."""
+        shape, n = rows.shape[1:], len(self.files)
+        width = int(np.prod(shape))
+        if width == 0:
+            return np.zeros((n,) + shape)
+        return _gather_rows(rows.reshape(len(self.ids), width), n, self.rank, self.world, self.on_gpu).reshape((n,) + shape)
+
+    def stage_models(self):
+        """The loci's models: the main run's (a rank without loci: none); under --site-rates, which reads rates only,
+        Jukes-Cantor, or the base frequencies the `.rates` documents carry with exchangeabilities of 1 (f81) or the
+        --exchangeabilities given."""
+        args, L = self.args, len(self.mine)
+        if not args.site_rates:
+            return self.models if self.models is not None else dict(
+                pi=np.zeros((0, 4)), exch=np.zeros((0, 6)), model="gtr" if args.site_model == 'locus' else "f81")
+        if args.site_model == 'jc':
+            return dict(pi=np.full((L, 4), 0.25), exch=None, model="f81")
+        import json
+        pi = np.empty((L, 4))
+        for l, f in enumerate(self.mine):
+            with open(f) as fh:
+                freqs = json.load(fh)["sites"].get("freqs")
+            if not freqs:
+                raise IOError("{0} carries no base frequencies (\"freqs\"): --quartets can only use --site-model jc with it".format(f))
+            pi[l] = [freqs[k] for k in "ACGT"]
+        if args.site_model == 'f81':
+            return dict(pi=pi, exch=None, model="f81")
+        return dict(pi=pi, exch=np.tile(np.array(args.exchangeabilities, dtype=np.float64), (L, 1)), model="gtr")
+
+    def path(self, name):
+        return os.path.join(self.args.output, name)
+
+
 def _main(args, rank, world, on_gpu, engine_mod, pool):
     if world > 1:
         tdist.init_process_group(None if on_gpu else "gloo")
@@ -415,8 +481,6 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
     else:
         setup = None
     args.output, tree_depth, correction, tree = _broadcast(setup, rank, world)
-    # generate a vector of times given start and stops
-    T = int(tree_depth)
     for label, tip, internode in args.quartets or []:
         if tip + internode > tree_depth:
             raise ValueError("--quartets {0}: T + to = {1} exceeds the tree depth {2}".format(label, tip + internode, tree_depth))
@@ -426,236 +490,78 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
     root = newick.read_tree(tree, 'newick')
     leaf_names = [n.name for n in newick.leaves(root)]
     parent, blen, leaf = newick.to_arrays(root, leaf_names)
-    integ_mode = 0 if args.integral_mode == 'quadpack' else 1
-    progress = pipeline.dot_progress if rank == 0 else None
     cat_rates, cat_weights = (compute.discrete_gamma(args.gamma_alpha, args.gamma_categories)
                               if args.gamma_categories > 1 else (None, None))
-    W = T + len(args.times) + 2 * len(args.intervals)
+    # T: a vector of times given start and stops
+    run = pipeline.Run(leaf_names, parent, blen, leaf, int(tree_depth), args.times, args.intervals, correction=correction,
+                       threshold=args.threshold, round_decimals=-1 if args.full_precision_rates else 4,
+                       integ_mode=0 if args.integral_mode == 'quadpack' else 1, device=args.device,
+                       start_rule=1 if args.reference_start else 0, cat_rates=cat_rates, cat_weights=cat_weights)
+    eng = engine_mod
+    if eng is None:
+        from . import engine as eng
+    progress = pipeline.dot_progress if rank == 0 else None
     db_name = os.path.join(args.output, 'phylogenetic-informativeness.sqlite')
+    probe_db = _ProbeDb(db_name, run)
     stored = False
-
-    def store(pis):   # tapir_compute.py's last step; single process: may run while the pool writes the .rates files
-        import time
-        t_db = time.perf_counter()
-        conn, c = db.create_probe_db(db_name)
-        db.insert_pi_data(conn, c, pis)
-        conn.commit()
-        c.close()
-        conn.close()
-        LAST_TIMINGS["sqlite"] = time.perf_counter() - t_db
-
-    class _TableSink:
-        """sqlite rows block by block, in file order, while later blocks are still being computed (pipeline._run_streamed)"""
-
-        def __init__(self):
-            self.conn = self.c = None
-            self.seconds = 0.0
-
-        def add(self, names, tables):
-            import time
-            t0 = time.perf_counter()
-            if self.conn is None:
-                self.conn, self.c = db.create_probe_db(db_name)
-            db.insert_tables(self.conn, self.c, names, tables, T, args.times, args.intervals)
-            self.seconds += time.perf_counter() - t0
-
-        def close(self):
-            import time
-            t0 = time.perf_counter()
-            if self.conn is None:
-                self.conn, self.c = db.create_probe_db(db_name)
-            self.conn.commit()
-            self.c.close()
-            self.conn.close()
-            self.seconds += time.perf_counter() - t0
-            LAST_TIMINGS["sqlite"] = self.seconds
-
-    if not args.site_rates:
-        if rank == 0:
-            print("\nEstimating site rates and PI for files:")
-        files = base.get_files(args.alignments, '*.nex,*.nexus')
-        mine = [files[i] for i in tdist.shard_loci(len(files), rank, world)]
+    pis, tables, models, ebfit = [], np.zeros((0, run.width)), None, None
+    if rank == 0:
+        print("Estimating PI for files (--site-rate option):" if args.site_rates else "\nEstimating site rates and PI for files:")
+    files = base.get_files(args.alignments, '*.rates' if args.site_rates else '*.nex,*.nexus')
+    ids = list(tdist.shard_loci(len(files), rank, world))
+    mine = [files[i] for i in ids]
+    if mine and args.site_rates:
+        pis, tables = pipeline.run_rate_files(mine, run, subsets=subset_pi, engine_mod=eng, progress=progress, return_tables=True)
+    elif mine:
         exch, pi = None, None  # None: fit and model-average the exchangeabilities per locus (HyPhy stage 1)
         if args.exchangeabilities is not None:
             exch = np.array(args.exchangeabilities)
         if args.subs_model:
             exch, pi = read_subs_model(args.subs_model, mine)
-        if mine:
-            pis, out = pipeline.run_alignments(mine, leaf_names, parent, blen, leaf, T, args.times, args.intervals,
-                                               correction, args.threshold, exch, pi=pi, subsets=subset_pi,
-                                               output_dir=args.output, device=args.device, integ_mode=integ_mode,
-                                               round_decimals=-1 if args.full_precision_rates else 4,
-                                               engine_mod=engine_mod, progress=progress, pool=pool,
-                                               cat_rates=cat_rates, cat_weights=cat_weights,
-                                               start_rule=1 if args.reference_start else 0,
-                                               during_write=store if world == 1 else None,
-                                               table_sink=_TableSink() if world == 1 else None,
-                                               site_model=args.site_model, rate_estimator=args.rate_estimator,
-                                               eb_options=None if args.rate_estimator != 'eb' else dict(
-                                                   categories=args.eb_categories, alpha=args.eb_alpha,
-                                                   alpha_bounds=args.eb_alpha_bounds))
-            tables = out["final_tables"]
-            models = out.get("models")
-            ebfit = out.get("eb")
-            stored = bool(out.get("during_write_done"))
-            sqlite_seconds = LAST_TIMINGS.get("sqlite")
-            LAST_TIMINGS.clear()
-            LAST_TIMINGS.update(out.get("timings", {}))
-            if stored:
-                LAST_TIMINGS["sqlite"] = sqlite_seconds
-        else:
-            pis, tables, models, ebfit = [], np.zeros((0, W)), None, None
-    else:
-        models = ebfit = None
-        if rank == 0:
-            print("Estimating PI for files (--site-rate option):")
-        files = base.get_files(args.alignments, '*.rates')
-        mine = [files[i] for i in tdist.shard_loci(len(files), rank, world)]
-        if mine:
-            pis, tables = pipeline.run_rate_files(mine, leaf_names, parent, blen, leaf, T, args.times, args.intervals,
-                                                  correction, subsets=subset_pi, device=args.device, integ_mode=integ_mode,
-                                                  engine_mod=engine_mod, progress=progress, return_tables=True)
-        else:
-            pis, tables = [], np.zeros((0, W))
-    # the one collective: every rank's PI rows -> all rows in file order
-    all_tables = _gather_rows(tables, len(files), rank, world, on_gpu)
+        # single process: the database may be written while the pool writes the .rates files
+        pis, out = pipeline.run_alignments(mine, run, exch, pi=pi, subsets=subset_pi, output_dir=args.output, engine_mod=eng,
+                                           progress=progress, pool=pool,
+                                           during_write=probe_db.store if world == 1 else None,
+                                           table_sink=probe_db if world == 1 else None,
+                                           site_model=args.site_model, rate_estimator=args.rate_estimator,
+                                           eb_options=None if args.rate_estimator != 'eb' else dict(
+                                               categories=args.eb_categories, alpha=args.eb_alpha,
+                                               alpha_bounds=args.eb_alpha_bounds))
+        tables = out["final_tables"]
+        models = out.get("models")
+        ebfit = out.get("eb")
+        stored = bool(out.get("during_write_done"))
+        sqlite_seconds = LAST_TIMINGS.get("sqlite")
+        LAST_TIMINGS.clear()
+        LAST_TIMINGS.update(out.get("timings", {}))
+        if stored:
+            LAST_TIMINGS["sqlite"] = sqlite_seconds
+    cx = _Stage(args, rank, world, on_gpu, eng, run, files, mine, ids, [p[1] for p in pis], models, ebfit, subset_pi)
+    # the one collective of the main run: every rank's PI rows -> all rows in file order
+    all_tables = cx.gather(tables)
     if rank == 0:
         # store results somewhere
         sys.stdout.write("\nStoring results in {0}...".format(db_name))
         sys.stdout.flush()
-        if world == 1:
-            if not stored:
-                store(pis)
-        else:
-            import time
-            t_db = time.perf_counter()
-            conn, c = db.create_probe_db(db_name)
-            db.insert_tables(conn, c, files, all_tables, T, args.times, args.intervals)
-            conn.commit()
-            c.close()
-            conn.close()
-            LAST_TIMINGS["sqlite"] = time.perf_counter() - t_db
+        if world > 1:
+            probe_db.add(files, all_tables)
+            probe_db.close()
+        elif not stored:
+            probe_db.store(pis)
         sys.stdout.write("DONE")
         sys.stdout.flush()
         print("\n")
+    # (after the main database is stored: a failure of an opt-in stage leaves a finished run's outputs in place)
     if args.bootstrap:
-        # (after the main database is stored: a failure of this opt-in stage leaves a finished run's outputs in place)
-        # every rank resamples its own loci from their final rates; the generator's stream ids are the global file indices,
-        # so the bands do not depend on the world size.  The summaries travel like the PI rows.
-        eng = engine_mod
-        if eng is None:
-            from . import engine as eng
-        Wb = T + len(args.intervals)
-        ids = list(tdist.shard_loci(len(files), rank, world))
-        boot = pipeline.bootstrap_tables(eng, [p[1] for p in pis], leaf_names, parent, blen, leaf, T, args.intervals,
-                                         args.device, integ_mode, ids, args.bootstrap, args.bootstrap_seed, args.bootstrap_level)
-        all_boot = _gather_rows(boot.reshape(len(ids), 4 * Wb), len(files), rank, world, on_gpu)
-        if rank == 0:
-            db.write_bootstrap_db(os.path.join(args.output, 'phylogenetic-informativeness-bootstrap.sqlite'), files,
-                                  all_boot.reshape(len(files), 4, Wb), T, args.times, args.intervals, args.bootstrap,
-                                  args.bootstrap_seed, args.bootstrap_level)
+        _bootstrap_stage(cx)
     if args.parametric_bootstrap:
-        # (as the site bootstrap: after the main database, every rank on its own loci, stream ids = global file indices; the
-        # alignments are re-read: the main run does not keep them)
-        eng = engine_mod
-        if eng is None:
-            from . import engine as eng
-        Wb = T + len(args.intervals)
-        ids = list(tdist.shard_loci(len(files), rank, world))
-        pmodels = models if models is not None else dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)),
-                                                         model="gtr" if args.site_model == 'locus' else "f81")
-        pboot, _ = pipeline.parametric_bootstrap_tables(
-            eng, mine, [p[1] for p in pis], pmodels, leaf_names, parent, blen, leaf, T, args.intervals, correction, args.threshold,
-            -1 if args.full_precision_rates else 4, args.device, integ_mode, ids, args.parametric_bootstrap,
-            args.parametric_bootstrap_seed, args.parametric_bootstrap_level, subsets=subset_pi,
-            start_rule=1 if args.reference_start else 0, output_dir=args.output)
-        all_pboot = _gather_rows(pboot.reshape(len(ids), 4 * Wb), len(files), rank, world, on_gpu)
-        if rank == 0:
-            db.write_bootstrap_db(os.path.join(args.output, 'phylogenetic-informativeness-parametric-bootstrap.sqlite'), files,
-                                  all_pboot.reshape(len(files), 4, Wb), T, args.times, args.intervals, args.parametric_bootstrap,
-                                  args.parametric_bootstrap_seed, args.parametric_bootstrap_level, method="parametric")
+        _parametric_bootstrap_stage(cx)
     if args.posterior_pi:
-        # (as the parametric bootstrap: after the main database, every rank on its own loci with the fits of its own run, stream
-        # ids = global file indices, the alignments re-read; bands, categories and fits travel as one row per locus)
-        eng = engine_mod
-        if eng is None:
-            from . import engine as eng
-        Wb, K = T + len(args.intervals), args.eb_categories
-        ids = list(tdist.shard_loci(len(files), rank, world))
-        pmodels = models if models is not None else dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)),
-                                                         model="gtr" if args.site_model == 'locus' else "f81")
-        fit = ebfit if ebfit is not None else dict(alpha=np.zeros(0), scale=np.zeros(0), categories=K)
-        post = pipeline.posterior_pi_tables(
-            eng, mine, [p[1] for p in pis], pmodels, fit, leaf_names, parent, blen, leaf, T, args.intervals, correction,
-            args.threshold, -1 if args.full_precision_rates else 4, args.device, integ_mode, ids, args.posterior_pi,
-            args.posterior_pi_seed, args.posterior_pi_level, subsets=subset_pi)
-        packed = np.concatenate([post["bands"].reshape(len(ids), 4 * Wb), post["category_rate"].reshape(len(ids), K),
-                                 post["expected_sites"].reshape(len(ids), K),
-                                 np.asarray(fit["alpha"], dtype=np.float64).reshape(len(ids), 1),
-                                 np.asarray(fit["scale"], dtype=np.float64).reshape(len(ids), 1)], axis=1)
-        all_post = _gather_rows(packed, len(files), rank, world, on_gpu)
-        if rank == 0:
-            db.write_posterior_db(os.path.join(args.output, 'phylogenetic-informativeness-posterior.sqlite'), files,
-                                  all_post[:, :4 * Wb].reshape(len(files), 4, Wb), all_post[:, 4 * Wb:4 * Wb + K],
-                                  all_post[:, 4 * Wb + K:4 * Wb + 2 * K], all_post[:, 4 * Wb + 2 * K], all_post[:, 4 * Wb + 2 * K + 1],
-                                  T, args.times, args.intervals, args.posterior_pi, args.posterior_pi_seed, args.posterior_pi_level)
+        _posterior_pi_stage(cx)
     if args.quartets:
-        # (as the bootstrap: an opt-in stage after the main database, from every rank's final rates; rows travel like the PI rows)
-        eng = engine_mod
-        if eng is None:
-            from . import engine as eng
-        labels = [q[0] for q in args.quartets]
-        lengths = np.array([[q[1], q[2]] for q in args.quartets], dtype=np.float64)
-        ids = list(tdist.shard_loci(len(files), rank, world))
-        if args.site_rates:
-            models = _site_rates_models(mine, args)
-        elif models is None:
-            models = dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)), model="gtr" if args.site_model == 'locus' else "f81")
-        rows = pipeline.quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent, blen, leaf, T,
-                                       args.device, lengths, model=models["model"])
-        all_rows = _gather_rows(rows.reshape(len(ids), 8 * len(labels)), len(files), rank, world, on_gpu)
-        if args.exact_quartets:
-            exact = pipeline.exact_quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent, blen,
-                                                  leaf, T, args.device, lengths, model=models["model"],
-                                                  window_cap=args.exact_quartets_window)
-            all_exact = _gather_rows(exact.reshape(len(ids), 6 * len(labels)), len(files), rank, world, on_gpu)
-        if rank == 0:
-            name = os.path.join(args.output, 'phylogenetic-informativeness-quartets.sqlite')
-            db.write_quartet_db(name, files, all_rows.reshape(len(files), len(labels), 8), labels, lengths, models["model"])
-            if args.exact_quartets:
-                db.add_quartet_exact_table(name, all_exact.reshape(len(files), len(labels), 6), labels, args.exact_quartets_window)
+        _quartets_stage(cx)
     if args.unequal_quartets or args.tree_quartets:
-        # (as --quartets; the typed rows first, then the input tree's internodes, read in the tree's original units)
-        eng = engine_mod
-        if eng is None:
-            from . import engine as eng
-        typed = args.unequal_quartets or []
-        of_tree = compute.tree_quartets(newick.read_tree(args.tree, args.tree_format)) if args.tree_quartets else []
-        labels = [q[0] for q in typed] + [q[0] for q in of_tree]
-        lengths = np.array([q[1:6] for q in typed] + [q[2:7] for q in of_tree], dtype=np.float64).reshape(-1, 5)
-        ids = list(tdist.shard_loci(len(files), rank, world))
-        if args.site_rates:
-            models = _site_rates_models(mine, args)
-        elif models is None:
-            models = dict(pi=np.zeros((0, 4)), exch=np.zeros((0, 6)), model="gtr" if args.site_model == 'locus' else "f81")
-        rows = pipeline.unequal_quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent, blen,
-                                               leaf, T, args.device, lengths, model=models["model"])
-        # (a tree without an internode and nothing typed: no row to compute or gather, the file says so)
-        all_rows = (_gather_rows(rows.reshape(len(ids), 13 * len(labels)), len(files), rank, world, on_gpu) if labels
-                    else np.zeros((len(files), 0)))
-        if args.exact_quartets:
-            exact = pipeline.exact_unequal_quartet_tables(eng, [p[1] for p in pis], models["pi"], models["exch"], leaf_names, parent,
-                                                          blen, leaf, T, args.device, lengths, model=models["model"],
-                                                          window_cap=args.exact_quartets_window)
-            all_exact = (_gather_rows(exact.reshape(len(ids), 6 * len(labels)), len(files), rank, world, on_gpu) if labels
-                         else np.zeros((len(files), 0)))
-        if rank == 0:
-            name = os.path.join(args.output, 'phylogenetic-informativeness-unequal-quartets.sqlite')
-            db.write_unequal_quartet_db(name, files, all_rows.reshape(len(files), len(labels), 13), labels, lengths, models["model"],
-                                        clades=[(q[0], q[1]) for q in of_tree])
-            if args.exact_quartets:
-                db.add_quartet_exact_table(name, all_exact.reshape(len(files), len(labels), 6), labels, args.exact_quartets_window,
-                                           unequal=True)
+        _unequal_quartets_stage(cx)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
@@ -663,23 +569,83 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
     return args.output
 
 
-def _site_rates_models(rate_files, args):
-    """The loci's models for --quartets under --site-rates, which reads rates only: Jukes-Cantor, or the base frequencies the
-    `.rates` documents carry with exchangeabilities of 1 (f81) or the --exchangeabilities given."""
-    import json
-    L = len(rate_files)
-    if args.site_model == 'jc':
-        return dict(pi=np.full((L, 4), 0.25), exch=None, model="f81")
-    pi = np.empty((L, 4))
-    for l, f in enumerate(rate_files):
-        with open(f) as fh:
-            freqs = json.load(fh)["sites"].get("freqs")
-        if not freqs:
-            raise IOError("{0} carries no base frequencies (\"freqs\"): --quartets can only use --site-model jc with it".format(f))
-        pi[l] = [freqs[k] for k in "ACGT"]
-    if args.site_model == 'f81':
-        return dict(pi=pi, exch=None, model="f81")
-    return dict(pi=pi, exch=np.tile(np.array(args.exchangeabilities, dtype=np.float64), (L, 1)), model="gtr")
+def _bootstrap_stage(cx):
+    """--bootstrap: every rank resamples its own loci from their final rates; the summaries travel like the PI rows."""
+    args, run = cx.args, cx.run
+    boot = pipeline.bootstrap_tables(cx.eng, cx.per_locus, run, cx.ids, args.bootstrap, args.bootstrap_seed, args.bootstrap_level)
+    all_boot = cx.gather(boot)
+    if cx.rank == 0:
+        db.write_bootstrap_db(cx.path('phylogenetic-informativeness-bootstrap.sqlite'), cx.files, all_boot, run.T, run.times,
+                              run.intervals, args.bootstrap, args.bootstrap_seed, args.bootstrap_level)
+
+
+def _parametric_bootstrap_stage(cx):
+    """--parametric-bootstrap: as the site bootstrap; the alignments are re-read: the main run does not keep them."""
+    args, run = cx.args, cx.run
+    pboot, _ = pipeline.parametric_bootstrap_tables(
+        cx.eng, cx.mine, cx.per_locus, cx.stage_models(), run, cx.ids, args.parametric_bootstrap, args.parametric_bootstrap_seed,
+        args.parametric_bootstrap_level, subsets=cx.subsets, output_dir=args.output)
+    all_pboot = cx.gather(pboot)
+    if cx.rank == 0:
+        db.write_bootstrap_db(cx.path('phylogenetic-informativeness-parametric-bootstrap.sqlite'), cx.files, all_pboot, run.T,
+                              run.times, run.intervals, args.parametric_bootstrap, args.parametric_bootstrap_seed,
+                              args.parametric_bootstrap_level, method="parametric")
+
+
+def _posterior_pi_stage(cx):
+    """--posterior-pi: as the parametric bootstrap, with the fits of the rank's own run; bands, categories and fits travel as
+    one row per locus."""
+    args, run, n = cx.args, cx.run, len(cx.ids)
+    Wb, K = run.band_width, args.eb_categories
+    fit = cx.ebfit if cx.ebfit is not None else dict(alpha=np.zeros(0), scale=np.zeros(0), categories=K)
+    post = pipeline.posterior_pi_tables(cx.eng, cx.mine, cx.per_locus, cx.stage_models(), fit, run, cx.ids, args.posterior_pi,
+                                        args.posterior_pi_seed, args.posterior_pi_level, subsets=cx.subsets)
+    packed = np.concatenate([post["bands"].reshape(n, 4 * Wb), post["category_rate"].reshape(n, K),
+                             post["expected_sites"].reshape(n, K), np.asarray(fit["alpha"], dtype=np.float64).reshape(n, 1),
+                             np.asarray(fit["scale"], dtype=np.float64).reshape(n, 1)], axis=1)
+    all_post = cx.gather(packed)
+    if cx.rank == 0:
+        bands, cat_rate, sites, alpha, scale = np.split(all_post, [4 * Wb, 4 * Wb + K, 4 * Wb + 2 * K, 4 * Wb + 2 * K + 1], axis=1)
+        db.write_posterior_db(cx.path('phylogenetic-informativeness-posterior.sqlite'), cx.files,
+                              bands.reshape(len(cx.files), 4, Wb), cat_rate, sites, alpha[:, 0], scale[:, 0], run.T, run.times,
+                              run.intervals, args.posterior_pi, args.posterior_pi_seed, args.posterior_pi_level)
+
+
+def _quartets_stage(cx):
+    """--quartets (and their exact probabilities): from every rank's final rates; rows travel like the PI rows."""
+    args, models = cx.args, cx.stage_models()
+    labels = [q[0] for q in args.quartets]
+    lengths = np.array([[q[1], q[2]] for q in args.quartets], dtype=np.float64)
+    call = (cx.eng, cx.per_locus, models["pi"], models["exch"], cx.run, lengths)
+    all_rows = cx.gather(pipeline.quartet_tables(*call, model=models["model"]))
+    if args.exact_quartets:
+        all_exact = cx.gather(pipeline.exact_quartet_tables(*call, model=models["model"], window_cap=args.exact_quartets_window))
+    if cx.rank == 0:
+        name = cx.path('phylogenetic-informativeness-quartets.sqlite')
+        db.write_quartet_db(name, cx.files, all_rows, labels, lengths, models["model"])
+        if args.exact_quartets:
+            db.add_quartet_exact_table(name, all_exact, labels, args.exact_quartets_window)
+
+
+def _unequal_quartets_stage(cx):
+    """--unequal-quartets / --tree-quartets: as --quartets; the typed rows first, then the input tree's internodes, read in
+    the tree's original units."""
+    args, models = cx.args, cx.stage_models()
+    typed = args.unequal_quartets or []
+    of_tree = compute.tree_quartets(newick.read_tree(args.tree, args.tree_format)) if args.tree_quartets else []
+    labels = [q[0] for q in typed] + [q[0] for q in of_tree]
+    lengths = np.array([q[1:6] for q in typed] + [q[2:7] for q in of_tree], dtype=np.float64).reshape(-1, 5)
+    call = (cx.eng, cx.per_locus, models["pi"], models["exch"], cx.run, lengths)
+    all_rows = cx.gather(pipeline.unequal_quartet_tables(*call, model=models["model"]))
+    if args.exact_quartets:
+        all_exact = cx.gather(pipeline.exact_unequal_quartet_tables(*call, model=models["model"],
+                                                                    window_cap=args.exact_quartets_window))
+    if cx.rank == 0:
+        name = cx.path('phylogenetic-informativeness-unequal-quartets.sqlite')
+        db.write_unequal_quartet_db(name, cx.files, all_rows, labels, lengths, models["model"],
+                                    clades=[(q[0], q[1]) for q in of_tree])
+        if args.exact_quartets:
+            db.add_quartet_exact_table(name, all_exact, labels, args.exact_quartets_window, unequal=True)
 
 
 if __name__ == '__main__':

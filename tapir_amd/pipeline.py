@@ -8,6 +8,7 @@ batch (taxon-major state masks + CSR locus offsets), one call into the HIP engin
 tapir/compute.py:40-43) and worker()-shaped result tuples for tapir_amd.db.
 """
 import contextlib
+import dataclasses
 import os
 import sys
 
@@ -356,14 +357,16 @@ def model_averaged_exchangeabilities(eng, states, offsets, pi, ntaxa, parent, bl
     in_engine = hasattr(eng, "Plan") and hasattr(eng.Plan, "stage1_fit")
     if pi is None and not in_engine:
         pi = nexus.base_frequencies_from_histogram(eng.state_histogram(states, offsets, device=device))
+    def open_plan(off, blk_pi):
+        return eng.Plan(ntaxa, parent, blen, leaf, off, blk_pi, np.ones((len(blk_pi), 6)), T, times, intervals,
+                        correction=correction, device=device)
+
     for l0 in range(0, L, step):
         l1 = min(L, l0 + step)
         off = offsets[l0:l1 + 1] - offsets[l0]
         if in_engine:
             cols = states[:, offsets[l0]:offsets[l1]]          # a view: rows are `states.strides[0]` bytes apart
-            blk_pi = np.full((l1 - l0, 4), 0.25) if pi is None else pi[l0:l1]
-            plan = eng.Plan(ntaxa, parent, blen, leaf, off, blk_pi, np.ones((l1 - l0, 6)), T, times, intervals,
-                            correction=correction, device=device)
+            plan = open_plan(off, np.full((l1 - l0, 4), 0.25) if pi is None else pi[l0:l1])
             try:
                 res = plan.stage1_fit(cols, details=False, compress_patterns=True, empirical_pi=pi is None)
             finally:
@@ -373,8 +376,7 @@ def model_averaged_exchangeabilities(eng, states, offsets, pi, ntaxa, parent, bl
         # an engine without the call (the tests' CPU stand-in): site patterns, then the host optimiser of stage1.py
         sub = np.ascontiguousarray(states[:, offsets[l0]:offsets[l1]])
         pstates, poffsets, weights, _ = eng.compress_columns(sub, off, device=device, want_map=False)
-        plan = eng.Plan(ntaxa, parent, blen, leaf, poffsets, pi[l0:l1], np.ones((l1 - l0, 6)), T, times, intervals,
-                        correction=correction, device=device)
+        plan = open_plan(poffsets, pi[l0:l1])
         try:
             plan.set_column_weights(weights)
             out[l0:l1] = stage1.model_averaged_exchangeabilities(plan, pstates, pi[l0:l1], parent,
@@ -388,18 +390,145 @@ def model_averaged_exchangeabilities(eng, states, offsets, pi, ntaxa, parent, bl
 STREAM_BLOCK_LOCI = 8192   # loci per block of the streamed run (_run_streamed)
 
 
+@dataclasses.dataclass(frozen=True)
+class Run:
+    """What one run fixes for every locus and every stage: the tree (blen already scaled by `correction`), the PI schedule,
+    how raw rates become final rates, and what every plan of the run is opened with.  Nothing of the loci (offsets, models,
+    rates) is in here."""
+    leaf_names: list
+    parent: list
+    blen: list
+    leaf: list
+    T: int
+    times: list
+    intervals: list
+    correction: float = 1.0
+    threshold: int = 3
+    round_decimals: int = 4
+    integ_mode: int = 0
+    device: int = 0
+    start_rule: int = 0        # 1: every column starts at siteRate = 1 as in HyPhy (bf:1050) instead of at its parsimony rate
+    cat_rates: list = None     # the optional rate mixture (more than one category)
+    cat_weights: list = None
+
+    @property
+    def width(self):
+        """Columns of a PI row: the net profile, the times, then integral and error of every interval."""
+        return self.T + len(self.times) + 2 * len(self.intervals)
+
+    @property
+    def band_width(self):
+        """Columns of a band row (the replicate stages): the net profile and the interval integrals."""
+        return self.T + len(self.intervals)
+
+    def plan(self, eng, offsets, pi, exch, times=None, start_rule=True, mixture=False, **model):
+        """A plan with the run's correction, threshold and rounding (the main run and the stages that estimate rates again).
+        times: [] for the band stages; start_rule False: never passed; mixture: the main run alone carries it; model=: the
+        engine's own default applies where it is not given."""
+        kw = dict(correction=self.correction, threshold=self.threshold, round_decimals=self.round_decimals,
+                  integ_mode=self.integ_mode, device=self.device, **model)
+        if mixture and self.cat_rates is not None and len(self.cat_rates) > 1:
+            kw.update(cat_rates=self.cat_rates, cat_weights=self.cat_weights)
+        if start_rule and self.start_rule:
+            kw["start_rule"] = int(self.start_rule)
+        return eng.Plan(len(self.leaf_names), self.parent, self.blen, self.leaf, offsets, pi, exch, self.T,
+                        self.times if times is None else times, self.intervals, **kw)
+
+    @contextlib.contextmanager
+    def final_rates_plan(self, eng, per_locus, times=None, pi=None, exch=None, model=None):
+        """The plan for already-final per-locus rates (NaN = culled) -- no rounding, no correction, no cull -- with the
+        concatenated rates and the loci's offsets; closed on leaving.  The PI stages do not look at the models (model None:
+        placeholders, the run's intervals and integ_mode); the quartet stages pass the loci's pi / exch / model as
+        _locus_models returns them and have neither times nor intervals."""
+        offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
+        rates = np.concatenate(per_locus) if per_locus else np.zeros(0)
+        L = len(per_locus)
+        if model is None:
+            pi, exch, intervals, kw = np.full((L, 4), 0.25), np.ones((L, 6)), self.intervals, dict(integ_mode=self.integ_mode)
+            times = self.times if times is None else times
+        else:
+            times, intervals, kw = [], [], dict(model=model)
+        plan = eng.Plan(len(self.leaf_names), self.parent, self.blen, self.leaf, offsets, pi, exch, self.T, times, intervals,
+                        correction=1.0, threshold=0, round_decimals=-1, device=self.device, **kw)
+        try:
+            yield plan, rates, offsets
+        finally:
+            plan.close()
+
+    def corrected(self, rate):
+        """(rate rounded like HyPhy's JSON, that / correction): what tapir has after parse_site_rates."""
+        rate4 = compute.round_like_hyphy(rate, self.round_decimals) if self.round_decimals >= 0 else rate
+        return rate4, rate4 / self.correction
+
+    def final_rates(self, rate, nres):
+        """(rate4, corrected, culled): corrected() and the cull (bin/tapir_compute.py:100-102; NaN = culled)."""
+        rate4, corrected = self.corrected(rate)
+        return rate4, corrected, np.where(nres >= self.threshold, corrected, np.nan)
+
+    def tuples(self, names, per_locus, tables):
+        """worker()-shaped result tuples from the loci's final rates and PI rows."""
+        T, n_t, n_i = self.T, len(self.times), len(self.intervals)
+        out = []
+        for l, name in enumerate(names):
+            row = tables[l]
+            rates = per_locus[l]
+            fin = rates[~np.isnan(rates)]
+            mean_rate = float(fin.mean()) if fin.size else float("nan")  # bin/tapir_compute.py:110 (never stored)
+            pi_net = row[:T].copy()
+            pi_times = dict(zip(self.times, row[T:T + n_t]))
+            pi_epochs = {}
+            for k, (a, b) in enumerate(self.intervals):
+                pi_epochs["{0}-{1}".format(a, b)] = {"sum(integral)": row[T + n_t + k], "sum(error)": row[T + n_t + n_i + k]}
+            out.append((name, rates, mean_rate, None, pi_net, pi_times, pi_epochs))
+        return out
+
+
+class _RatesShare:
+    """The per-site arrays of the `.rates` files in one file the pool's workers map (they were forked before the arrays
+    existed): rows subst, rate4, lnl, corrected, and sd under empirical Bayes.  jobs() are _write_job's plain tuples."""
+
+    def __init__(self, total, eb):
+        import tempfile
+        self.total, self.eb = max(total, 1), eb
+        fd, self.path = tempfile.mkstemp(prefix="tapir_amd_", suffix=".f64", dir=_shared_dir(32 * self.total))
+        os.close(fd)
+        self.arr = None
+
+    def fill(self, a, b, subst, rate4, lnl, corrected, sd=None):
+        if self.arr is None:
+            self.arr = np.memmap(self.path, dtype=np.float64, mode="w+", shape=(5 if self.eb else 4, self.total))
+        self.arr[0, a:b], self.arr[1, a:b], self.arr[2, a:b], self.arr[3, a:b] = subst, rate4, lnl, corrected
+        if self.eb:
+            self.arr[4, a:b] = sd
+
+    def jobs(self, paths, offsets, l0, pi, exch, ebfit=None):
+        """One job per path: the loci l0, l0 + 1, ... of `offsets`, `pi`, `exch` and of the fits."""
+        jobs = [(p, self.path, self.total, int(offsets[l]), int(offsets[l + 1]), pi[l], exch[l])
+                for l, p in enumerate(paths, l0)]
+        if self.eb:
+            jobs = [job + (_eb_meta(ebfit, l),) for l, job in enumerate(jobs, l0)]
+        return jobs
+
+    def close(self):
+        self.arr = None
+        try:
+            os.unlink(self.path)
+        except OSError:
+            pass
+
+
 def _eb_meta(fit, l):
     return dict(alpha=fit["alpha"][l], scale=fit["scale"][l], categories=fit["categories"], locus_lnl=fit["locus_lnl"][l])
 
 
-def _eb_rates(plan, states, offsets, parent, blen, leaf, eb_options, tables=True):
+def _eb_rates(run, plan, states, eb_options, tables=True):
     """The empirical-Bayes estimator in the place of the site-rate launch (tapir_amd/eb.py): the per-column arrays run_fused
     returns (rate = posterior mean, lnl = log marginal likelihood, subst = rate x tree length, flag = 0) plus sd and the
     per-locus fit; the PI tables come from the same tphip_pi_tables call, fed with these rates."""
     from . import eb
     est = eb.estimate(plan, states, ncat=eb_options["categories"], alpha=eb_options.get("alpha"),
                       alpha_bounds=eb_options.get("alpha_bounds") or eb.ALPHA_BOUNDS)
-    length = float(np.asarray(blen, np.float64)[np.asarray(parent) >= 0].sum())
+    length = float(np.asarray(run.blen, np.float64)[np.asarray(run.parent) >= 0].sum())
     out = dict(rate=est["rate"], subst=est["rate"] * length, lnl=est["lnl"], flag=np.zeros(len(est["rate"]), np.uint8),
                nres=est["nres"], sd=est["sd"],
                eb=dict(alpha=est["alpha"], scale=est["scale"], locus_lnl=est["locus_lnl"], categories=est["categories"]))
@@ -426,8 +555,7 @@ def _fixed_model_pi(eng, site_model, states, offsets, device):
     return nexus.base_frequencies_from_histogram(eng.state_histogram(np.ascontiguousarray(states), offsets, device=device))
 
 
-def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                  pi, output_dir, device, integ_mode, round_decimals, extra, pool, progress, table_sink, timings, lap,
+def _run_streamed(eng, run, states, offsets, alignments, pi, output_dir, pool, progress, table_sink, timings, lap,
                   site_model="locus", eb_options=None):
     """The whole pipeline block by block, host and device working at the same time.
 
@@ -438,24 +566,18 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
     the 50 000 loci and the host ~8 s for their 12 GB of text and 5.4 M rows: one after the other that is the sum, here close
     to the larger.  Results are those of the unstreamed run (loci are independent; every array is filled at the same places).
     A fixed site model (site_model jc / f81) has no stage 1: each block's plan carries the model from the start."""
-    import tempfile
-    import time
     L = len(alignments)
     total = int(offsets[-1])
-    ntaxa = len(leaf_names)
-    W = T + len(times) + 2 * len(intervals)
     new = getattr(eng, "pinned_empty", None) or np.empty
     out = dict(rate=new(total, np.float64), subst=new(total, np.float64), lnl=new(total, np.float64), flag=new(total, np.uint8),
-               nres=new(total, np.int32), tables=new((L, W), np.float64))
-    nrow = 4
+               nres=new(total, np.int32), tables=new((L, run.width), np.float64))
     if eb_options is not None:   # the posterior sd is a fifth per-site array; the per-locus fits go into the .rates headers
-        nrow = 5
         out["sd"] = np.empty(total)
         out["eb"] = dict(alpha=np.empty(L), scale=np.empty(L), locus_lnl=np.empty(L), categories=int(eb_options["categories"]))
     exch_all, pi_all = np.empty((L, 6)), np.empty((L, 4))
     per_locus = [None] * L
-    fd, shared = tempfile.mkstemp(prefix="tapir_amd_", suffix=".f64", dir=_shared_dir(32 * max(total, 1)))
-    os.close(fd)
+    paths = [os.path.join(output_dir, os.path.basename(a) + ".rates") for a in alignments]
+    share = _RatesShare(total, eb_options is not None)
     pending = []
     sink_thread = None
     if table_sink is not None:
@@ -477,24 +599,18 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
         sink_thread = threading.Thread(target=drain, name="tapir_amd-sqlite")
         sink_thread.start()
     try:
-        arr = np.memmap(shared, dtype=np.float64, mode="w+", shape=(nrow, max(total, 1)))
         step = _block_sizes()[1]
         for l0 in range(0, L, step):
             l1 = min(L, l0 + step)
             a, b = int(offsets[l0]), int(offsets[l1])
-            cols = states[:, a:b]
+            cols, off = states[:, a:b], offsets[l0:l1 + 1] - a
             if site_model != "locus":
-                blk_pi = _fixed_model_pi(eng, site_model, cols, offsets[l0:l1 + 1] - a, device)
+                blk_pi, blk_exch, model = _fixed_model_pi(eng, site_model, cols, off, run.device), None, dict(model="f81")
                 lap("base_frequencies")
-                plan = eng.Plan(ntaxa, parent, blen, leaf, offsets[l0:l1 + 1] - a, blk_pi, None, T, times, intervals,
-                                correction=correction, threshold=threshold, round_decimals=round_decimals, integ_mode=integ_mode,
-                                device=device, model="f81", **extra)
                 exch_all[l0:l1], pi_all[l0:l1] = 1.0, blk_pi
             else:
-                blk_pi = np.full((l1 - l0, 4), 0.25) if pi is None else pi[l0:l1]
-                plan = eng.Plan(ntaxa, parent, blen, leaf, offsets[l0:l1 + 1] - a, blk_pi, np.ones((l1 - l0, 6)), T, times, intervals,
-                                correction=correction, threshold=threshold, round_decimals=round_decimals, integ_mode=integ_mode,
-                                device=device, **extra)
+                blk_pi, blk_exch, model = np.full((l1 - l0, 4), 0.25) if pi is None else pi[l0:l1], np.ones((l1 - l0, 6)), {}
+            plan = run.plan(eng, off, blk_pi, blk_exch, mixture=True, **model)
             try:
                 if site_model == "locus":
                     res = plan.stage1_fit(cols, details=False, compress_patterns=True, empirical_pi=pi is None)
@@ -502,7 +618,7 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
                     exch_all[l0:l1], pi_all[l0:l1] = res["exch"], res["pi"]
                     plan.set_models(exch=res["exch"])
                 if eb_options is not None:
-                    blk = _eb_rates(plan, np.ascontiguousarray(cols), offsets[l0:l1 + 1] - a, parent, blen, leaf, eb_options)
+                    blk = _eb_rates(run, plan, np.ascontiguousarray(cols), eb_options)
                     for k in ("rate", "subst", "lnl", "flag", "nres", "sd"):
                         out[k][a:b] = blk[k]
                     out["tables"][l0:l1] = blk["tables"]
@@ -514,27 +630,19 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
                     lap("site_rates_and_pi_incl_pcie")
             finally:
                 plan.close()
-            rate4 = compute.round_like_hyphy(out["rate"][a:b], round_decimals) if round_decimals >= 0 else out["rate"][a:b]
-            corrected = rate4 / correction
-            culled = np.where(out["nres"][a:b] >= threshold, corrected, np.nan)
+            rate4, corrected, culled = run.final_rates(out["rate"][a:b], out["nres"][a:b])
             for l in range(l0, l1):
                 per_locus[l] = culled[offsets[l] - a:offsets[l + 1] - a]
-            arr[0, a:b], arr[1, a:b], arr[2, a:b], arr[3, a:b] = out["subst"][a:b], rate4, out["lnl"][a:b], corrected
+            share.fill(a, b, out["subst"][a:b], rate4, out["lnl"][a:b], corrected, out["sd"][a:b] if "sd" in out else None)
             lap("round_correct_cull")
-            jobs = [(os.path.join(output_dir, os.path.basename(alignments[l]) + ".rates"), shared, max(total, 1), int(offsets[l]),
-                     int(offsets[l + 1]), pi_all[l], exch_all[l]) for l in range(l0, l1)]
-            if eb_options is not None:
-                arr[4, a:b] = out["sd"][a:b]
-                jobs = [job + (_eb_meta(out["eb"], l),) for job, l in zip(jobs, range(l0, l1))]
-            pending.append(pool.write_rates_async(jobs))
+            pending.append(pool.write_rates_async(share.jobs(paths[l0:l1], offsets, l0, pi_all, exch_all, out.get("eb"))))
             if sink_thread is not None:
                 q.put((alignments[l0:l1], out["tables"][l0:l1].copy()))
-        t_w = time.perf_counter()
         for res in pending:
             for _ in res.get():
                 if progress:
                     progress()
-        del arr
+        share.close()
         lap("write_rates_files")
         if sink_thread is not None:
             q.put(None)
@@ -547,23 +655,20 @@ def _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, le
         if sink_thread is not None and sink_thread.is_alive():
             q.put(None)
             sink_thread.join()
-        try:
-            os.unlink(shared)
-        except OSError:
-            pass
+        share.close()
     out["timings"] = timings
     out["final_tables"] = out["tables"]
     out["streamed_blocks"] = (L + step - 1) // step
     out["models"] = dict(pi=pi_all, exch=exch_all, model="gtr" if site_model == "locus" else "f81")
-    return _tuples(alignments, per_locus, out["tables"], T, times, intervals), out
+    return run.tuples(alignments, per_locus, out["tables"]), out
 
 
-def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                   exch, pi=None, subsets=None, output_dir=None, device=0, integ_mode=0, round_decimals=4,
-                   engine_mod=None, progress=None, pool=None, cat_rates=None, cat_weights=None, start_rule=0,
+def run_alignments(alignments, run, exch, pi=None, subsets=None, output_dir=None, engine_mod=None, progress=None, pool=None,
                    during_write=None, table_sink=None, site_model="locus", rate_estimator="ml", eb_options=None):
     """Site rates + PI for a list of NEXUS alignments.  Returns a list of worker()-shaped tuples
     (alignment, rates, mean_rate, None, pi_net, pi_times, pi_epochs) in the order of `alignments`.
+
+    run: the Run (tree, PI schedule, correction / threshold / rounding, device, integral mode, start rule, rate mixture).
 
     during_write: callable(tuples) the caller would run next on the returned tuples (the command line: the sqlite
     inserts).  When the pool's workers write the `.rates` files it runs on a second thread of this process meanwhile
@@ -589,7 +694,7 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
         eb_options.setdefault("categories", _eb.DEFAULT_CATEGORIES)
         if not _eb.MIN_CATEGORIES <= int(eb_options["categories"]) <= _eb.MAX_CATEGORIES:
             raise PipelineError("the empirical-Bayes prior takes 2..16 categories")
-        if cat_rates is not None and len(cat_rates) > 1:
+        if run.cat_rates is not None and len(run.cat_rates) > 1:
             raise PipelineError("the empirical-Bayes estimator has its own prior: it cannot run on top of the rate mixture")
     else:
         if eb_options is not None:
@@ -611,64 +716,51 @@ def run_alignments(alignments, leaf_names, parent, blen, leaf, T, times, interva
         t_mark[0] = now
 
     pinned = getattr(eng, "pinned_empty", None)   # the real engine: I/O arrays in pinned memory
-    states, offsets = load_alignments(alignments, leaf_names, pool, alloc=pinned)
+    states, offsets = load_alignments(alignments, run.leaf_names, pool, alloc=pinned)
     lap("parse_nexus")
     L = len(alignments)
-    extra = {} if cat_rates is None or len(cat_rates) <= 1 else dict(cat_rates=cat_rates, cat_weights=cat_weights)
-    if start_rule:   # every column starts at siteRate = 1 as in HyPhy (bf:1050) instead of at its parsimony rate
-        extra["start_rule"] = int(start_rule)
     need_subset = any(os.path.basename(a) in subsets for a in alignments)
     if ((exch is None or fixed) and pool is not None and hasattr(pool, "write_rates_async") and output_dir is not None and not need_subset and
             L > _block_sizes()[1] and hasattr(eng, "Plan") and hasattr(eng.Plan, "run_fused_into") and
             _shared_dir(32 * max(int(offsets[-1]), 1)) is not None and os.environ.get("TPHIP_NO_STREAM") is None):
         if pi is not None:
             pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
-        return _run_streamed(eng, states, offsets, alignments, leaf_names, parent, blen, leaf, T, times, intervals, correction,
-                             threshold, pi, output_dir, device, integ_mode, round_decimals, extra, pool, progress, table_sink,
-                             timings, lap, site_model=site_model, eb_options=eb_options)
+        return _run_streamed(eng, run, states, offsets, alignments, pi, output_dir, pool, progress, table_sink, timings, lap,
+                             site_model=site_model, eb_options=eb_options)
     if fixed:
-        pi = _fixed_model_pi(eng, site_model, states, offsets, device)
+        pi = _fixed_model_pi(eng, site_model, states, offsets, run.device)
         lap("base_frequencies")
-        out = _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                        round_decimals, integ_mode, device, extra, pi, None, need_subset, pinned, eb_options=eb_options, model="f81")
-        lap("site_rates_and_pi_incl_pcie")
-        exch = np.ones((L, 6))
-        tuples, out = _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction,
-                              threshold, round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool,
-                              progress, during_write, timings, lap)
-        out["models"] = dict(pi=np.asarray(pi, dtype=np.float64), exch=exch, model="f81")
-        return tuples, out
-    if pi is None and exch is not None:
-        hist = eng.state_histogram(states, offsets, device=device)
-        pi = nexus.base_frequencies_from_histogram(hist)
-    lap("base_frequencies")
-    if exch is None:   # HyPhy's stage 1; the empirical base frequencies (when none are given) come from the same upload
-        exch, pi = model_averaged_exchangeabilities(eng, states, offsets, pi, len(leaf_names), parent, blen, leaf, T, times,
-                                                    intervals, correction, device, return_pi=True)
-        lap("stage1_model_averaging")
-    pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
-    exch = np.asarray(exch, dtype=np.float64)
-    if exch.ndim == 1:
-        exch = np.tile(exch, (L, 1))
-    out = _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                    round_decimals, integ_mode, device, extra, pi, exch, need_subset, pinned, eb_options=eb_options)
+        plan_exch, exch, model = None, np.ones((L, 6)), dict(model="f81")
+    else:
+        if pi is None and exch is not None:
+            hist = eng.state_histogram(states, offsets, device=run.device)
+            pi = nexus.base_frequencies_from_histogram(hist)
+        lap("base_frequencies")
+        if exch is None:   # HyPhy's stage 1; the empirical base frequencies (when none are given) come from the same upload
+            exch, pi = model_averaged_exchangeabilities(eng, states, offsets, pi, len(run.leaf_names), run.parent, run.blen,
+                                                        run.leaf, run.T, run.times, run.intervals, run.correction, run.device,
+                                                        return_pi=True)
+            lap("stage1_model_averaging")
+        pi = np.asarray(pi, dtype=np.float64).reshape(L, 4)
+        exch = np.asarray(exch, dtype=np.float64)
+        if exch.ndim == 1:
+            exch = np.tile(exch, (L, 1))
+        plan_exch, model = exch, {}
+    out = _run_plan(eng, run, states, offsets, pi, plan_exch, need_subset, pinned, eb_options, **model)
     lap("site_rates_and_pi_incl_pcie")
-    tuples, out = _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-                          round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool, progress,
+    tuples, out = _finish(eng, run, out, alignments, offsets, pi, exch, subsets, need_subset, output_dir, pool, progress,
                           during_write, timings, lap)
-    out["models"] = dict(pi=pi, exch=exch, model="gtr")   # the loci's models, for stages that need them (quartet_tables)
+    # the loci's models, for stages that need them (quartet_tables)
+    out["models"] = dict(pi=np.asarray(pi, dtype=np.float64), exch=exch, model=model.get("model", "gtr"))
     return tuples, out
 
 
-def _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold, round_decimals,
-              integ_mode, device, extra, pi, exch, need_subset, pinned, eb_options=None, **model):
+def _run_plan(eng, run, states, offsets, pi, exch, need_subset, pinned, eb_options=None, **model):
     """One plan over the whole batch: per-site rates, and the PI tables unless a subset needs its own."""
-    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi, exch, T, times, intervals,
-                    correction=correction, threshold=threshold, round_decimals=round_decimals,
-                    integ_mode=integ_mode, device=device, **extra, **model)
+    plan = run.plan(eng, offsets, pi, exch, mixture=True, **model)
     try:
         if eb_options is not None:
-            return _eb_rates(plan, states, offsets, parent, blen, leaf, eb_options, tables=not need_subset)
+            return _eb_rates(run, plan, states, eb_options, tables=not need_subset)
         if need_subset:
             return plan.site_rates(states)
         return plan.run_fused(states, pinned=True) if pinned else plan.run_fused(states)
@@ -676,16 +768,12 @@ def _run_plan(eng, states, offsets, leaf_names, parent, blen, leaf, T, times, in
         plan.close()
 
 
-def _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, times, intervals, correction, threshold,
-            round_decimals, integ_mode, device, pi, exch, subsets, need_subset, output_dir, pool, progress, during_write,
+def _finish(eng, run, out, alignments, offsets, pi, exch, subsets, need_subset, output_dir, pool, progress, during_write,
             timings, lap):
     """Rounding, culling, the `.rates` files and the worker()-shaped tuples of run_alignments."""
     L = len(alignments)
     ebfit = out.get("eb")   # the per-locus fits of an empirical-Bayes run (None: maximum-likelihood rates)
-    # what tapir would have after parse_site_rates + cull (bin/tapir_compute.py:100-102)
-    rate4 = compute.round_like_hyphy(out["rate"], round_decimals) if round_decimals >= 0 else out["rate"]
-    corrected = rate4 / correction
-    culled = np.where(out["nres"] >= threshold, corrected, np.nan)
+    rate4, corrected, culled = run.final_rates(out["rate"], out["nres"])
     per_locus = []
     for l, a in enumerate(alignments):
         r = culled[offsets[l]:offsets[l + 1]]
@@ -697,99 +785,59 @@ def _finish(eng, out, alignments, offsets, leaf_names, parent, blen, leaf, T, ti
     if output_dir is not None:
         paths = [os.path.join(output_dir, os.path.basename(a) + ".rates") for a in alignments]
         if pool is not None and L > 1:
-            import tempfile
-            # the workers were forked before these arrays existed: hand them over through one shared file
             total = int(offsets[-1])
-            fd, shared = tempfile.mkstemp(prefix="tapir_amd_", suffix=".f64", dir=_shared_dir(32 * max(total, 1)))
-            os.close(fd)
+            share = _RatesShare(total, ebfit is not None)
             side = None
             try:
-                arr = np.memmap(shared, dtype=np.float64, mode="w+", shape=(4 if ebfit is None else 5, max(total, 1)))
-                arr[0, :total], arr[1, :total], arr[2, :total], arr[3, :total] = out["subst"], rate4, out["lnl"], corrected
-                if ebfit is not None:
-                    arr[4, :total] = out["sd"]
-                arr.flush()
-                jobs = [(paths[l], shared, max(total, 1), int(offsets[l]), int(offsets[l + 1]), pi[l], exch[l]) for l in range(L)]
-                if ebfit is not None:
-                    jobs = [job + (_eb_meta(ebfit, l),) for l, job in enumerate(jobs)]
+                share.fill(0, total, out["subst"], rate4, out["lnl"], corrected, out.get("sd"))
+                share.arr.flush()
+                jobs = share.jobs(paths, offsets, 0, pi, exch, ebfit)
                 if during_write is not None and not need_subset:
-                    side = _SideThread(during_write, lambda: _tuples(alignments, per_locus, out["tables"], T, times, intervals))
+                    side = _SideThread(during_write, lambda: run.tuples(alignments, per_locus, out["tables"]))
                 pool.write_rates(jobs, progress)
-                del arr
             finally:
-                os.unlink(shared)
+                share.close()
                 if side is not None:
                     timings["during_write"] = side.join()
                     out["during_write_done"] = True
         else:
             for l in range(L):
                 sl = slice(offsets[l], offsets[l + 1])
-                if ebfit is not None:
-                    _write_rates_file(paths[l], pi[l], exch[l], out["subst"][sl], rate4[sl], out["lnl"][sl], corrected[sl],
-                                      sd=out["sd"][sl], eb=_eb_meta(ebfit, l))
-                    if progress:
-                        progress()
-                    continue
-                _write_rates_file(paths[l], pi[l], exch[l], out["subst"][sl], rate4[sl], out["lnl"][sl], corrected[sl])
+                _write_rates_file(paths[l], pi[l], exch[l], out["subst"][sl], rate4[sl], out["lnl"][sl], corrected[sl],
+                                  sd=None if ebfit is None else out["sd"][sl], eb=None if ebfit is None else _eb_meta(ebfit, l))
                 if progress:
                     progress()
     elif progress:
         for _ in alignments:
             progress()
     lap("write_rates_files")
-    if need_subset:
-        tables = _tables_for_rates(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device, integ_mode)
-    else:
-        tables = out["tables"]
+    tables = _tables_for_rates(eng, run, per_locus) if need_subset else out["tables"]
     out["timings"] = timings
     out["final_tables"] = tables   # [L, W] rows as stored in sqlite (after any subset slicing)
     if out.get("during_write_done"):
         return side.arg, out
-    return _tuples(alignments, per_locus, tables, T, times, intervals), out
+    return run.tuples(alignments, per_locus, tables), out
 
 
-def run_rate_files(rate_files, leaf_names, parent, blen, leaf, T, times, intervals, correction, subsets=None,
-                   device=0, integ_mode=0, engine_mod=None, progress=None, return_tables=False):
+def run_rate_files(rate_files, run, subsets=None, engine_mod=None, progress=None, return_tables=False):
     """The --site-rates path (bin/tapir_compute.py:103-104, 153-158): re-read "rate" from each JSON, divide by
     the correction (again: the reference does not read `corrected_rates`), rewrite the file, NO culling."""
-    from . import compute
     eng = engine_mod
     if eng is None:
         from . import engine as eng
     subsets = subsets or {}
     per_locus = []
     for f in rate_files:
-        r = compute.parse_site_rates(f, correction=correction)
+        r = compute.parse_site_rates(f, correction=run.correction)
         base = os.path.basename(f)
         if base in subsets:
             r = r[subsets[base][0]:subsets[base][1]]
         per_locus.append(r)
         if progress:
             progress()
-    tables = _tables_for_rates(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device, integ_mode)
-    tuples = _tuples(rate_files, per_locus, tables, T, times, intervals)
+    tables = _tables_for_rates(eng, run, per_locus)
+    tuples = run.tuples(rate_files, per_locus, tables)
     return (tuples, tables) if return_tables else tuples
-
-
-@contextlib.contextmanager
-def _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device, integ_mode=None, pi=None,
-                      exch=None, model=None):
-    """The plan for already-final per-locus rates (NaN = culled) -- no rounding, no correction, no cull -- with the
-    concatenated rates and the loci's offsets; closed on leaving.  The PI stage does not look at the models (model None:
-    placeholders); the quartet stages pass the loci's pi / exch / model as _locus_models returns them."""
-    offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_locus])]).astype(np.int64)
-    rates = np.concatenate(per_locus) if per_locus else np.zeros(0)
-    L = len(per_locus)
-    kw = {} if integ_mode is None else dict(integ_mode=integ_mode)
-    if model is not None:
-        kw["model"] = model
-    plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, np.full((L, 4), 0.25) if model is None else pi,
-                    np.ones((L, 6)) if model is None else exch, T, times, intervals, correction=1.0, threshold=0,
-                    round_decimals=-1, device=device, **kw)
-    try:
-        yield plan, rates, offsets
-    finally:
-        plan.close()
 
 
 def _locus_models(L, pi, exch, model):
@@ -805,15 +853,13 @@ def _locus_models(L, pi, exch, model):
     return pi, exch
 
 
-def _tables_for_rates(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device, integ_mode):
+def _tables_for_rates(eng, run, per_locus):
     """PI tables for already-final rates (NaN = culled): tphip_pi_tables with no rounding/correction/cull."""
-    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, times, intervals, device,
-                           integ_mode) as (plan, rates, _):
+    with run.final_rates_plan(eng, per_locus) as (plan, rates, _):
         return plan.pi_tables(rates, None)
 
 
-def bootstrap_tables(eng, per_locus, leaf_names, parent, blen, leaf, T, intervals, device, integ_mode, locus_ids,
-                     replicates, seed=1, level=0.95):
+def bootstrap_tables(eng, per_locus, run, locus_ids, replicates, seed=1, level=0.95):
     """Site-bootstrap summaries [L, 4, T + n_i] (mean, sd, lo, hi of the net-PI profile and of the interval integrals) for
     already-final rates (NaN = culled), on a no-rounding plan exactly as _tables_for_rates: every path that ends in
     per-locus final rates (streamed or not, --subset-pi-map-file, --site-rates, --rate-estimator eb) is served without
@@ -821,50 +867,30 @@ def bootstrap_tables(eng, per_locus, leaf_names, parent, blen, leaf, T, interval
     a locus' bands do not depend on which rank, or which loci beside it, it was computed with.  The locus' model (and under
     eb the fitted prior) are held fixed: the bands are conditional on them."""
     if len(per_locus) == 0:
-        return np.zeros((0, 4, T + len(intervals)))
-    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], intervals, device,
-                           integ_mode) as (plan, rates, _):
+        return np.zeros((0, 4, run.band_width))
+    with run.final_rates_plan(eng, per_locus, times=[]) as (plan, rates, _):
         return plan.pi_bootstrap(rates, None, replicates=replicates, seed=seed, level=level,
                                  locus_ids=np.asarray(locus_ids, dtype=np.int64))
 
 
-PARBOOT_BLOCK_COLS = 1 << 24   # columns per plan of parametric_bootstrap_tables
-
-
-def parametric_bootstrap_tables(eng, alignments, per_locus, models, leaf_names, parent, blen, leaf, T, intervals, correction,
-                                threshold, round_decimals, device, integ_mode, locus_ids, replicates, seed=1, level=0.95,
-                                subsets=None, start_rule=0, output_dir=None):
-    """Parametric bootstrap of the site rates and the PI rows (DESIGN.md section 3.7): every column of every locus is
-    simulated `replicates` times down the tree under the locus' model at its own rate, with the observed pattern of missing
-    cells, its rate re-estimated and the PI row recomputed.  Returns the summaries [L, 4, T + n_i] (mean, sd, lo, hi) and,
-    per locus, the (mean, sd) of every site's final rate over the replicates (NaN for culled sites); with output_dir the
-    latter are also written as NAME.rates-bootstrap.json beside the `.rates` files.
-
-    alignments: the loci's NEXUS files, re-read here and sliced as run_alignments slices the rates for `subsets`
-    (--subset-pi-map-file).  per_locus: the run's final rates (rounded, / correction, NaN = culled); the raw rate of the
-    simulation is final rate x correction, so a culled column comes out all missing and is culled again.  models:
-    run_alignments' out["models"].  The plans carry the run's real correction, threshold and round_decimals.  The loci go
-    through in blocks of at most 2^24 columns; a column's bytes do not depend on the loci beside it, so the blocking changes
-    no bit.  locus_ids: the generator's stream ids -- the command line passes the global file indices.  The models and the
-    tree are held fixed (no stage-1 refit per replicate): the bands are conditional on the fitted substitution model."""
-    subsets = subsets or {}
-    L, Wb = len(alignments), T + len(intervals)
-    summary = np.zeros((L, 4, Wb))
-    moments = []
-    if L == 0:
-        return summary, moments
+def _band_models(models, L):
+    """run_alignments' out["models"] as (model, pi [L, 4], exch [L, 6] or None under "f81")."""
     model = models["model"]
     pi = np.asarray(models["pi"], dtype=np.float64).reshape(L, 4)
-    exch = None if model == "f81" else np.asarray(models["exch"], dtype=np.float64).reshape(L, 6)
-    ids = np.asarray(locus_ids, dtype=np.int64)
-    extra = dict(start_rule=int(start_rule)) if start_rule else {}
-    l0 = 0
+    return model, pi, None if model == "f81" else np.asarray(models["exch"], dtype=np.float64).reshape(L, 6)
+
+
+def _observed_blocks(run, alignments, per_locus, subsets, budget):
+    """The loci's observed columns in blocks of at most `budget` columns (one locus at least): yields (l0, l1, states, offsets)
+    with the alignments l0..l1 re-read, sliced as run_alignments slices the rates for `subsets`, and held against the
+    lengths of the final rates."""
+    L, l0 = len(alignments), 0
     while l0 < L:
         l1, cols = l0, 0
-        while l1 < L and (l1 == l0 or cols + len(per_locus[l1]) <= PARBOOT_BLOCK_COLS):
+        while l1 < L and (l1 == l0 or cols + len(per_locus[l1]) <= budget):
             cols += len(per_locus[l1])
             l1 += 1
-        states, off = load_alignments(alignments[l0:l1], leaf_names)
+        states, off = load_alignments(alignments[l0:l1], run.leaf_names)
         blocks = []
         for k, a in enumerate(alignments[l0:l1]):
             blk = states[:, off[k]:off[k + 1]]
@@ -874,12 +900,39 @@ def parametric_bootstrap_tables(eng, alignments, per_locus, models, leaf_names, 
             if blk.shape[1] != len(per_locus[l0 + k]):
                 raise PipelineError("{0}: {1} columns, but {2} final rates".format(base, blk.shape[1], len(per_locus[l0 + k])))
             blocks.append(blk)
-        states = np.ascontiguousarray(np.concatenate(blocks, axis=1))
-        offsets = np.concatenate([[0], np.cumsum([b.shape[1] for b in blocks])]).astype(np.int64)
-        raw = np.concatenate(per_locus[l0:l1]) * correction
-        plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi[l0:l1], None if exch is None else exch[l0:l1], T, [],
-                        intervals, correction=correction, threshold=threshold, round_decimals=round_decimals,
-                        integ_mode=integ_mode, device=device, model=model, **extra)
+        yield (l0, l1, np.ascontiguousarray(np.concatenate(blocks, axis=1)),
+               np.concatenate([[0], np.cumsum([b.shape[1] for b in blocks])]).astype(np.int64))
+        l0 = l1
+
+
+PARBOOT_BLOCK_COLS = 1 << 24   # columns per plan of parametric_bootstrap_tables
+
+
+def parametric_bootstrap_tables(eng, alignments, per_locus, models, run, locus_ids, replicates, seed=1, level=0.95, subsets=None,
+                                output_dir=None):
+    """Parametric bootstrap of the site rates and the PI rows (DESIGN.md section 3.7): every column of every locus is
+    simulated `replicates` times down the tree under the locus' model at its own rate, with the observed pattern of missing
+    cells, its rate re-estimated and the PI row recomputed.  Returns the summaries [L, 4, T + n_i] (mean, sd, lo, hi) and,
+    per locus, the (mean, sd) of every site's final rate over the replicates (NaN for culled sites); with output_dir the
+    latter are also written as NAME.rates-bootstrap.json beside the `.rates` files.
+
+    alignments: the loci's NEXUS files, re-read here and sliced as run_alignments slices the rates for `subsets`
+    (--subset-pi-map-file).  per_locus: the run's final rates (rounded, / correction, NaN = culled); the raw rate of the
+    simulation is final rate x correction, so a culled column comes out all missing and is culled again.  models:
+    run_alignments' out["models"].  The plans carry the run's real correction, threshold, round_decimals and start rule.  The
+    loci go through in blocks of at most 2^24 columns; a column's bytes do not depend on the loci beside it, so the blocking
+    changes no bit.  locus_ids: the generator's stream ids -- the command line passes the global file indices.  The models and
+    the tree are held fixed (no stage-1 refit per replicate): the bands are conditional on the fitted substitution model."""
+    L = len(alignments)
+    summary = np.zeros((L, 4, run.band_width))
+    moments = []
+    if L == 0:
+        return summary, moments
+    model, pi, exch = _band_models(models, L)
+    ids = np.asarray(locus_ids, dtype=np.int64)
+    for l0, l1, states, offsets in _observed_blocks(run, alignments, per_locus, subsets or {}, PARBOOT_BLOCK_COLS):
+        raw = np.concatenate(per_locus[l0:l1]) * run.correction
+        plan = run.plan(eng, offsets, pi[l0:l1], None if exch is None else exch[l0:l1], times=[], model=model)
         try:
             s, mean, sd = plan.pi_parametric_bootstrap(raw, states, replicates=replicates, seed=seed, level=level,
                                                        locus_ids=ids[l0:l1], return_rate_moments=True)
@@ -888,7 +941,6 @@ def parametric_bootstrap_tables(eng, alignments, per_locus, models, leaf_names, 
         summary[l0:l1] = s
         for k in range(l1 - l0):
             moments.append((mean[offsets[k]:offsets[k + 1]], sd[offsets[k]:offsets[k + 1]]))
-        l0 = l1
     if output_dir is not None:
         for a, (mean, sd) in zip(alignments, moments):
             _write_rate_moments_file(os.path.join(output_dir, os.path.basename(a) + ".rates-bootstrap.json"), mean, sd)
@@ -900,8 +952,7 @@ def parametric_bootstrap_tables(eng, alignments, per_locus, models, leaf_names, 
 POSTERIOR_PI_BYTES = 256 << 20
 
 
-def posterior_pi_tables(eng, alignments, per_locus, models, ebfit, leaf_names, parent, blen, leaf, T, intervals, correction,
-                        threshold, round_decimals, device, integ_mode, locus_ids, replicates, seed=1, level=0.95, subsets=None):
+def posterior_pi_tables(eng, alignments, per_locus, models, ebfit, run, locus_ids, replicates, seed=1, level=0.95, subsets=None):
     """The empirical-Bayes rate posterior carried into the PI rows, beside bootstrap_tables: per locus
     the analytic mean and sd of the net-PI profile and of the interval integrals under the posterior of the sites' rate
     categories, and the band [lo, hi] of `replicates` posterior draws.  Returns dict(bands [L, 4, T + n_i] = mean, sd, lo, hi;
@@ -915,40 +966,17 @@ def posterior_pi_tables(eng, alignments, per_locus, models, ebfit, leaf_names, p
     generator's stream ids -- the command line passes the global file indices.  Everything is conditional on the fitted
     (scale, alpha), the model and the tree: the bands carry the posterior of the sites' rates, not the uncertainty of the fit."""
     from . import eb
-    subsets = subsets or {}
-    L, Wb = len(alignments), T + len(intervals)
+    L = len(alignments)
     K = int(ebfit["categories"]) if L else 0
-    out = dict(bands=np.zeros((L, 4, Wb)), category_rate=np.zeros((L, K)), expected_sites=np.zeros((L, K)))
+    out = dict(bands=np.zeros((L, 4, run.band_width)), category_rate=np.zeros((L, K)), expected_sites=np.zeros((L, K)))
     if L == 0:
         return out
-    model = models["model"]
-    pi = np.asarray(models["pi"], dtype=np.float64).reshape(L, 4)
-    exch = None if model == "f81" else np.asarray(models["exch"], dtype=np.float64).reshape(L, 6)
+    model, pi, exch = _band_models(models, L)
     alpha = np.asarray(ebfit["alpha"], dtype=np.float64).reshape(L)
     scale = np.asarray(ebfit["scale"], dtype=np.float64).reshape(L)
     ids = np.asarray(locus_ids, dtype=np.int64)
-    block_cols = max(1, POSTERIOR_PI_BYTES // (8 * K))
-    l0 = 0
-    while l0 < L:
-        l1, cols = l0, 0
-        while l1 < L and (l1 == l0 or cols + len(per_locus[l1]) <= block_cols):
-            cols += len(per_locus[l1])
-            l1 += 1
-        states, off = load_alignments(alignments[l0:l1], leaf_names)
-        blocks = []
-        for k, a in enumerate(alignments[l0:l1]):
-            blk = states[:, off[k]:off[k + 1]]
-            base = os.path.basename(a)
-            if base in subsets:
-                blk = blk[:, subsets[base][0]:subsets[base][1]]
-            if blk.shape[1] != len(per_locus[l0 + k]):
-                raise PipelineError("{0}: {1} columns, but {2} final rates".format(base, blk.shape[1], len(per_locus[l0 + k])))
-            blocks.append(blk)
-        states = np.ascontiguousarray(np.concatenate(blocks, axis=1))
-        offsets = np.concatenate([[0], np.cumsum([b.shape[1] for b in blocks])]).astype(np.int64)
-        plan = eng.Plan(len(leaf_names), parent, blen, leaf, offsets, pi[l0:l1], None if exch is None else exch[l0:l1], T, [],
-                        intervals, correction=correction, threshold=threshold, round_decimals=round_decimals,
-                        integ_mode=integ_mode, device=device, model=model)
+    for l0, l1, states, offsets in _observed_blocks(run, alignments, per_locus, subsets or {}, max(1, POSTERIOR_PI_BYTES // (8 * K))):
+        plan = run.plan(eng, offsets, pi[l0:l1], None if exch is None else exch[l0:l1], times=[], start_rule=False, model=model)
         try:
             table = eb.posterior_table(plan, states, alpha[l0:l1], scale[l0:l1], ncat=K)
             res = eb.posterior_pi(plan, table, alpha[l0:l1], scale[l0:l1], replicates, seed=seed, level=level, locus_ids=ids[l0:l1])
@@ -958,9 +986,7 @@ def posterior_pi_tables(eng, alignments, per_locus, models, ebfit, leaf_names, p
         out["bands"][l0:l1, :2] = res["analytic"]
         out["bands"][l0:l1, 2:] = res["summary"][:, 2:]
         out["expected_sites"][l0:l1] = res["expected_counts"]
-        raw = (kappa * scale[l0:l1])[:, None] * eb.gamma_tables(alpha[l0:l1], K)[0]
-        out["category_rate"][l0:l1] = (compute.round_like_hyphy(raw, round_decimals) if round_decimals >= 0 else raw) / correction
-        l0 = l1
+        out["category_rate"][l0:l1] = run.corrected((kappa * scale[l0:l1])[:, None] * eb.gamma_tables(alpha[l0:l1], K)[0])[1]
     return out
 
 
@@ -972,7 +998,7 @@ def _write_rate_moments_file(path, mean, sd):
         json.dump({"mean": clean(mean), "sd": clean(sd)}, fh)
 
 
-def quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr"):
+def quartet_tables(eng, per_locus, pi, exch, run, quartets, model="gtr"):
     """Quartet signal and noise rows [L, n_q, 8] (Y, X, Yy, Xx, XY, p_correct, p_incorrect, p_polytomy; DESIGN.md section
     3.6) for already-final rates (NaN = culled), on a no-rounding plan exactly as bootstrap_tables: every path that ends in
     per-locus final rates is served without being touched.  Unlike the PI stage this one needs the loci's models: pi [L, 4]
@@ -985,12 +1011,11 @@ def quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, 
     if L == 0:
         return np.zeros((0, len(quartets), 8))
     pi, exch = _locus_models(L, pi, exch, model)
-    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], [], device, pi=pi, exch=exch,
-                           model=model) as (plan, rates, _):
+    with run.final_rates_plan(eng, per_locus, pi=pi, exch=exch, model=model) as (plan, rates, _):
         return plan.quartet_tables(rates, None, quartets)
 
 
-def unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr"):
+def unequal_quartet_tables(eng, per_locus, pi, exch, run, quartets, model="gtr"):
     """Rows [L, n_q, 13] of quartets with unequal tips (the sums of y, x1, x2, y^2, x1^2, x2^2, y x1, y x2, x1 x2, then
     p_correct, p_ac, p_ad, p_polytomy) for already-final rates, on a no-rounding plan exactly as
     quartet_tables.  quartets: [n_q, 5] rows (Ta, Tb, Tc, Td, t_o) in the tree's original time units; a list longer than
@@ -1001,8 +1026,7 @@ def unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, l
     if L == 0 or len(quartets) == 0:
         return np.zeros((L, len(quartets), 13))
     pi, exch = _locus_models(L, pi, exch, model)
-    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], [], device, pi=pi, exch=exch,
-                           model=model) as (plan, rates, _):
+    with run.final_rates_plan(eng, per_locus, pi=pi, exch=exch, model=model) as (plan, rates, _):
         return np.concatenate([plan.unequal_quartet_tables(rates, None, quartets[q0:q0 + 256])
                                for q0 in range(0, len(quartets), 256)], axis=1)
 
@@ -1022,13 +1046,12 @@ def exact_quartet_tile(L, ncols, n_q, planes, window_cap):
     return int(max(1, min(256, n_q, fit)))
 
 
-def _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model, window_cap, unequal):
-    L, n_q = len(per_locus), len(quartets)
+def _exact_quartet_tables(eng, per_locus, pi, exch, run, quartets, model, window_cap, unequal):
+    L, n_q, device = len(per_locus), len(quartets), run.device
     if L == 0 or n_q == 0:
         return np.zeros((L, n_q, 6))
     pi, exch = _locus_models(L, pi, exch, model)
-    with _final_rates_plan(eng, per_locus, leaf_names, parent, blen, leaf, T, [], [], device, pi=pi, exch=exch,
-                           model=model) as (plan, rates, offsets):
+    with run.final_rates_plan(eng, per_locus, pi=pi, exch=exch, model=model) as (plan, rates, offsets):
         ncols, planes = int(offsets[-1]), 3 if unequal else 2
         tile = exact_quartet_tile(L, ncols, n_q, planes, window_cap)
         stream = eng.device_stream(device)
@@ -1047,40 +1070,22 @@ def _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, le
         return out
 
 
-def exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr", window_cap=128):
+def exact_quartet_tables(eng, per_locus, pi, exch, run, quartets, model="gtr", window_cap=128):
     """Exact resolution probabilities beside quartet_tables: rows [L, n_q, 6] (p_correct, p_ac, p_ad, p_polytomy, window,
     tail_bound) from the same final rates on the same no-rounding plan.  Per tile of quartets
     (exact_quartet_tile) the per-site planes are written by quartet_sites_dev and read by quartet_exact_dev where they lie;
     only the rows leave the device.  With equal tips p_ac = p_ad up to rounding (one noise plane serves both).  A pair whose
     law does not fit window_cap has NaN probabilities and window 0.  A locus' rows depend on its rates, its model, the
     quartet and window_cap only."""
-    return _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device,
-                                 np.asarray(quartets, dtype=np.float64).reshape(-1, 2), model, window_cap, False)
+    return _exact_quartet_tables(eng, per_locus, pi, exch, run, np.asarray(quartets, dtype=np.float64).reshape(-1, 2), model,
+                                 window_cap, False)
 
 
-def exact_unequal_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device, quartets, model="gtr",
-                                 window_cap=128):
+def exact_unequal_quartet_tables(eng, per_locus, pi, exch, run, quartets, model="gtr", window_cap=128):
     """exact_quartet_tables for quartets [n_q, 5] (Ta, Tb, Tc, Td, t_o) beside unequal_quartet_tables; a list longer than the
     engine's 256 goes through in tiles like any other."""
-    return _exact_quartet_tables(eng, per_locus, pi, exch, leaf_names, parent, blen, leaf, T, device,
-                                 np.asarray(quartets, dtype=np.float64).reshape(-1, 5), model, window_cap, True)
-
-
-def _tuples(names, per_locus, tables, T, times, intervals):
-    n_t, n_i = len(times), len(intervals)
-    out = []
-    for l, name in enumerate(names):
-        row = tables[l]
-        rates = per_locus[l]
-        fin = rates[~np.isnan(rates)]
-        mean_rate = float(fin.mean()) if fin.size else float("nan")  # bin/tapir_compute.py:110 (never stored)
-        pi_net = row[:T].copy()
-        pi_times = dict(zip(times, row[T:T + n_t]))
-        pi_epochs = {}
-        for k, (a, b) in enumerate(intervals):
-            pi_epochs["{0}-{1}".format(a, b)] = {"sum(integral)": row[T + n_t + k], "sum(error)": row[T + n_t + n_i + k]}
-        out.append((name, rates, mean_rate, None, pi_net, pi_times, pi_epochs))
-    return out
+    return _exact_quartet_tables(eng, per_locus, pi, exch, run, np.asarray(quartets, dtype=np.float64).reshape(-1, 5), model,
+                                 window_cap, True)
 
 
 def dot_progress():

@@ -104,7 +104,7 @@ def test_bootstrap_tables_do_not_depend_on_the_shard():
     from tapir_amd import pipeline
     per_locus = _final_rates()
     t = TREE3
-    args = (t["leaf_names"], t["parent"], t["blen"], t["leaf"], 12, [[0, 5], [3, 12]], 0, 1)
+    args = (pipeline.Run(t["leaf_names"], t["parent"], t["blen"], t["leaf"], 12, [], [[0, 5], [3, 12]], device=0, integ_mode=1),)
     full = pipeline.bootstrap_tables(bootstrap_engine, per_locus, *args, locus_ids=np.arange(5), replicates=16, seed=3, level=0.9)
     assert full.shape == (5, 4, 14)
     for ids in ([0, 2, 4], [1, 3], [4]):

@@ -1,6 +1,7 @@
 """Empirical-Bayes site rates on the host side (no GPU): the reference (tests/eb_reference.py) against its 40-digit twin and
 hand-written formulas, the ctypes options struct against the C header, the command line, and the pipeline end to end with
 the CPU stand-in engine (tests/eb_engine.py: the two engine calls answered by the reference)."""
+import dataclasses
 import json
 import math
 import os
@@ -198,15 +199,16 @@ def test_rate_estimator_conflicts_are_argparse_errors(tmp_path, golden_dir, caps
 def test_pipeline_rejects_unknown_estimator(golden_dir):
     import eb_engine
     from tapir_amd import pipeline
-    args = ([os.path.join(golden_dir, "chr1_918.nex")], ["a"], [1, -1], [0.1, 0], [0, -1], 5, [1], [[0, 2]], 1.0, 3, np.ones(6))
+    args = ([os.path.join(golden_dir, "chr1_918.nex")], pipeline.Run(["a"], [1, -1], [0.1, 0], [0, -1], 5, [1], [[0, 2]], 1.0, 3), np.ones(6))
     with pytest.raises(pipeline.PipelineError):
         pipeline.run_alignments(*args, engine_mod=eb_engine, rate_estimator="x")
     with pytest.raises(pipeline.PipelineError):
         pipeline.run_alignments(*args, engine_mod=eb_engine, rate_estimator="ml", eb_options=dict(categories=4))
     with pytest.raises(pipeline.PipelineError):
         pipeline.run_alignments(*args, engine_mod=eb_engine, rate_estimator="eb", eb_options=dict(categories=40))
+    mixed = dataclasses.replace(args[1], cat_rates=[0.5, 1.5], cat_weights=[0.5, 0.5])
     with pytest.raises(pipeline.PipelineError):
-        pipeline.run_alignments(*args, engine_mod=eb_engine, rate_estimator="eb", cat_rates=[0.5, 1.5], cat_weights=[0.5, 0.5])
+        pipeline.run_alignments(args[0], mixed, args[2], engine_mod=eb_engine, rate_estimator="eb")
 
 
 def _read_outputs(outdir):

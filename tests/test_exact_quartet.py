@@ -150,7 +150,7 @@ def test_tiled_rows_equal_untiled_rows(monkeypatch):
     tree = ([3, 3, 4, 4, -1], [0.1, 0.1, 0.2, 0.1, 0.0], [0, 1, 2, -1, -1])
     q2 = np.array([[20.0, 5.0], [0.0, 3.0], [35.0, 1.0], [7.0, 7.0], [50.0, 0.5]])
     q5 = np.array([[20.0, 22.0, 25.0, 30.0, 5.0], [1.0, 0.0, 3.0, 40.0, 2.0], [9.0, 9.0, 9.0, 9.0, 4.0]])
-    args = (exact_quartet_engine, per_locus, pi, exch, ["a", "b", "c"]) + tree + (8, 0)
+    args = (exact_quartet_engine, per_locus, pi, exch, pipeline.Run(["a", "b", "c"], *tree, 8, [], [], device=0))
     whole = pipeline.exact_quartet_tables(*args, q2), pipeline.exact_unequal_quartet_tables(*args, q5)
     assert whole[0].shape == (4, 5, 6) and whole[1].shape == (4, 3, 6)
     del exact_quartet_engine.CALLS[:]
@@ -159,7 +159,7 @@ def test_tiled_rows_equal_untiled_rows(monkeypatch):
     assert [c[1] for c in exact_quartet_engine.CALLS] == [2, 2, 1, 2, 1]
     assert np.array_equal(whole[0], tiled[0]) and np.array_equal(whole[1], tiled[1])
     assert np.all(whole[0][:, :, 4] > 0) and np.all(np.abs(whole[0][:, :, :4].sum(axis=2) - 1) <= 1e-12)
-    assert pipeline.exact_quartet_tables(exact_quartet_engine, [], pi[:0], exch[:0], ["a", "b", "c"], *tree, 8, 0, q2).shape == (0, 5, 6)
+    assert pipeline.exact_quartet_tables(exact_quartet_engine, [], pi[:0], exch[:0], args[4], q2).shape == (0, 5, 6)
 
 
 # ---- the command line -----------------------------------------------------------------------------------------------

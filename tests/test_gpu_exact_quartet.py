@@ -134,8 +134,8 @@ def test_device_calls_chain_without_leaving_the_device():
     old = pipeline.EXACT_QUARTET_BYTES
     pipeline.EXACT_QUARTET_BYTES = 4 * 8 * 440
     try:
-        rows = pipeline.exact_unequal_quartet_tables(engine, per_locus, c["pi"], c["exch"], ["a", "b", "c", "d", "e"], PARENT, BLEN, LEAF,
-                                                     8, 0, U6)
+        rows = pipeline.exact_unequal_quartet_tables(engine, per_locus, c["pi"], c["exch"],
+                                                     pipeline.Run(["a", "b", "c", "d", "e"], PARENT, BLEN, LEAF, 8, [], [], device=0), U6)
     finally:
         pipeline.EXACT_QUARTET_BYTES = old
     assert np.array_equal(rows, host)

@@ -584,7 +584,7 @@ def test_cli_multiprocessing_flag_gives_identical_files(golden_dir, tmp_path, or
 
     with pipeline.HostPool(2) as pool:
         with pytest.raises(RuntimeError, match="disk full"):
-            pipeline.run_alignments(files, leaf_names, parent, blen, leaf, 100, [10], [(5, 15)], 1.0, 3,
+            pipeline.run_alignments(files, pipeline.Run(leaf_names, parent, blen, leaf, 100, [10], [(5, 15)], 1.0, 3),
                                     np.ones(6), output_dir=str(out), engine_mod=oracle_engine, pool=pool, during_write=fail)
     assert len(os.listdir(out)) == 6
     if os.path.isdir("/dev/shm"):
@@ -771,6 +771,51 @@ def test_stage1_blocks_of_loci_give_the_same_rates():
     a = pipeline.model_averaged_exchangeabilities(*args)
     b = pipeline.model_averaged_exchangeabilities(*args, block_loci=2)
     assert a.shape == (3, 6) and np.max(np.abs(a - b) / a) < 2e-5
+
+
+_RUN_FLAGS = ["--device", "3", "--integral-mode", "closed", "--reference-start", "--threshold", "2"]
+_MAIN_PLAN = dict(correction=100, device=3, integ_mode=1, round_decimals=4, start_rule=1, threshold=2)
+
+
+@pytest.mark.parametrize("engine, extra, plans", [
+    ("posterior_pi_engine", ["--rate-estimator", "eb", "--eb-categories", "4", "--eb-alpha", "0.8", "--posterior-pi", "16"],
+     [([10, 30], [[5, 15], [20, 40]], _MAIN_PLAN),
+      ([], [[5, 15], [20, 40]], dict(correction=100, device=3, integ_mode=1, model="gtr", round_decimals=4, threshold=2))]),
+    ("bootstrap_engine", ["--bootstrap", "8", "--full-precision-rates"],
+     [([10, 30], [[5, 15], [20, 40]], dict(_MAIN_PLAN, round_decimals=-1)),
+      ([], [[5, 15], [20, 40]], dict(correction=1.0, device=3, integ_mode=1, round_decimals=-1, threshold=0))]),
+    ("quartet_engine", ["--quartets", "3:2,10:5"],
+     [([10, 30], [[5, 15], [20, 40]], _MAIN_PLAN),
+      ([], [], dict(correction=1.0, device=3, model="gtr", round_decimals=-1, threshold=0))]),
+])
+def test_run_options_reach_every_plan(tmp_path, monkeypatch, engine, extra, plans):
+    """What a one-GPU box cannot see: the run's device, integral mode, start rule, threshold, correction and rounding reach
+    the plan of the main run and of the opt-in stage, each with exactly the keyword arguments it had before pipeline.Run
+    carried them (the expected lists are the recorded constructor calls of that code: a stage that does not pass an option
+    leaves it to the engine's default)."""
+    import importlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from tapir_amd import cli, synth
+    mod = importlib.import_module(engine)
+    seen = []
+
+    class Plan(mod.Plan):
+        def __init__(self, ntaxa, parent, blen, leaf, offsets, pi, exch, T, times, intervals, **kw):
+            seen.append((len(offsets) - 1, T, list(times), [list(i) for i in intervals], sorted(kw.items())))
+            super().__init__(ntaxa, parent, blen, leaf, offsets, pi, exch, T, times, intervals, **kw)
+
+    monkeypatch.setattr(mod, "Plan", Plan)
+    d = synth.simulate(3, 30, 5, 3)
+    aln = tmp_path / "aln"
+    aln.mkdir()
+    tree = synth.write_nexus_dir(str(aln), d["states"].numpy(), d["locus_offsets"], d["names"], d["root"])
+    shutil.move(tree, tmp_path / "tree.newick")
+    out = tmp_path / "out"
+    out.mkdir()
+    cli.main([str(aln), str(tmp_path / "tree.newick"), "--output", str(out), "--times", "10,30", "--intervals", "5-15,20-40",
+              "--exchangeabilities", "1,1.2,0.8,0.9,1.5,1"] + extra + _RUN_FLAGS, engine_mod=mod)
+    print(seen)
+    assert seen == [(3, 100, times, intervals, sorted(kw.items())) for times, intervals, kw in plans]
 
 
 def test_nexus_sequential_wrapping_and_matchchar(tmp_path):

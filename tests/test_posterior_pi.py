@@ -273,11 +273,14 @@ def test_posterior_tables_do_not_depend_on_the_shard_or_the_blocking(tmp_path, m
     models = dict(pi=np.full((4, 4), 0.25), exch=np.tile([1, 1.2, 0.8, 0.9, 1.5, 1], (4, 1)), model="gtr")
     fit = dict(alpha=np.array([0.8, 1.5, 0.5, 3.0]), scale=np.array([0.4, 0.6, 0.5, 0.3]), categories=4)
 
+    the_run = pipeline.Run(names, parent, blen, leaf, 12, [], [[0, 5], [3, 12]], correction=100.0, threshold=3, round_decimals=4,
+                           device=0, integ_mode=0)
+
     def run(idx):
         sub = dict(alpha=fit["alpha"][idx], scale=fit["scale"][idx], categories=4)
         m = dict(pi=models["pi"][idx], exch=models["exch"][idx], model="gtr")
-        return pipeline.posterior_pi_tables(posterior_pi_engine, [files[i] for i in idx], [per_locus[i] for i in idx], m, sub, names,
-                                            parent, blen, leaf, 12, [[0, 5], [3, 12]], 100.0, 3, 4, 0, 0, idx, 16, seed=3, level=0.9)
+        return pipeline.posterior_pi_tables(posterior_pi_engine, [files[i] for i in idx], [per_locus[i] for i in idx], m, sub, the_run,
+                                            idx, 16, seed=3, level=0.9)
 
     full = run([0, 1, 2, 3])
     assert full["bands"].shape == (4, 4, 14) and full["category_rate"].shape == (4, 4) and np.all(full["bands"][:, 1, 1:] > 0)
@@ -286,8 +289,7 @@ def test_posterior_tables_do_not_depend_on_the_shard_or_the_blocking(tmp_path, m
         part = run(idx)
         for k in full:
             assert np.array_equal(part[k], full[k][idx]), (idx, k)
-    empty = pipeline.posterior_pi_tables(posterior_pi_engine, [], [], models, dict(alpha=[], scale=[], categories=4), names, parent, blen,
-                                         leaf, 12, [[0, 5], [3, 12]], 100.0, 3, 4, 0, 0, [], 16)
+    empty = pipeline.posterior_pi_tables(posterior_pi_engine, [], [], models, dict(alpha=[], scale=[], categories=4), the_run, [], 16)
     assert empty["bands"].shape == (0, 4, 14)
 
 

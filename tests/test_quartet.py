@@ -174,7 +174,7 @@ def test_quartet_tables_do_not_depend_on_the_shard():
     exch = rng.uniform(0.5, 3, (5, 6))
     t = TREE3
     quartets = [(20.0, 5.0), (1.5, 0.25)]
-    args = (t["leaf_names"], t["parent"], t["blen"], t["leaf"], 12, 0, quartets)
+    args = (pipeline.Run(t["leaf_names"], t["parent"], t["blen"], t["leaf"], 12, [], [], device=0), quartets)
     full = pipeline.quartet_tables(quartet_engine, per_locus, pi, exch, *args)
     assert full.shape == (5, 2, 8)
     for ids in ([0, 2, 4], [1, 3], [4]):

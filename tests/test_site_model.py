@@ -162,8 +162,8 @@ def test_pipeline_rejects_model_with_exchangeabilities(golden_dir):
     import site_model_engine
     from tapir_amd import pipeline
     with pytest.raises(pipeline.PipelineError):
-        pipeline.run_alignments([os.path.join(golden_dir, "chr1_918.nex")], ["a"], [1, -1], [0.1, 0], [0, -1], 5, [1],
-                                [[0, 2]], 1.0, 3, np.ones(6), engine_mod=site_model_engine, site_model="jc")
+        pipeline.run_alignments([os.path.join(golden_dir, "chr1_918.nex")],
+                                pipeline.Run(["a"], [1, -1], [0.1, 0], [0, -1], 5, [1], [[0, 2]], 1.0, 3), np.ones(6), engine_mod=site_model_engine, site_model="jc")
     with pytest.raises(pipeline.PipelineError):
-        pipeline.run_alignments([os.path.join(golden_dir, "chr1_918.nex")], ["a"], [1, -1], [0.1, 0], [0, -1], 5, [1],
-                                [[0, 2]], 1.0, 3, None, engine_mod=site_model_engine, site_model="k80")
+        pipeline.run_alignments([os.path.join(golden_dir, "chr1_918.nex")],
+                                pipeline.Run(["a"], [1, -1], [0.1, 0], [0, -1], 5, [1], [[0, 2]], 1.0, 3), None, engine_mod=site_model_engine, site_model="k80")

@@ -277,7 +277,7 @@ def test_unequal_quartet_tables_do_not_depend_on_the_shard_or_on_the_list():
     exch = rng.uniform(0.5, 3, (5, 6))
     t = TREE3
     quartets = [(20.0, 25.0, 30.0, 35.0, 5.0), (100.0, 5.0, 100.0, 5.0, 2.0)]
-    args = (t["leaf_names"], t["parent"], t["blen"], t["leaf"], 12, 0)
+    args = (pipeline.Run(t["leaf_names"], t["parent"], t["blen"], t["leaf"], 12, [], [], device=0),)
     full = pipeline.unequal_quartet_tables(unequal_quartet_engine, per_locus, pi, exch, *args, quartets)
     assert full.shape == (5, 2, 13)
     for ids in ([0, 2, 4], [1, 3], [4]):

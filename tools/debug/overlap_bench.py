@@ -31,7 +31,7 @@ def store(pis):
 with pipeline.HostPool(int(sys.argv[2])) as pool:
     for mode in ("sequential", "overlapped"):
         t0 = time.perf_counter()
-        pis, out = pipeline.run_alignments(files, leaf_names, parent, blen, leaf, T, times, intervals, 1.0, 3, np.ones(6),
+        pis, out = pipeline.run_alignments(files, pipeline.Run(leaf_names, parent, blen, leaf, T, times, intervals, 1.0, 3), np.ones(6),
                                            output_dir=work + "/out", engine_mod=eng, pool=pool,
                                            during_write=store if mode == "overlapped" else None)
         t1 = time.perf_counter()
