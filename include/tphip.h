@@ -675,6 +675,69 @@ int tphip_quartet_exact(tphip_plan *plan, const double *y, const double *x1, con
                         const tphip_quartet_exact_opts *opts, double *rows);
 
 /* ------------------------------------------------------------------------------------------------
+ * Locus-set accumulation curves (an extension): how likely is a set of loci, analysed together, to resolve a quartet's
+ * internode, and how many of the best loci are needed?  For quartet q the order o_q[0..n_k) lists distinct locus indices; the
+ * set of size k is the concatenation of the columns of loci o_q[0] .. o_q[k-1].  Sites are independent, so the set's law is
+ * that of one long locus: the per-locus probabilities do not combine, but the moment sums add and the characteristic
+ * function is the product of the loci's.
+ *
+ * Normal rows (tphip_locus_set_rows): input the per-locus rows of tphip_quartet_tables ([nloci][n_q][8], family
+ * TPHIP_LOCUS_SET_EQUAL) or of tphip_unequal_quartet_tables ([nloci][n_q][13], TPHIP_LOCUS_SET_UNEQUAL).  Row (q, k) of
+ * rows [n_q][n_k][8 or 13], k = 1..n_k stored at index k - 1, has the layout of a per-locus row: its 5 or 9 sums are the
+ * left-to-right sums of the loci's own sums in the order given, its probabilities the family's own rule applied to them.
+ * The row k = 1 equals the per-locus row of locus o_q[0] bit for bit.
+ *
+ * Exact rows (tphip_locus_set_exact): input the per-site planes of tphip_quartet_exact.  All prefixes of a quartet share the
+ * torus M = window_cap; the centres and the three variances of prefix k are the left-to-right sums over the order of the
+ * loci's own six sums.  Prefix k is computed iff the tail bound of tphip_quartet_exact at M = window_cap is at most
+ * tail_tolerance for it and for every prefix before it, and k <= n_head; a variance term is >= 0, so the computed prefixes
+ * form a head k <= K_q.  Row (q, k) of rows [n_q][n_k][6]: p_correct, p_ac, p_ad, p_polytomy, window, tail_bound with the
+ * regions, weights and clamps of tphip_quartet_exact; window = window_cap and tail_bound the bound at the cap for a computed
+ * prefix.  A prefix that is not computed is never truncated: NaN in the four probabilities, window = 0, tail_bound the bound
+ * at the cap.  When all three variances are 0 the row is read off the centres.
+ *
+ * Determinism: row (q, k) depends only on the per-locus rows, or the planes, of the first k loci of o_q in that order, and
+ * (exact rows) on window_cap and tail_tolerance -- not on the loci after k, on n_k, on n_head as long as k <= n_head, on the
+ * other quartets or their orders, on the workspace or on the GPU count.  No floating-point atomics.
+ * Errors are TPHIP_ERR_INVALID throughout: a repeated or out-of-range index in `order` and a workspace below
+ * tphip_locus_set_exact_workspace_bytes() included; nloci * n_q is at most 2^24 per call. */
+#define TPHIP_LOCUS_SET_EQUAL 0
+#define TPHIP_LOCUS_SET_UNEQUAL 1
+typedef struct tphip_locus_set_opts {
+    uint32_t struct_size;      /* sizeof(tphip_locus_set_opts) of the caller */
+    int32_t n_q;               /* quartets, 1..256 */
+    int32_t n_k;               /* K: entries of a quartet's order, 1..nloci */
+    int32_t family;            /* TPHIP_LOCUS_SET_EQUAL or TPHIP_LOCUS_SET_UNEQUAL: the layout of the normal rows (the exact
+                                  call reads planes and ignores it) */
+    int32_t window_cap;        /* exact rows: M, a power of two in 16..512; 0 = 128 */
+    double tail_tolerance;     /* exact rows: in (0, 1); 0 = 1e-12 */
+    int32_t n_head;            /* exact rows: the most prefixes per quartet that are computed, 0 = n_k, else 1..n_k; it sizes
+                                  the workspace, and prefixes beyond it are reported as not computed */
+    const int32_t *order;     /* HOST [n_q][n_k] distinct locus indices per quartet; read and validated before the call
+                                  returns */
+} tphip_locus_set_opts;
+
+/* d_locus_rows [nloci][n_q][8 or 13], d_rows [n_q][n_k][8 or 13] on `device`.  Needs no plan.  Enqueues its kernels on
+ * `stream`; the order is copied to a buffer of the call's own, which is freed before the call returns (that waits for the
+ * kernels). */
+int tphip_locus_set_rows_dev(int32_t device, const double *d_locus_rows, int64_t nloci, const tphip_locus_set_opts *opts,
+                             double *d_rows, void *stream);
+/* host-pointer twin */
+int tphip_locus_set_rows(int32_t device, const double *locus_rows, int64_t nloci, const tphip_locus_set_opts *opts,
+                         double *rows);
+/* bytes of device workspace (8-byte aligned) tphip_locus_set_exact_dev needs for these options (`order` is not read) */
+int tphip_locus_set_exact_workspace_bytes(const tphip_plan *plan, const tphip_locus_set_opts *opts, size_t *bytes);
+/* d_rows [n_q][n_k][6].  The order is validated, then written into the workspace by launches that carry it as kernel arguments
+ * (960 indices each): the caller's array need not outlive the call.  Enqueues on `stream`, does not synchronise, copies nothing:
+ * it can be captured; the head of every quartet is found on the device. */
+int tphip_locus_set_exact_dev(tphip_plan *plan, const double *d_y, const double *d_x1, const double *d_x2,
+                              const tphip_locus_set_opts *opts, double *d_rows, void *d_workspace, size_t workspace_bytes,
+                              void *stream);
+/* host-pointer twin: the library allocates its own buffers; x1 == x2 is uploaded once */
+int tphip_locus_set_exact(tphip_plan *plan, const double *y, const double *x1, const double *x2,
+                          const tphip_locus_set_opts *opts, double *rows);
+
+/* ------------------------------------------------------------------------------------------------
  * Parametric bootstrap of the site rates and the PI rows (an extension).  The site bootstrap above resamples columns with
  * their rates held fixed; this one asks how noisy the rates themselves are: every column is simulated down the plan's tree
  * under the locus' model at the column's own rate, with the observed pattern of missing cells, its rate is re-estimated by

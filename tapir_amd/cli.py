@@ -12,6 +12,8 @@ and noise in another file of its own, phylogenetic-informativeness-quartets.sqli
 --unequal-quartets / --tree-quartets (the same for quartets with four tip lengths of their own, typed or read off the input
 tree's internodes, in phylogenetic-informativeness-unequal-quartets.sqlite), --exact-quartets / --exact-quartets-window (the
 exact resolution probabilities beside the normal approximation: a table quartet_exact in those quartet files),
+--locus-sets / --locus-sets-order / --locus-sets-max / --locus-sets-target (accumulation curves over an ordered list of loci:
+tables locus_set, locus_set_summary and, with --exact-quartets, locus_set_exact in those quartet files),
 --parametric-bootstrap / --parametric-bootstrap-seed / --parametric-bootstrap-level (the rates re-estimated on simulated
 alignments: bands in phylogenetic-informativeness-parametric-bootstrap.sqlite, per-site moments in NAME.rates-bootstrap.json),
 --posterior-pi / --posterior-pi-seed / --posterior-pi-level (with --rate-estimator eb: the posterior of the sites' rate
@@ -162,7 +164,23 @@ def get_args(argv=None):
                      help="largest window of --exact-quartets, a power of two in 16..512 (default 128: variances of the count "
                           "differences up to about 46); a locus and quartet that need a larger one get NULL probabilities "
                           "and window 0, never a truncated answer.  Needs --exact-quartets")
+    new.add_argument('--locus-sets', default=False, action='store_true',
+                     help="accumulation curves over an ordered list of loci: how likely the first k loci, analysed together, "
+                          "are to resolve each quartet, for every k (tables `locus_set` and `locus_set_summary` in each quartet "
+                          "database the run writes; with --exact-quartets also `locus_set_exact`, all prefixes on the window "
+                          "of --exact-quartets-window).  The default order is per quartet: descending per-locus p_correct of "
+                          "the normal approximation, ties by file order.  Needs --quartets, --unequal-quartets or --tree-quartets")
+    new.add_argument('--locus-sets-order', action=base.FullPaths, default=None, metavar='FILE',
+                     help="one locus name per line (a file's name without its extension): the order of --locus-sets, the same "
+                          "for every quartet; loci that are not named are left out.  Needs --locus-sets")
+    new.add_argument('--locus-sets-max', type=int, default=None, metavar='K',
+                     help="the largest set of --locus-sets: the order is cut to its first K loci (K >= 1; default all).  "
+                          "Needs --locus-sets")
+    new.add_argument('--locus-sets-target', type=float, default=None, metavar='P',
+                     help="the p_correct, in (0, 1), whose smallest sufficient k `locus_set_summary` reports (default 0.95).  "
+                          "Needs --locus-sets")
     args = parser.parse_args(argv)
+    _locus_set_flags(parser, args)
     if args.exact_quartets:
         if args.quartets is None and args.unequal_quartets is None and not args.tree_quartets:
             parser.error("--exact-quartets needs --quartets, --unequal-quartets or --tree-quartets")
@@ -224,6 +242,26 @@ def get_args(argv=None):
             parser.error("--posterior-pi must be in 2..4096")
     _seed_and_level(parser, args, '--posterior-pi')
     return args
+
+
+def _locus_set_flags(parser, args):
+    """--locus-sets and its three options: given without the stage they are an error, with it they get their defaults and
+    their ranges are held."""
+    options = (('--locus-sets-order', args.locus_sets_order), ('--locus-sets-max', args.locus_sets_max),
+               ('--locus-sets-target', args.locus_sets_target))
+    if not args.locus_sets:
+        for flag, value in options:
+            if value is not None:
+                parser.error("{0} needs --locus-sets".format(flag))
+        return
+    if args.quartets is None and args.unequal_quartets is None and not args.tree_quartets:
+        parser.error("--locus-sets needs --quartets, --unequal-quartets or --tree-quartets")
+    if args.locus_sets_max is not None and args.locus_sets_max < 1:
+        parser.error("--locus-sets-max must be at least 1")
+    if args.locus_sets_target is None:
+        args.locus_sets_target = 0.95
+    if not 0.0 < args.locus_sets_target < 1.0:
+        parser.error("--locus-sets-target must be in (0, 1)")
 
 
 def _seed_and_level(parser, args, flag):
@@ -625,6 +663,8 @@ def _quartets_stage(cx):
         db.write_quartet_db(name, cx.files, all_rows, labels, lengths, models["model"])
         if args.exact_quartets:
             db.add_quartet_exact_table(name, all_exact, labels, args.exact_quartets_window)
+    if args.locus_sets:
+        _locus_sets(cx, cx.path('phylogenetic-informativeness-quartets.sqlite'), all_rows, labels, lengths, models, False)
 
 
 def _unequal_quartets_stage(cx):
@@ -646,6 +686,50 @@ def _unequal_quartets_stage(cx):
                                     clades=[(q[0], q[1]) for q in of_tree])
         if args.exact_quartets:
             db.add_quartet_exact_table(name, all_exact, labels, args.exact_quartets_window, unequal=True)
+    if args.locus_sets:
+        _locus_sets(cx, cx.path('phylogenetic-informativeness-unequal-quartets.sqlite'), all_rows, labels, lengths, models, True)
+
+
+def _gather_objects(obj, rank, world):
+    """Every rank's picklable object -> the list of them on rank 0 (None elsewhere)."""
+    if world == 1:
+        return [obj]
+    import torch.distributed as dist
+    box = [None] * world if rank == 0 else None
+    dist.gather_object(obj, box, dst=0)
+    return box
+
+
+def _locus_sets(cx, name, all_rows, labels, lengths, models, unequal):
+    """--locus-sets, after a quartet stage has written `name`: the order from the gathered per-locus rows (every rank has them and
+    finds the same order), the normal rows on rank 0, and with --exact-quartets the exact rows on rank 0 too, from the final
+    rates and models of the loci the orders name, which travel there from the ranks that own them -- the sub-batch is the
+    same whatever the world size, so the rows are the same bits."""
+    args = cx.args
+    if len(cx.files) == 0 or len(labels) == 0:
+        return
+    order = pipeline.locus_set_order(all_rows, [db.locus_name(f) for f in cx.files], args.locus_sets_order, args.locus_sets_max)
+    exact = None
+    if args.exact_quartets:
+        union = np.unique(order)
+        wanted = set(union.tolist())
+        pi, exch = models["pi"], models["exch"]
+        mine = {int(g): (cx.per_locus[l], np.asarray(pi[l], dtype=np.float64), None if exch is None else np.asarray(exch[l], dtype=np.float64))
+                for l, g in enumerate(cx.ids) if int(g) in wanted}
+        parts = _gather_objects(mine, cx.rank, cx.world)
+        if cx.rank == 0:
+            have = {g: v for part in parts for g, v in part.items()}
+            chosen = [have[int(g)] for g in union]
+            exact = pipeline.exact_locus_set_tables(
+                cx.eng, [v[0] for v in chosen], np.array([v[1] for v in chosen]),
+                None if models["model"] != "gtr" else np.array([v[2] for v in chosen]), cx.run, lengths,
+                np.searchsorted(union, order), model=models["model"], window_cap=args.exact_quartets_window, unequal=unequal)
+    if cx.rank == 0:
+        rows = pipeline.locus_set_tables(cx.eng, all_rows, order, cx.run.device)
+        db.add_locus_set_tables(name, rows, order, labels, args.locus_sets_target,
+                                "p_correct" if args.locus_sets_order is None else "file:" + os.path.basename(args.locus_sets_order),
+                                args.locus_sets_max, unequal=unequal, exact=exact,
+                                window_cap=args.exact_quartets_window if args.exact_quartets else None)
 
 
 if __name__ == '__main__':

@@ -301,3 +301,69 @@ def write_unequal_quartet_db(db_name, names, rows, labels, quartets, model, clad
     conn.commit()
     c.close()
     conn.close()
+
+
+LOCUS_SET_SUMS = {False: ("Y", "X", "Yy", "Xx", "XY"), True: ("Y", "X1", "X2", "Yy", "X1x1", "X2x2", "YX1", "YX2", "X1X2")}
+
+
+def add_locus_set_tables(db_name, rows, order, labels, target, order_rule, max_k, unequal=False, exact=None, window_cap=None):
+    """--locus-sets: the accumulation curves over an ordered list of loci, added to a quartet database
+    that write_quartet_db or write_unequal_quartet_db (unequal=True) has just written.  rows [n_q, K, 8 or 13] from
+    pipeline.locus_set_tables and order [n_q, K] (indices into the file's loci, in file order) -> the table locus_set: per
+    quartet and k the locus added at step k (`id`), the sums of the set of the first k loci and its normal-approximation
+    probabilities.  locus_set_summary: per quartet the target, the smallest k whose p_correct reaches it (NULL if none does)
+    and p_correct of the whole list.  exact [n_q, K, 6] from pipeline.exact_locus_set_tables (--exact-quartets) -> the table
+    locus_set_exact (a prefix that was not computed has NULL probabilities and window 0) and the column k_needed_exact, NULL
+    when no computed prefix reaches the target.  meta: the order rule, the maximum, the target and the cap."""
+    import numpy as np
+    conn = sqlite3.connect(db_name)
+    c = conn.cursor()
+    sums = LOCUS_SET_SUMS[bool(unequal)]
+    width = len(sums) + (4 if unequal else 3)
+    wrong = "p_ac FLOAT, p_ad FLOAT" if unequal else "p_incorrect FLOAT"
+    c.execute("CREATE TABLE locus_set (quartet TEXT, k INT, id INT, " + ", ".join(s + " FLOAT" for s in sums) + ", p_correct FLOAT, "
+              + wrong + ", p_polytomy FLOAT, FOREIGN KEY(id) REFERENCES loci(id))")
+    c.execute("CREATE TABLE locus_set_summary (quartet TEXT, target FLOAT, k_needed INT, p_correct_all FLOAT"
+              + (", k_needed_exact INT" if exact is not None else "") + ")")
+    keys = [r[0] for r in c.execute("SELECT id FROM loci ORDER BY id").fetchall()]
+    order = np.asarray(order, dtype=np.int64)
+    n_q, K = len(labels), order.shape[1] if order.ndim == 2 else 0
+    rows = np.asarray(rows, dtype=np.float64).reshape(n_q, K, width)
+    p_col = len(sums)
+
+    def first_reaching(p):   # the smallest k (from 1) with p >= target; NaN never is
+        hit = np.flatnonzero(p >= target)
+        return int(hit[0]) + 1 if hit.size else None
+
+    out, summary = [], []
+    for q in range(n_q):
+        for k in range(K):
+            out.append((labels[q], k + 1, keys[int(order[q, k])]) + tuple(rows[q, k].tolist()))
+        row = (labels[q], float(target), first_reaching(rows[q, :, p_col]), float(rows[q, K - 1, p_col]) if K else None)
+        if exact is not None:
+            with np.errstate(invalid="ignore"):
+                row += (first_reaching(np.asarray(exact, dtype=np.float64).reshape(n_q, K, 6)[q, :, 0]),)
+        summary.append(row)
+    c.executemany("INSERT INTO locus_set VALUES (" + ",".join("?" * (3 + width)) + ")", out)
+    c.executemany("INSERT INTO locus_set_summary VALUES (" + ",".join("?" * (5 if exact is not None else 4)) + ")", summary)
+    meta = [("locus_sets_order", str(order_rule)), ("locus_sets_max", "all" if max_k is None else str(int(max_k))),
+            ("locus_sets_target", repr(float(target)))]
+    if exact is not None:
+        exact = np.asarray(exact, dtype=np.float64).reshape(n_q, K, 6)
+        c.execute("CREATE TABLE locus_set_exact (quartet TEXT, k INT, p_correct FLOAT, " + wrong + ", p_polytomy FLOAT, window INT, "
+                  "tail_bound FLOAT)")
+        out = []
+        for q in range(n_q):
+            for k in range(K):
+                pc, p1, p2, rest, window, bound = exact[q, k].tolist()
+                if window == 0:
+                    probs = (None,) * (4 if unequal else 3)
+                else:
+                    probs = (pc, p1, p2, rest) if unequal else (pc, p1 + p2, rest)
+                out.append((labels[q], k + 1) + probs + (int(window), bound))
+        c.executemany("INSERT INTO locus_set_exact VALUES (" + ",".join("?" * (8 if unequal else 7)) + ")", out)
+        meta.append(("locus_sets_window_cap", str(int(window_cap))))
+    c.executemany("INSERT INTO meta VALUES (?,?)", meta)
+    conn.commit()
+    c.close()
+    conn.close()

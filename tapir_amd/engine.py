@@ -72,6 +72,11 @@ class QuartetExactOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("window_cap", _i32), ("tail_tolerance", _f64)]
 
 
+class LocusSetOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_q", _i32), ("n_k", _i32), ("family", _i32), ("window_cap", _i32),
+                ("tail_tolerance", _f64), ("n_head", _i32), ("order", _vp)]
+
+
 class SimulateOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("replicate", _i32), ("seed", ctypes.c_uint64), ("locus_ids", _vp)]
 
@@ -162,6 +167,11 @@ SYMBOLS = [
     ("tphip_quartet_exact_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(QuartetExactOpts), ctypes.POINTER(ctypes.c_size_t)]),
     ("tphip_quartet_exact_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(QuartetExactOpts), _vp, _vp, ctypes.c_size_t, _vp]),
     ("tphip_quartet_exact", ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(QuartetExactOpts), _vp]),
+    ("tphip_locus_set_rows_dev", ctypes.c_int, [_i32, _vp, _i64, ctypes.POINTER(LocusSetOpts), _vp, _vp]),
+    ("tphip_locus_set_rows", ctypes.c_int, [_i32, _vp, _i64, ctypes.POINTER(LocusSetOpts), _vp]),
+    ("tphip_locus_set_exact_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(LocusSetOpts), ctypes.POINTER(ctypes.c_size_t)]),
+    ("tphip_locus_set_exact_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(LocusSetOpts), _vp, _vp, ctypes.c_size_t, _vp]),
+    ("tphip_locus_set_exact", ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(LocusSetOpts), _vp]),
     ("tphip_simulate_columns_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp, _vp]),
     ("tphip_simulate_columns", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(SimulateOpts), _vp]),
     ("tphip_parboot_workspace_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ParbootOpts), ctypes.POINTER(ctypes.c_size_t)]),
@@ -931,6 +941,38 @@ class Plan:
         _check(self._lib.tphip_quartet_exact_dev(self._h, _ptr(d_y), _ptr(d_x1), _ptr(d_x2), ctypes.byref(opts), _ptr(d_rows),
                                                  _ptr(d_ws), _nbytes(d_ws), stream))
 
+    # ---- locus-set accumulation curves, exact rows (csrc/locus_set_driver.hip) ---------------------
+    def locus_set_exact_workspace_bytes(self, n_q, n_k, window_cap=128, n_head=0):
+        """bytes of device workspace for locus_set_exact_dev with n_q quartets, orders of n_k loci, this cap and n_head."""
+        opts, _ = _locus_set_opts(np.zeros((int(n_q), int(n_k)), np.int32), window_cap=window_cap, n_head=n_head)
+        return _size_out(self._lib.tphip_locus_set_exact_workspace_bytes, self._h, ctypes.byref(opts))
+
+    def locus_set_exact(self, y, x1, x2, order, window_cap=128, tail_tolerance=0.0, n_head=0):
+        """The exact law of the quartet counts of the sets of loci order[q, :k], k = 1..K, analysed together
+        (tphip_locus_set_exact): y, x1, x2 [n_q, ncols] as for quartet_exact, order int [n_q, K] distinct locus indices per
+        quartet.  Returns rows [n_q, K, 6]: p_correct, p_ac, p_ad, p_polytomy, window, tail_bound, all on the torus
+        M = window_cap; a prefix whose law does not fit it within tail_tolerance (0: 1e-12), or beyond n_head (0: K), has NaN
+        in the four probabilities and window 0."""
+        same = x2 is x1
+        y, x1 = _np(y, np.float64), _np(x1, np.float64)
+        x2 = x1 if same else _np(x2, np.float64)
+        if y.ndim != 2 or y.shape[1] != self.ncols or x1.shape != y.shape or x2.shape != y.shape:
+            raise TphipError("y, x1 and x2 must be [n_q, ncols] planes of one shape")
+        opts, order = _locus_set_opts(order, window_cap=window_cap, tail_tolerance=tail_tolerance, n_head=n_head)
+        if order.shape[0] != y.shape[0]:
+            raise TphipError("order must have one row per quartet of the planes")
+        rows = np.zeros(order.shape + (6,))
+        _check(self._lib.tphip_locus_set_exact(self._h, y.ctypes.data, x1.ctypes.data, x2.ctypes.data, ctypes.byref(opts),
+                                               rows.ctypes.data))
+        return rows
+
+    def locus_set_exact_dev(self, d_y, d_x1, d_x2, order, d_rows, d_ws, window_cap=128, tail_tolerance=0.0, n_head=0, stream=0):
+        """tphip_locus_set_exact_dev on device tensors: d_y, d_x1, d_x2 [n_q, ncols] (views of a *_sites_dev buffer), order a
+        host array [n_q, K], d_rows [n_q, K, 6]; enqueues, does not synchronise (the order travels as kernel arguments)."""
+        opts, order = _locus_set_opts(order, window_cap=window_cap, tail_tolerance=tail_tolerance, n_head=n_head)
+        _check(self._lib.tphip_locus_set_exact_dev(self._h, _ptr(d_y), _ptr(d_x1), _ptr(d_x2), ctypes.byref(opts), _ptr(d_rows),
+                                                   _ptr(d_ws), _nbytes(d_ws), stream))
+
     # ---- parametric bootstrap of site rates and PI rows (csrc/simulate_driver.hip) ---------------
     def _ids(self, locus_ids):
         if locus_ids is None:
@@ -1066,6 +1108,42 @@ def summarize_rows(rows, level=0.95, device=0):
     summary = np.zeros((L, 4, Wb))
     _check(load().tphip_summarize_rows(device, rows.ctypes.data, L, B, Wb, float(level), summary.ctypes.data))
     return summary
+
+
+LOCUS_SET_EQUAL, LOCUS_SET_UNEQUAL = 0, 1
+
+
+def _locus_set_opts(order, family=LOCUS_SET_EQUAL, window_cap=128, tail_tolerance=0.0, n_head=0):
+    """order: int [n_q, K].  Returns the options and the array they point into (keep it alive)."""
+    order = _np(order, np.int32)
+    if order.ndim != 2:
+        raise TphipError("order must be [n_q, K]")
+    opts = LocusSetOpts(struct_size=ctypes.sizeof(LocusSetOpts), n_q=order.shape[0], n_k=order.shape[1], family=int(family),
+                        window_cap=int(window_cap), tail_tolerance=float(tail_tolerance), n_head=int(n_head), order=order.ctypes.data)
+    return opts, order
+
+
+def locus_set_rows(locus_rows, order, device=0):
+    """The normal-approximation rows of the sets of loci order[q, :k], k = 1..K (tphip_locus_set_rows): locus_rows [L, n_q, 8]
+    as quartet_tables returns them or [L, n_q, 13] as unequal_quartet_tables does, order int [n_q, K] distinct locus indices
+    per quartet.  Returns [n_q, K, 8 or 13] in the per-locus layout: the sums added left to right in the order given, the
+    probabilities by the family's own rule; row k = 1 is the per-locus row of locus order[q, 0] bit for bit."""
+    locus_rows = _np(locus_rows, np.float64)
+    if locus_rows.ndim != 3 or locus_rows.shape[2] not in (8, 13):
+        raise TphipError("locus_rows must be [L, n_q, 8] or [L, n_q, 13]")
+    opts, order = _locus_set_opts(order, LOCUS_SET_EQUAL if locus_rows.shape[2] == 8 else LOCUS_SET_UNEQUAL)
+    if order.shape[0] != locus_rows.shape[1]:
+        raise TphipError("order must have one row per quartet of locus_rows")
+    rows = np.zeros(order.shape + (locus_rows.shape[2],))
+    _check(load().tphip_locus_set_rows(int(device), locus_rows.ctypes.data, locus_rows.shape[0], ctypes.byref(opts), rows.ctypes.data))
+    return rows
+
+
+def locus_set_rows_dev(d_locus_rows, nloci, order, d_rows, family=LOCUS_SET_EQUAL, device=0, stream=0):
+    """tphip_locus_set_rows_dev on device tensors: d_locus_rows [L, n_q, 8 or 13], order a host array [n_q, K], d_rows
+    [n_q, K, 8 or 13]."""
+    opts, order = _locus_set_opts(order, family)
+    _check(load().tphip_locus_set_rows_dev(int(device), _ptr(d_locus_rows), int(nloci), ctypes.byref(opts), _ptr(d_rows), stream))
 
 
 def state_histogram(states, locus_offsets, device=0):

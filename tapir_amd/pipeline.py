@@ -1088,6 +1088,103 @@ def exact_unequal_quartet_tables(eng, per_locus, pi, exch, run, quartets, model=
                                  window_cap, True)
 
 
+# ---- locus-set accumulation curves ----------------------------------------------------------------
+def locus_set_order(rows, names, order_file=None, max_k=None):
+    """The order of the loci per quartet, int32 [n_q, K].  rows: the per-locus normal rows [L, n_q, 8] (quartet_tables) or
+    [L, n_q, 13] (unequal_quartet_tables); names: the loci's names, in the rows' order.  Default: per quartet, descending
+    per-locus normal-approximation p_correct, ties by ascending locus index (a stable argsort of -p_correct: the order never
+    depends on the exact rows).  order_file: one locus name per line (blank lines skipped), the same order for every quartet;
+    a name that is unknown or repeated is an error, loci that are not named are left out.  Then the order is cut to max_k."""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 3 or rows.shape[2] not in (8, 13) or rows.shape[0] != len(names):
+        raise PipelineError("locus_set_order: rows must be [L, n_q, 8] or [L, n_q, 13] with one row per name")
+    L, n_q = rows.shape[:2]
+    if max_k is not None and int(max_k) < 1:
+        raise PipelineError("locus_set_order: max_k must be at least 1")
+    if order_file is None:
+        order = np.argsort(-rows[:, :, 5 if rows.shape[2] == 8 else 9].T, axis=1, kind="stable")
+    else:
+        index = {n: l for l, n in enumerate(names)}
+        if len(index) != L:
+            raise PipelineError("locus_set_order: the loci's names are not distinct, so an order file cannot name them")
+        with open(order_file) as fh:
+            listed = [line.strip() for line in fh if line.strip()]
+        if not listed:
+            raise PipelineError("{0} names no locus".format(order_file))
+        for n in listed:
+            if n not in index:
+                raise PipelineError("{0}: unknown locus {1!r}".format(order_file, n))
+        if len(set(listed)) != len(listed):
+            raise PipelineError("{0}: a locus is named more than once".format(order_file))
+        order = np.tile(np.array([index[n] for n in listed], dtype=np.int64), (n_q, 1))
+    if max_k is not None:
+        order = order[:, :int(max_k)]
+    return np.ascontiguousarray(order, dtype=np.int32)
+
+
+def locus_set_tables(eng, rows, order, device=0):
+    """The normal rows of the sets order[q, :k], k = 1..K: [n_q, K, 8 or 13] in the per-locus rows' layout (their sums added
+    left to right in the order given, the family's probability rule on those sums; engine.locus_set_rows).  rows: all loci's
+    per-locus rows [L, n_q, 8 or 13].  A list longer than the engine's 256 quartets, or than 2^24 (locus, quartet) pairs, goes
+    through in slices; a quartet's rows do not depend on the others, so the split changes nothing."""
+    rows, order = np.asarray(rows, dtype=np.float64), np.asarray(order, dtype=np.int32)
+    if order.size == 0:
+        return np.zeros(order.shape + (rows.shape[2],))
+    L, n_q = rows.shape[:2]
+    step = int(max(1, min(256, (1 << 24) // max(1, L))))
+    return np.concatenate([eng.locus_set_rows(rows[:, q0:q0 + step], order[q0:q0 + step], device)
+                           for q0 in range(0, n_q, step)], axis=0)
+
+
+def locus_set_tile(L, ncols, n_q, n_k, planes, window_cap):
+    """(quartets per tile, n_head): the most quartets (up to the engine's 256) for which the per-site planes and the exact
+    call's workspace at n_head = 1 (per quartet 48 bytes a locus, 36 a prefix, 2048 for the alignment of its five arrays, 24 a computed prefix and tile of 512
+    frequencies at the cap) each fit EXACT_QUARTET_BYTES, and then the most prefixes per quartet that keep the workspace
+    there; at least one of each."""
+    tiles = (window_cap * (window_cap // 2 + 1) + 511) // 512
+    fixed = 48 * L + 36 * n_k + 2048
+    fit = min(EXACT_QUARTET_BYTES // max(1, 8 * planes * ncols), EXACT_QUARTET_BYTES // (fixed + 24 * tiles), (1 << 24) // max(1, L))
+    tile = int(max(1, min(256, n_q, fit)))
+    n_head = (EXACT_QUARTET_BYTES // tile - fixed) // (24 * tiles)
+    return tile, int(max(1, min(n_k, n_head)))
+
+
+def exact_locus_set_tables(eng, per_locus, pi, exch, run, quartets, order, model="gtr", window_cap=128, unequal=False):
+    """The exact rows of the sets order[q, :k]: [n_q, K, 6] (p_correct, p_ac, p_ad, p_polytomy, window, tail_bound) on the
+    torus M = window_cap, from the final rates of `per_locus` on a no-rounding plan exactly as exact_quartet_tables.
+    quartets [n_q, 2] (T, t_o), or [n_q, 5] (Ta, Tb, Tc, Td, t_o) with unequal=True; order indexes per_locus.  Quartets go
+    through in tiles (locus_set_tile): the planes are written by *_quartet_sites_dev and read by locus_set_exact_dev where
+    they lie; only the rows leave the device.  A prefix that does not fit the cap, or lies beyond the tile's n_head, has NaN
+    probabilities and window 0."""
+    quartets = np.asarray(quartets, dtype=np.float64).reshape(-1, 5 if unequal else 2)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    L, n_q, device = len(per_locus), len(quartets), run.device
+    if order.ndim != 2 or order.shape[0] != n_q:
+        raise PipelineError("exact_locus_set_tables: order must be [n_q, K]")
+    n_k = order.shape[1]
+    if L == 0 or n_q == 0 or n_k == 0:
+        return np.zeros((n_q, n_k, 6))
+    pi, exch = _locus_models(L, pi, exch, model)
+    with run.final_rates_plan(eng, per_locus, pi=pi, exch=exch, model=model) as (plan, rates, offsets):
+        ncols, planes = int(offsets[-1]), 3 if unequal else 2
+        tile, n_head = locus_set_tile(L, ncols, n_q, n_k, planes, window_cap)
+        stream = eng.device_stream(device)
+        d_rates = eng.device_array(rates, device)
+        d_flat = eng.device_empty((planes * tile * ncols,), device)
+        d_ws = eng.device_empty((plan.locus_set_exact_workspace_bytes(tile, n_k, window_cap, n_head),), device, np.uint8)
+        out = np.zeros((n_q, n_k, 6))
+        for q0 in range(0, n_q, tile):
+            part = quartets[q0:q0 + tile]
+            k = len(part)
+            d_sites = d_flat[:planes * k * ncols].reshape(planes, k, ncols)   # (a view: the last tile may be shorter)
+            (plan.unequal_quartet_sites_dev if unequal else plan.quartet_sites_dev)(d_rates, None, part, d_sites, stream)
+            d_rows = eng.device_empty((k, n_k, 6), device)
+            plan.locus_set_exact_dev(d_sites[0], d_sites[1], d_sites[planes - 1], order[q0:q0 + k], d_rows, d_ws, window_cap, 0.0,
+                                     n_head, stream)
+            out[q0:q0 + k] = eng.host_array(d_rows)
+        return out
+
+
 def dot_progress():
     sys.stdout.write(".")
     sys.stdout.flush()
