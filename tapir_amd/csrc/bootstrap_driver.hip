@@ -1,68 +1,25 @@
 // bootstrap_driver.hip -- site bootstrap of the per-locus PI rows: the C entry points
-// tphip_pi_resample / tphip_pi_bootstrap / tphip_bootstrap_counts and the blocking of loci and replicate ranges over the
-// caller's workspace.  The kernels are in bootstrap_kernels.hpp.
-//
-// A block is a run of consecutive loci whose counts [B][columns], per-site integrals [columns][n_i] and replicate rows
-// [loci][B][Wb] fit the workspace together; a locus too long for that is taken alone, its counts drawn and multiplied one
-// replicate range at a time.  A replicate row is computed by one wave from the locus' own columns in a fixed order
-// (bootstrap_matrix_kernel), so the blocking changes no bit of it.
+// tphip_pi_resample / tphip_pi_bootstrap / tphip_bootstrap_counts and the summary launch of every band stage.  The kernels are
+// in bootstrap_kernels.hpp; how loci and replicate ranges are blocked over the caller's workspace is in band_blocks.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstddef>
 #include <vector>
 
+#include "band_driver_common.hpp"
 #include "bootstrap_kernels.hpp"
-#include "tphip_internal.hpp"
 
 namespace {
 
-constexpr size_t kBsAlign = 256;
-constexpr size_t kBsPreferredCap = (size_t)1 << 30;   // like stage 1's chunks: about 1 GiB of workspace at most
 constexpr int32_t kBsMaxResampleReps = 1 << 20;
+constexpr BandOptsRules kBsOptsRules{band_seed_end<tphip_bootstrap_opts>(), band_ids_end<tphip_bootstrap_opts>(), "null tphip_bootstrap_opts",
+                                     "tphip_bootstrap_opts.struct_size is too small: set it to sizeof(tphip_bootstrap_opts)",
+                                     "bootstrap replicates must be in 2..4096", "bootstrap level must be in (0, 1)"};
 
 inline int32_t bs_width(const tphip_plan* p) { return p->T + p->n_i; }
-inline size_t bs_pitch(int64_t cols) { return (size_t)((cols + 1) & ~(int64_t)1); }   // 16-bit counters per row: whole words
-inline size_t bs_integ_bytes(const tphip_plan* p, int64_t cols) { return align_up(sizeof(double) * (size_t)cols * (size_t)p->n_i, kBsAlign); }
-inline size_t bs_counts_bytes(int64_t cols, int64_t reps) { return align_up(sizeof(uint16_t) * bs_pitch(cols) * (size_t)reps, kBsAlign); }
-inline size_t bs_rows_bytes(const tphip_plan* p, int64_t loci, int64_t reps) {
-    return align_up(sizeof(double) * (size_t)loci * (size_t)reps * (size_t)bs_width(p), kBsAlign);
-}
-inline size_t bs_ids_bytes(const tphip_plan* p) { return align_up(sizeof(int64_t) * (size_t)p->nloci, kBsAlign); }
-// replicates drawn together when a locus goes through the workspace in ranges: whole replicate tiles of the matrix kernel
-inline int64_t bs_min_range(int64_t B) { return std::min<int64_t>(B, kBsRepTile); }
-
-struct BsOpts {
-    int32_t replicates = 0;
-    double level = 0.0;
-    uint64_t seed = 0;
-    const int64_t* locus_ids = nullptr;
-};
-
-int bs_read_opts(const tphip_bootstrap_opts* o, BsOpts* out) {
-    if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_bootstrap_opts");
-    if (o->struct_size < offsetof(tphip_bootstrap_opts, seed) + sizeof(uint64_t))
-        return fail(TPHIP_ERR_INVALID, "tphip_bootstrap_opts.struct_size is too small: set it to sizeof(tphip_bootstrap_opts)");
-    out->replicates = o->replicates;
-    out->level = o->level;
-    out->seed = o->seed;
-    out->locus_ids = (o->struct_size >= offsetof(tphip_bootstrap_opts, locus_ids) + sizeof(const int64_t*)) ? o->locus_ids : nullptr;
-    if (out->replicates < 2 || out->replicates > kBsMaxReplicates)
-        return fail(TPHIP_ERR_INVALID, "bootstrap replicates must be in 2..4096");
-    if (!(out->level > 0.0 && out->level < 1.0)) return fail(TPHIP_ERR_INVALID, "bootstrap level must be in (0, 1)");
-    return TPHIP_OK;
-}
-
-void bs_workspace(const tphip_plan* p, int64_t B, size_t* min_bytes, size_t* preferred) {
-    size_t mn = 0;
-    for (int64_t l = 0; l < p->nloci; ++l) {
-        const int64_t n = p->h_offsets[l + 1] - p->h_offsets[l];
-        mn = std::max(mn, bs_integ_bytes(p, n) + bs_counts_bytes(n, bs_min_range(B)) + bs_rows_bytes(p, 1, B));
-    }
-    const size_t fixed = kBsAlign + bs_ids_bytes(p);
-    const size_t all = bs_integ_bytes(p, p->ncols) + bs_counts_bytes(p->ncols, B) + bs_rows_bytes(p, p->nloci, B);
-    *min_bytes = fixed + mn;
-    *preferred = fixed + std::max(mn, std::min(all, kBsPreferredCap));
+inline BandBytes bs_workspace(const tphip_plan* p, int64_t B) {
+    return bootstrap_bytes(p->h_offsets.data(), p->nloci, p->n_i, bs_width(p), B, kBsRepTile);
 }
 
 // numpy.quantile's default rule for n sorted values: virtual index n q + (1 + q (1 - 1 - 1)) - 1 evaluated as numpy does,
@@ -77,19 +34,6 @@ void bs_quantile_index(int32_t n, double q, int32_t* idx, double* frac) {
     if (vi >= (double)(n - 1)) { *idx = n - 1; *frac = 0.0; return; }
     *idx = (int32_t)fl;
     *frac = vi - fl;
-}
-
-// what bootstrap_summary_kernel needs for B replicates of width Wb at coverage `level`; rows and summary are set per launch
-SummaryParams bs_summary_params(int32_t B, int32_t Wb, double level) {
-    SummaryParams S;
-    S.rows = nullptr; S.summary = nullptr;
-    S.B = B; S.Wb = Wb;
-    S.npow2 = 2;
-    while (S.npow2 < B) S.npow2 <<= 1;
-    const double q_lo = (1.0 - level) / 2.0, q_hi = 1.0 - (1.0 - level) / 2.0;
-    bs_quantile_index(B, q_lo, &S.idx_lo, &S.frac_lo);
-    bs_quantile_index(B, q_hi, &S.idx_hi, &S.frac_hi);
-    return S;
 }
 
 // integrals of the columns [c0, c1) into `integ`
@@ -136,13 +80,23 @@ int bs_launch_draw(const int64_t* d_offsets, const int64_t* d_ids, int64_t singl
     return TPHIP_OK;
 }
 
-char* bs_ws_base(void* ws, size_t ws_bytes, size_t* usable) {
-    const uintptr_t a = (uintptr_t)ws, b = (a + kBsAlign - 1) / kBsAlign * kBsAlign;
-    *usable = ws_bytes > (size_t)(b - a) ? ws_bytes - (size_t)(b - a) : 0;
-    return (char*)b;
-}
-
 }  // namespace
+
+int band_summarize(const double* d_rows, int64_t nloci, int32_t B, int32_t Wb, double level, double* d_summary, hipStream_t st) {
+    if (nloci == 0 || Wb == 0) return TPHIP_OK;
+    if (nloci * (int64_t)Wb > 0x7fffffffll) return fail(TPHIP_ERR_INVALID, "nloci * Wb beyond 2^31 - 1 entries");
+    SummaryParams S;
+    S.rows = d_rows; S.summary = d_summary;
+    S.B = B; S.Wb = Wb;
+    S.npow2 = 2;
+    while (S.npow2 < B) S.npow2 <<= 1;
+    const double q_lo = (1.0 - level) / 2.0, q_hi = 1.0 - (1.0 - level) / 2.0;
+    bs_quantile_index(B, q_lo, &S.idx_lo, &S.frac_lo);
+    bs_quantile_index(B, q_hi, &S.idx_hi, &S.frac_hi);
+    bootstrap_summary_kernel<<<dim3((unsigned)(nloci * Wb)), dim3(256), 0, st>>>(S);
+    HIP_TRY(hipGetLastError());
+    return TPHIP_OK;
+}
 
 extern "C" {
 
@@ -150,18 +104,15 @@ int32_t tphip_bootstrap_width(const tphip_plan* p) { return p ? bs_width(p) : 0;
 
 int tphip_bootstrap_workspace_bytes(const tphip_plan* p, const tphip_bootstrap_opts* opts, size_t* min_bytes, size_t* preferred_bytes) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    size_t mn = 0, pf = 0;
-    if (!opts) {   // tphip_pi_resample_dev: the per-site integrals of the loci of a block, nothing that depends on nrep
-        mn = kBsAlign + bs_integ_bytes(p, p->max_locus_cols);
-        pf = kBsAlign + std::max(bs_integ_bytes(p, p->max_locus_cols), std::min(bs_integ_bytes(p, p->ncols), kBsPreferredCap));
-    } else {
-        BsOpts o;
-        int rc = bs_read_opts(opts, &o);
+    BandBytes W = resample_bytes(p->max_locus_cols, p->ncols, p->n_i);   // no opts: tphip_pi_resample_dev, whatever nrep
+    if (opts) {
+        BandOpts o;
+        int rc = band_read_opts(opts, kBsOptsRules, &o);
         if (rc) return rc;
-        bs_workspace(p, o.replicates, &mn, &pf);
+        W = bs_workspace(p, o.replicates);
     }
-    if (min_bytes) *min_bytes = mn;
-    if (preferred_bytes) *preferred_bytes = pf;
+    if (min_bytes) *min_bytes = W.min;
+    if (preferred_bytes) *preferred_bytes = W.preferred;
     return TPHIP_OK;
 }
 
@@ -175,15 +126,13 @@ int tphip_pi_resample_dev(tphip_plan* p, const double* d_rates, const int32_t* d
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     size_t usable = 0;
-    char* base = ws ? bs_ws_base(ws, ws_bytes, &usable) : nullptr;
+    char* base = ws ? band_ws_base(ws, ws_bytes, &usable) : nullptr;
     const PiParams Q = plan_pi_params(p, d_rates, d_nres);
-    // the workspace holds the per-site integrals only: consecutive loci as far as it reaches
     int64_t l0 = 0;
     while (l0 < p->nloci) {
-        int64_t l1 = l0;
-        while (l1 < p->nloci && (l1 == l0 || bs_integ_bytes(p, p->h_offsets[l1 + 1] - p->h_offsets[l0]) <= usable)) ++l1;
+        const int64_t l1 = resample_next_block(p->h_offsets.data(), p->nloci, l0, p->n_i, usable);
         const int64_t c0 = p->h_offsets[l0], c1 = p->h_offsets[l1];
-        if (p->n_i > 0 && c1 > c0 && (!base || bs_integ_bytes(p, c1 - c0) > usable))
+        if (p->n_i > 0 && c1 > c0 && (!base || bs_integ_bytes(c1 - c0, p->n_i) > usable))
             return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than the minimum of tphip_bootstrap_workspace_bytes()");
         int rc = bs_launch_integrals(p, Q, c0, c1, (double*)base, st);
         if (rc) return rc;
@@ -198,53 +147,34 @@ int tphip_pi_resample_dev(tphip_plan* p, const double* d_rates, const int32_t* d
 int tphip_pi_bootstrap_dev(tphip_plan* p, const double* d_rates, const int32_t* d_nres, const tphip_bootstrap_opts* opts,
                            double* d_summary, double* d_rows, void* ws, size_t ws_bytes, void* stream) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    BsOpts o;
-    int rc = bs_read_opts(opts, &o);
+    BandOpts o;
+    int rc = band_read_opts(opts, kBsOptsRules, &o);
     if (rc) return rc;
     const int32_t Wb = bs_width(p), B = o.replicates;
     if (p->nloci == 0 || Wb == 0) return TPHIP_OK;
     if (!d_summary || !ws || (p->ncols && !d_rates)) return fail(TPHIP_ERR_INVALID, "null device pointer");
-    size_t mn = 0, pf = 0;
-    bs_workspace(p, B, &mn, &pf);
-    if (ws_bytes < mn) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than the minimum of tphip_bootstrap_workspace_bytes()");
+    if (ws_bytes < bs_workspace(p, B).min)
+        return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than the minimum of tphip_bootstrap_workspace_bytes()");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     size_t usable = 0;
-    char* base = bs_ws_base(ws, ws_bytes, &usable);
-    int64_t* d_ids = nullptr;
-    if (o.locus_ids) {
-        // read now: the caller's array need not outlive the call
-        d_ids = (int64_t*)base;
-        HIP_TRY(hipMemcpyAsync(d_ids, o.locus_ids, sizeof(int64_t) * (size_t)p->nloci, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    base += bs_ids_bytes(p);
-    usable -= bs_ids_bytes(p);
+    char* base = band_ws_base(ws, ws_bytes, &usable);
+    const int64_t* d_ids = nullptr;
+    rc = band_stage_ids((int64_t*)base, o.locus_ids, p->nloci, st, &d_ids);
+    if (rc) return rc;
+    base += band_ids_bytes(p->nloci);
+    usable -= band_ids_bytes(p->nloci);
     const PiParams Q = plan_pi_params(p, d_rates, d_nres);
-    SummaryParams S = bs_summary_params(B, Wb, o.level);
     int64_t l0 = 0;
     while (l0 < p->nloci) {
-        // as many consecutive loci as fit with all B replicates' counts; a locus that does not fit alone goes in ranges
-        int64_t l1 = l0;
-        while (l1 < p->nloci) {
-            const int64_t n = p->h_offsets[l1 + 1] - p->h_offsets[l0];
-            if (l1 - l0 >= 65535 || bs_integ_bytes(p, n) + bs_counts_bytes(n, B) + bs_rows_bytes(p, l1 + 1 - l0, B) > usable) break;
-            ++l1;
-        }
-        int64_t range = B;
-        if (l1 == l0) {
-            l1 = l0 + 1;
-            const int64_t n = p->h_offsets[l1] - p->h_offsets[l0];
-            const size_t left = usable - bs_integ_bytes(p, n) - bs_rows_bytes(p, 1, B);   // >= one minimal range: ws_bytes >= mn
-            range = bs_min_range(B);
-            while (range + kBsRepTile <= B && bs_counts_bytes(n, range + kBsRepTile) <= left) range += kBsRepTile;
-        }
+        const BsBlock blk = bootstrap_next_block(p->h_offsets.data(), p->nloci, l0, p->n_i, Wb, B, kBsRepTile, usable);
+        const int64_t l1 = blk.l1, range = blk.range;
         const int64_t c0 = p->h_offsets[l0], c1 = p->h_offsets[l1], n = c1 - c0;
         int64_t max_cols = 0;
         for (int64_t l = l0; l < l1; ++l) max_cols = std::max(max_cols, p->h_offsets[l + 1] - p->h_offsets[l]);
         double* integ = (double*)base;
-        uint16_t* counts = (uint16_t*)(base + bs_integ_bytes(p, n));
-        double* ws_rows = (double*)(base + bs_integ_bytes(p, n) + bs_counts_bytes(n, range));
+        uint16_t* counts = (uint16_t*)(base + bs_integ_bytes(n, p->n_i));
+        double* ws_rows = (double*)(base + bs_integ_bytes(n, p->n_i) + bs_counts_bytes(n, range));
         double* rows = d_rows ? d_rows + (size_t)l0 * (size_t)B * (size_t)Wb : ws_rows;
         rc = bs_launch_integrals(p, Q, c0, c1, integ, st);
         if (rc) return rc;
@@ -255,10 +185,8 @@ int tphip_pi_bootstrap_dev(tphip_plan* p, const double* d_rates, const int32_t* 
             rc = bs_launch_matrix(p, Q, l0, l1, counts, (int64_t)bs_pitch(n), c0, integ, c0, rows, B, r0, nr, st);
             if (rc) return rc;
         }
-        S.rows = rows;
-        S.summary = d_summary + (size_t)l0 * 4 * (size_t)Wb;
-        bootstrap_summary_kernel<<<dim3((unsigned)((l1 - l0) * Wb)), dim3(256), 0, st>>>(S);
-        HIP_TRY(hipGetLastError());
+        rc = band_summarize(rows, l1 - l0, B, Wb, o.level, d_summary + (size_t)l0 * 4 * (size_t)Wb, st);
+        if (rc) return rc;
         l0 = l1;
     }
     return TPHIP_OK;
@@ -276,7 +204,7 @@ int tphip_pi_resample(tphip_plan* p, const double* rates, const int32_t* nres, c
     const int32_t* d_n = S.in(nres, n);
     const uint16_t* d_c = S.in(counts, n * (size_t)nrep);
     double* d_rows = S.out(rows, nrows);
-    const size_t ws_bytes = kBsAlign + std::min(bs_integ_bytes(p, p->ncols), std::max(kBsPreferredCap, bs_integ_bytes(p, p->max_locus_cols)));
+    const size_t ws_bytes = resample_bytes(p->max_locus_cols, p->ncols, p->n_i).preferred;
     char* ws = S.scratch<char>(ws_bytes);
     if (S.rc) return S.rc;
     int rc = tphip_pi_resample_dev(p, d_r, d_n, d_c, nrep, d_rows, ws, ws_bytes, nullptr);
@@ -286,15 +214,14 @@ int tphip_pi_resample(tphip_plan* p, const double* rates, const int32_t* nres, c
 int tphip_pi_bootstrap(tphip_plan* p, const double* rates, const int32_t* nres, const tphip_bootstrap_opts* opts, double* summary,
                        double* rows) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    BsOpts o;
-    int rc = bs_read_opts(opts, &o);
+    BandOpts o;
+    int rc = band_read_opts(opts, kBsOptsRules, &o);
     if (rc) return rc;
     const size_t n = (size_t)p->ncols, Wb = (size_t)bs_width(p), L = (size_t)p->nloci, B = (size_t)o.replicates;
     if (L * Wb == 0) return TPHIP_OK;
     if (!summary || (n && !rates)) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(p->device));
-    size_t mn = 0, pf = 0;
-    bs_workspace(p, o.replicates, &mn, &pf);
+    const size_t pf = bs_workspace(p, o.replicates).preferred;
     Staging S;
     const double* d_r = S.in(rates, n);
     const int32_t* d_n = S.in(nres, n);
@@ -324,24 +251,17 @@ int tphip_bootstrap_counts(int32_t device, uint64_t seed, int64_t locus_id, int6
     return TPHIP_OK;
 }
 
-// The summary kernel on any [L][B][Wb] rows (it lives here because a __global__ definition must stay in one translation
-// unit; the parametric bootstrap of simulate_driver.hip ends in this call).
+// The summary kernel on any [L][B][Wb] rows
 int tphip_summarize_rows_dev(int32_t device, const double* d_rows, int64_t nloci, int32_t B, int32_t Wb, double level,
                              double* d_summary, void* stream) {
     if (tphip_device_count() <= 0) return fail(TPHIP_ERR_NO_DEVICE, "no HIP device visible: libtphip has no CPU path");
-    if (B < 2 || B > kBsMaxReplicates) return fail(TPHIP_ERR_INVALID, "replicates must be in 2..4096");
+    if (B < 2 || B > kBandMaxReplicates) return fail(TPHIP_ERR_INVALID, "replicates must be in 2..4096");
     if (!(level > 0.0 && level < 1.0)) return fail(TPHIP_ERR_INVALID, "level must be in (0, 1)");
     if (nloci < 0 || Wb < 0) return fail(TPHIP_ERR_INVALID, "negative size");
     if (nloci == 0 || Wb == 0) return TPHIP_OK;
     if (!d_rows || !d_summary) return fail(TPHIP_ERR_INVALID, "null device pointer");
-    if (nloci * (int64_t)Wb > 0x7fffffffll) return fail(TPHIP_ERR_INVALID, "nloci * Wb beyond 2^31 - 1 entries");
     HIP_TRY(hipSetDevice(device));
-    SummaryParams S = bs_summary_params(B, Wb, level);
-    S.rows = d_rows;
-    S.summary = d_summary;
-    bootstrap_summary_kernel<<<dim3((unsigned)(nloci * Wb)), dim3(256), 0, (hipStream_t)stream>>>(S);
-    HIP_TRY(hipGetLastError());
-    return TPHIP_OK;
+    return band_summarize(d_rows, nloci, B, Wb, level, d_summary, (hipStream_t)stream);
 }
 
 int tphip_summarize_rows(int32_t device, const double* rows, int64_t nloci, int32_t B, int32_t Wb, double level, double* summary) {

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "band_blocks.hpp"
 #include "philox4x32.hpp"
 #include "pi_rate.hpp"
 #include "quadpack_device.hpp"
@@ -34,7 +35,6 @@ constexpr int kBsWaveReps = 32;               // replicates per wave: two 16-row
 constexpr int kBsRepTile = 4 * kBsWaveReps;   // 128 replicates per workgroup
 constexpr int kBsPitch = 129;                 // doubles per staged column: odd, so that the 32 columns a wave writes at one
                                               // entry index fall into 32 different bank pairs
-constexpr int kBsMaxReplicates = 4096;        // the summary kernel sorts one entry's replicates in 32 KB of LDS
 constexpr int kBsDrawBlock = 256;
 
 // ---- generator: philox4x32.hpp (plain C++, so that a host program can pin it to the known answers) ----------------
@@ -245,7 +245,7 @@ __device__ __forceinline__ double numpy_lerp(double a, double b, double t) {
 // fixed order -- thread t adds the sorted values t, t + 256, ... and a fixed tree adds the 256 partial sums -- so the
 // result depends on the multiset of values only.  sd is two-pass with B - 1 in the denominator.
 __global__ __launch_bounds__(256) void bootstrap_summary_kernel(SummaryParams P) {
-    __shared__ double v[kBsMaxReplicates];
+    __shared__ double v[kBandMaxReplicates];
     __shared__ double red[256];
     const int li = blockIdx.x / (unsigned)P.Wb, w = blockIdx.x % (unsigned)P.Wb;
     const double* src = P.rows + (size_t)li * P.B * P.Wb + w;

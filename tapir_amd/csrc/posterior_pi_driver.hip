@@ -1,59 +1,36 @@
 // posterior_pi_driver.hip -- the empirical-Bayes rate posterior carried into the per-locus PI rows:
-// the C entry points tphip_posterior_pi / tphip_posterior_pi_workspace_bytes, the blocking of loci over the caller's
-// workspace, and the launch that turns the mixture kernel's f_k + log w_k into the category posterior for
-// tphip_eb_posterior_table (eb_driver.hip).  The kernels are in posterior_pi_kernels.hpp; this unit is built with the
+// the C entry points tphip_posterior_pi / tphip_posterior_pi_workspace_bytes and the launch that turns the mixture kernel's
+// f_k + log w_k into the category posterior for tphip_eb_posterior_table (eb_driver.hip).  The kernels are in
+// posterior_pi_kernels.hpp, the blocking of loci over the caller's workspace in band_blocks.hpp; this unit is built with the
 // compiler's defaults.
-//
-// A block is a run of consecutive loci whose category rows [loci][K][Wb], counts [loci][B][K] and replicate rows
-// [loci][B][Wb] fit the workspace together.  Every locus needs the same amount, so any workspace that holds one locus
-// works, and since no kernel's arithmetic looks beyond its own locus the blocking changes no bit.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <vector>
 
+#include "band_driver_common.hpp"
 #include "posterior_pi_kernels.hpp"
-#include "tphip_internal.hpp"
 
 namespace {
 
-constexpr size_t kPpAlign = 256;
-constexpr size_t kPpPreferredCap = (size_t)1 << 30;   // as the bootstrap's: about 1 GiB of workspace at most
-constexpr int64_t kPpTargetGroups = 1024;             // workgroups a draw launch aims at before it cuts loci into segments
+constexpr int64_t kPpTargetGroups = 1024;   // workgroups a draw launch aims at before it cuts loci into segments
+constexpr int64_t kPpMaxSegCols = 0x40000000;   // columns of a segment at most (2^30: seg_cols is an int32)
+constexpr BandOptsRules kPpOptsRules{sizeof(tphip_posterior_pi_opts), sizeof(tphip_posterior_pi_opts), "null tphip_posterior_pi_opts",
+                                     "tphip_posterior_pi_opts.struct_size is smaller than this library's struct",
+                                     "posterior replicates must be in 2..4096", "posterior level must be in (0, 1)"};
 
-struct PpOpts {
-    int32_t B = 0, K = 0;
-    double level = 0.0;
-    uint64_t seed = 0;
-    const int64_t* locus_ids = nullptr;
-};
-
-int pp_read_opts(const tphip_posterior_pi_opts* o, PpOpts* out) {
-    if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_posterior_pi_opts");
-    if (o->struct_size < sizeof(tphip_posterior_pi_opts))
-        return fail(TPHIP_ERR_INVALID, "tphip_posterior_pi_opts.struct_size is smaller than this library's struct");
-    out->B = o->replicates; out->K = o->ncat; out->level = o->level; out->seed = o->seed; out->locus_ids = o->locus_ids;
-    if (out->B < 2 || out->B > 4096) return fail(TPHIP_ERR_INVALID, "posterior replicates must be in 2..4096");
-    if (!(out->level > 0.0 && out->level < 1.0)) return fail(TPHIP_ERR_INVALID, "posterior level must be in (0, 1)");
-    if (out->K < 2 || out->K > kPpMaxCat) return fail(TPHIP_ERR_INVALID, "tphip_posterior_pi_opts.ncat must be in 2..16");
+// the shared fields, then K = ncat
+int pp_read_opts(const tphip_posterior_pi_opts* opts, BandOpts* o, int32_t* K) {
+    int rc = band_read_opts(opts, kPpOptsRules, o);
+    if (rc) return rc;
+    *K = opts->ncat;
+    if (*K < 2 || *K > kPpMaxCat) return fail(TPHIP_ERR_INVALID, "tphip_posterior_pi_opts.ncat must be in 2..16");
     return TPHIP_OK;
 }
 
 inline size_t pp_width(const tphip_plan* p) { return (size_t)(p->T + p->n_i); }
-inline size_t pp_ids_bytes(const tphip_plan* p) { return align_up(sizeof(int64_t) * (size_t)(p->nloci ? p->nloci : 1), kPpAlign); }
-inline size_t pp_ptab_bytes(const tphip_plan* p, const PpOpts& o, size_t loci) { return align_up(sizeof(double) * loci * o.K * pp_width(p), kPpAlign); }
-inline size_t pp_counts_bytes(const PpOpts& o, size_t loci) { return align_up(sizeof(int32_t) * loci * o.B * o.K, kPpAlign); }
-inline size_t pp_rows_bytes(const tphip_plan* p, const PpOpts& o, size_t loci) { return align_up(sizeof(double) * loci * o.B * pp_width(p), kPpAlign); }
-inline size_t pp_block_bytes(const tphip_plan* p, const PpOpts& o, size_t loci) {
-    return pp_ptab_bytes(p, o, loci) + pp_counts_bytes(o, loci) + pp_rows_bytes(p, o, loci);
-}
-
-void pp_workspace(const tphip_plan* p, const PpOpts& o, size_t* min_bytes, size_t* preferred) {
-    const size_t fixed = kPpAlign + pp_ids_bytes(p);
-    const size_t one = pp_block_bytes(p, o, 1);
-    const size_t all = pp_block_bytes(p, o, (size_t)(p->nloci ? p->nloci : 1));
-    *min_bytes = fixed + one;
-    *preferred = fixed + std::max(one, std::min(all, kPpPreferredCap));
+inline BandBytes pp_workspace(const tphip_plan* p, const BandOpts& o, int32_t K) {
+    return posterior_bytes(p->nloci, (size_t)K, (size_t)o.replicates, pp_width(p));
 }
 
 }  // namespace
@@ -76,13 +53,13 @@ int tphip_internal_posterior_normalize(tphip_plan* p, const int32_t* d_dup_of, c
 int tphip_posterior_pi_workspace_bytes(const tphip_plan* p, const tphip_posterior_pi_opts* opts, size_t* min_bytes,
                                        size_t* preferred_bytes) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    PpOpts o;
-    int rc = pp_read_opts(opts, &o);
+    BandOpts o;
+    int32_t K = 0;
+    int rc = pp_read_opts(opts, &o, &K);
     if (rc) return rc;
-    size_t mn = 0, pf = 0;
-    pp_workspace(p, o, &mn, &pf);
-    if (min_bytes) *min_bytes = mn;
-    if (preferred_bytes) *preferred_bytes = pf;
+    const BandBytes W = pp_workspace(p, o, K);
+    if (min_bytes) *min_bytes = W.min;
+    if (preferred_bytes) *preferred_bytes = W.preferred;
     return TPHIP_OK;
 }
 
@@ -90,41 +67,27 @@ int tphip_posterior_pi_dev(tphip_plan* p, const double* d_post, const int32_t* d
                            const tphip_posterior_pi_opts* opts, double* d_analytic, double* d_expected_counts, double* d_summary,
                            double* d_rows, int32_t* d_counts, void* ws, size_t ws_bytes, void* stream) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    PpOpts o;
-    int rc = pp_read_opts(opts, &o);
+    BandOpts o;
+    int32_t K = 0;
+    int rc = pp_read_opts(opts, &o, &K);
     if (rc) return rc;
     const size_t Wb = pp_width(p), L = (size_t)p->nloci;
-    const int32_t B = o.B, K = o.K;
+    const int32_t B = o.replicates;
     if (L == 0 || Wb == 0) return TPHIP_OK;
     if (!d_analytic || !d_expected_counts || !d_summary || !d_scale || !d_cat_rate || !ws || (p->ncols && !d_post))
         return fail(TPHIP_ERR_INVALID, "null device pointer");
-    size_t mn = 0, pf = 0;
-    pp_workspace(p, o, &mn, &pf);
-    if (ws_bytes < mn) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than the minimum of tphip_posterior_pi_workspace_bytes()");
+    if (ws_bytes < pp_workspace(p, o, K).min)
+        return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than the minimum of tphip_posterior_pi_workspace_bytes()");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    const uintptr_t a0 = (uintptr_t)ws, a1 = (a0 + kPpAlign - 1) / kPpAlign * kPpAlign;
-    char* base = (char*)a1;
-    size_t usable = ws_bytes - (size_t)(a1 - a0);
-    int64_t* d_ids = nullptr;
-    if (o.locus_ids) {
-        // read now: the caller's array need not outlive the call
-        d_ids = (int64_t*)base;
-        HIP_TRY(hipMemcpyAsync(d_ids, o.locus_ids, sizeof(int64_t) * L, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    base += pp_ids_bytes(p);
-    usable -= pp_ids_bytes(p);
-    // loci per block: the most whose three regions fit (at least one: ws_bytes >= mn)
-    size_t nb = 1;
-    {
-        size_t lo = 1, hi = std::min<size_t>(L, 65535);
-        while (lo < hi) {
-            const size_t mid = (lo + hi + 1) / 2;
-            if (pp_block_bytes(p, o, mid) <= usable) lo = mid; else hi = mid - 1;
-        }
-        nb = lo;
-    }
+    size_t usable = 0;
+    char* base = band_ws_base(ws, ws_bytes, &usable);
+    const int64_t* d_ids = nullptr;
+    rc = band_stage_ids((int64_t*)base, o.locus_ids, p->nloci, st, &d_ids);
+    if (rc) return rc;
+    base += band_ids_bytes(p->nloci);
+    usable -= band_ids_bytes(p->nloci);
+    const size_t nb = posterior_block_loci(L, (size_t)K, (size_t)B, Wb, usable);   // at least one: ws_bytes >= the minimum
     PostPiParams Q{};
     Q.pi = plan_pi_params(p, nullptr, d_nres);
     Q.models = p->d_models.p; Q.scale = d_scale; Q.cat_rate = d_cat_rate; Q.post = d_post; Q.ncols_total = p->ncols;
@@ -137,8 +100,8 @@ int tphip_posterior_pi_dev(tphip_plan* p, const double* d_post, const int32_t* d
     for (size_t l0 = 0; l0 < L; l0 += nb) {
         const size_t n = std::min(nb, L - l0);
         double* ptab = (double*)base;
-        int32_t* ws_counts = (int32_t*)(base + pp_ptab_bytes(p, o, n));
-        double* ws_rows = (double*)(base + pp_ptab_bytes(p, o, n) + pp_counts_bytes(o, n));
+        int32_t* ws_counts = (int32_t*)(base + pp_ptab_bytes(n, (size_t)K, Wb));
+        double* ws_rows = (double*)(base + pp_ptab_bytes(n, (size_t)K, Wb) + pp_counts_bytes(n, (size_t)B, (size_t)K));
         int32_t* counts = d_counts ? d_counts + l0 * (size_t)B * K : ws_counts;
         double* rows = d_rows ? d_rows + l0 * (size_t)B * Wb : ws_rows;
         Q.locus0 = (int32_t)l0; Q.ptab = ptab; Q.counts = counts; Q.rows = rows;
@@ -154,7 +117,7 @@ int tphip_posterior_pi_dev(tphip_plan* p, const double* d_post, const int32_t* d
             const int64_t groups = (int64_t)n * rep_tiles;
             const int64_t segs = std::min(tiles, std::max<int64_t>(1, (kPpTargetGroups + groups - 1) / groups));
             const int64_t seg_tiles = (tiles + segs - 1) / segs;
-            D.seg_cols = (int32_t)std::min<int64_t>(seg_tiles * kPpTile, (int64_t)1 << 30);
+            D.seg_cols = (int32_t)std::min<int64_t>(seg_tiles * kPpTile, kPpMaxSegCols);
             const int64_t gz = (max_cols + D.seg_cols - 1) / D.seg_cols;
             if (gz > 65535) return fail(TPHIP_ERR_INVALID, "locus too long for one posterior draw launch");
             D.locus0 = (int32_t)l0; D.counts = counts;
@@ -168,7 +131,7 @@ int tphip_posterior_pi_dev(tphip_plan* p, const double* d_post, const int32_t* d
         const int64_t entries = (int64_t)B * (int64_t)Wb;
         posterior_rows_kernel<<<dim3((unsigned)n, (unsigned)((entries + kPpBlock - 1) / kPpBlock)), dim3(kPpBlock), 0, st>>>(Q);
         HIP_TRY(hipGetLastError());
-        rc = tphip_summarize_rows_dev(p->device, rows, (int64_t)n, B, (int32_t)Wb, o.level, d_summary + l0 * 4 * Wb, stream);
+        rc = band_summarize(rows, (int64_t)n, B, (int32_t)Wb, o.level, d_summary + l0 * 4 * Wb, st);
         if (rc) return rc;
     }
     return TPHIP_OK;
@@ -178,15 +141,15 @@ int tphip_posterior_pi(tphip_plan* p, const double* post, const int32_t* nres, c
                        const tphip_posterior_pi_opts* opts, double* analytic, double* expected_counts, double* summary, double* rows,
                        int32_t* counts) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    PpOpts o;
-    int rc = pp_read_opts(opts, &o);
+    BandOpts o;
+    int32_t ncat = 0;
+    int rc = pp_read_opts(opts, &o, &ncat);
     if (rc) return rc;
-    const size_t n = (size_t)p->ncols, Wb = pp_width(p), L = (size_t)p->nloci, B = (size_t)o.B, K = (size_t)o.K;
+    const size_t n = (size_t)p->ncols, Wb = pp_width(p), L = (size_t)p->nloci, B = (size_t)o.replicates, K = (size_t)ncat;
     if (L * Wb == 0) return TPHIP_OK;
     if (!analytic || !expected_counts || !summary || !scale || !cat_rate || (n && !post)) return fail(TPHIP_ERR_INVALID, "null host pointer");
     HIP_TRY(hipSetDevice(p->device));
-    size_t mn = 0, pf = 0;
-    pp_workspace(p, o, &mn, &pf);
+    const size_t pf = pp_workspace(p, o, ncat).preferred;
     Staging S;
     const double* d_post = S.in(post, K * n);
     const int32_t* d_nres = S.in(nres, n);

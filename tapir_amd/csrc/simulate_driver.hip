@@ -1,6 +1,6 @@
 // simulate_driver.hip -- parametric bootstrap of site rates and PI rows: the C entry points
 // tphip_simulate_columns (+ _dev), tphip_pi_parametric_bootstrap (+ _dev) and tphip_parboot_workspace_bytes.  The kernels
-// are in simulate_kernels.hpp; the summary at the end is tphip_summarize_rows_dev (bootstrap_driver.hip).
+// are in simulate_kernels.hpp, the summary at the end in bootstrap_driver.hip, the workspace's layout in band_blocks.hpp.
 //
 // A replicate is three enqueues on the caller's stream: simulate every column at its fitted rate with the observed pattern of
 // missing cells, the plan's own site-rate and PI-table stages on the simulated states (tphip_run_dev: de-duplication and start
@@ -13,49 +13,25 @@
 #include <cstddef>
 #include <vector>
 
+#include "band_driver_common.hpp"
 #include "simulate_kernels.hpp"
-#include "tphip_internal.hpp"
 
 namespace {
 
-constexpr size_t kSimAlign = 256;
-constexpr int32_t kParbootMaxReplicates = 4096;   // the summary kernel's limit (bootstrap_kernels.hpp: kBsMaxReplicates)
+constexpr BandOptsRules kParbootOptsRules{band_seed_end<tphip_parboot_opts>(), band_ids_end<tphip_parboot_opts>(), "null tphip_parboot_opts",
+                                          "tphip_parboot_opts.struct_size is too small: set it to sizeof(tphip_parboot_opts)",
+                                          "parametric bootstrap replicates must be in 2..4096",
+                                          "parametric bootstrap level must be in (0, 1)"};
 
-struct SimOpts {
-    int32_t replicate = 0;
-    uint64_t seed = 0;
-    const int64_t* locus_ids = nullptr;
-};
-
-struct ParbootOpts {
-    int32_t replicates = 0;
-    double level = 0.0;
-    uint64_t seed = 0;
-    const int64_t* locus_ids = nullptr;
-};
+struct SimOpts { int32_t replicate = 0; uint64_t seed = 0; const int64_t* locus_ids = nullptr; };
 
 int sim_read_opts(const tphip_simulate_opts* o, SimOpts* out) {
     if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_simulate_opts");
-    if (o->struct_size < offsetof(tphip_simulate_opts, seed) + sizeof(uint64_t))
+    if (o->struct_size < band_seed_end<tphip_simulate_opts>())
         return fail(TPHIP_ERR_INVALID, "tphip_simulate_opts.struct_size is too small: set it to sizeof(tphip_simulate_opts)");
-    out->replicate = o->replicate;
-    out->seed = o->seed;
-    out->locus_ids = (o->struct_size >= offsetof(tphip_simulate_opts, locus_ids) + sizeof(const int64_t*)) ? o->locus_ids : nullptr;
+    out->replicate = o->replicate; out->seed = o->seed;
+    out->locus_ids = o->struct_size >= band_ids_end<tphip_simulate_opts>() ? o->locus_ids : nullptr;
     if (out->replicate < 0 || out->replicate >= kSimMaxReplicate) return fail(TPHIP_ERR_INVALID, "replicate must be in 0..65535");
-    return TPHIP_OK;
-}
-
-int parboot_read_opts(const tphip_parboot_opts* o, ParbootOpts* out) {
-    if (!o) return fail(TPHIP_ERR_INVALID, "null tphip_parboot_opts");
-    if (o->struct_size < offsetof(tphip_parboot_opts, seed) + sizeof(uint64_t))
-        return fail(TPHIP_ERR_INVALID, "tphip_parboot_opts.struct_size is too small: set it to sizeof(tphip_parboot_opts)");
-    out->replicates = o->replicates;
-    out->level = o->level;
-    out->seed = o->seed;
-    out->locus_ids = (o->struct_size >= offsetof(tphip_parboot_opts, locus_ids) + sizeof(const int64_t*)) ? o->locus_ids : nullptr;
-    if (out->replicates < 2 || out->replicates > kParbootMaxReplicates)
-        return fail(TPHIP_ERR_INVALID, "parametric bootstrap replicates must be in 2..4096");
-    if (!(out->level > 0.0 && out->level < 1.0)) return fail(TPHIP_ERR_INVALID, "parametric bootstrap level must be in (0, 1)");
     return TPHIP_OK;
 }
 
@@ -98,15 +74,10 @@ int sim_prepare(tphip_plan* p) {
     return TPHIP_OK;
 }
 
-// stream ids to the device (read now: the caller's array need not outlive the call); *d_ids = null without ids
+// stream ids into the plan's own buffer, made on first use; *d_ids = null without ids
 int sim_stage_ids(tphip_plan* p, const int64_t* locus_ids, hipStream_t st, const int64_t** d_ids) {
-    *d_ids = nullptr;
-    if (!locus_ids) return TPHIP_OK;
-    if (!p->d_sim_ids) HIP_TRY(hipMalloc((void**)&p->d_sim_ids, sizeof(int64_t) * (size_t)p->nloci));
-    HIP_TRY(hipMemcpyAsync(p->d_sim_ids, locus_ids, sizeof(int64_t) * (size_t)p->nloci, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *d_ids = p->d_sim_ids;
-    return TPHIP_OK;
+    if (locus_ids && !p->d_sim_ids) HIP_TRY(hipMalloc((void**)&p->d_sim_ids, sizeof(int64_t) * (size_t)p->nloci));
+    return band_stage_ids(p->d_sim_ids, locus_ids, p->nloci, st, d_ids);
 }
 
 int sim_launch(const tphip_plan* p, const double* d_rates, const uint8_t* d_mask, const int64_t* d_ids, uint32_t replicate,
@@ -131,30 +102,11 @@ int sim_launch(const tphip_plan* p, const double* d_rates, const uint8_t* d_mask
     return TPHIP_OK;
 }
 
-// workspace of tphip_pi_parametric_bootstrap_dev: one replicate of states, the per-column outputs of the site-rate stage, one
-// table, the rows, the moments and the plan's own workspace
-struct ParbootLayout {
-    size_t states, rate, subst, lnl, flag, nres, tables, rows, mean, m2, plan_ws, total;
-};
-
+// workspace of tphip_pi_parametric_bootstrap_dev: struct ParbootLayout of band_blocks.hpp on the plan's sizes
+inline int32_t parboot_width(const tphip_plan* p) { return p->T + p->n_i; }
 ParbootLayout parboot_layout(const tphip_plan* p, int32_t B) {
-    ParbootLayout L;
-    const size_t n = (size_t)p->ncols, W = (size_t)(p->T + p->n_t + 2 * p->n_i), Wb = (size_t)(p->T + p->n_i);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off = align_up(off + bytes, kSimAlign); return at; };
-    L.states = take((size_t)p->ntaxa * n);
-    L.rate = take(sizeof(double) * n);
-    L.subst = take(sizeof(double) * n);
-    L.lnl = take(sizeof(double) * n);
-    L.flag = take(n);
-    L.nres = take(sizeof(int32_t) * n);
-    L.tables = take(sizeof(double) * (size_t)p->nloci * W);
-    L.rows = take(sizeof(double) * (size_t)p->nloci * (size_t)B * Wb);
-    L.mean = take(sizeof(double) * n);
-    L.m2 = take(sizeof(double) * n);
-    L.plan_ws = take(p->ws.total);
-    L.total = off + kSimAlign;   // the caller's pointer is aligned up
-    return L;
+    return tphip::parboot_layout((size_t)p->ntaxa, (size_t)p->ncols, (size_t)p->nloci, (size_t)(p->T + p->n_t + 2 * p->n_i),
+                                 (size_t)parboot_width(p), (size_t)B, p->ws.total);
 }
 
 }  // namespace
@@ -198,8 +150,8 @@ int tphip_simulate_columns(tphip_plan* p, const double* rates, const uint8_t* ma
 
 int tphip_parboot_workspace_bytes(const tphip_plan* p, const tphip_parboot_opts* opts, size_t* bytes) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    ParbootOpts o;
-    int rc = parboot_read_opts(opts, &o);
+    BandOpts o;
+    int rc = band_read_opts(opts, kParbootOptsRules, &o);
     if (rc) return rc;
     if (bytes) *bytes = parboot_layout(p, o.replicates).total;
     return TPHIP_OK;
@@ -209,21 +161,19 @@ int tphip_pi_parametric_bootstrap_dev(tphip_plan* p, const double* d_rates, cons
                                       const tphip_parboot_opts* opts, double* d_summary, double* d_rows, double* d_rate_mean,
                                       double* d_rate_sd, void* ws, size_t ws_bytes, void* stream) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    ParbootOpts o;
-    int rc = parboot_read_opts(opts, &o);
+    BandOpts o;
+    int rc = band_read_opts(opts, kParbootOptsRules, &o);
     if (rc) return rc;
     rc = sim_prepare(p);
     if (rc) return rc;
     if (!d_states_observed && p->ncols) return fail(TPHIP_ERR_INVALID, "null observed alignment: its pattern of missing cells is part of the bootstrap");
     if (!d_summary || !ws || (p->ncols && !d_rates)) return fail(TPHIP_ERR_INVALID, "null device pointer");
-    const int32_t B = o.replicates, Wb = p->T + p->n_i, W = p->T + p->n_t + 2 * p->n_i;
+    const int32_t B = o.replicates, Wb = parboot_width(p), W = p->T + p->n_t + 2 * p->n_i;
     const ParbootLayout L = parboot_layout(p, B);
-    const uintptr_t a = (uintptr_t)ws, al = (a + kSimAlign - 1) / kSimAlign * kSimAlign;
-    if (ws_bytes < L.total - kSimAlign + (size_t)(al - a))
-        return fail(TPHIP_ERR_INVALID, "workspace smaller than tphip_parboot_workspace_bytes()");
+    if (ws_bytes < L.total) return fail(TPHIP_ERR_INVALID, "workspace smaller than tphip_parboot_workspace_bytes()");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)al;
+    char* base = band_ws_base(ws, ws_bytes);
     const int64_t* d_ids = nullptr;
     rc = sim_stage_ids(p, o.locus_ids, st, &d_ids);
     if (rc) return rc;
@@ -252,16 +202,16 @@ int tphip_pi_parametric_bootstrap_dev(tphip_plan* p, const double* d_rates, cons
         }
         HIP_TRY(hipGetLastError());
     }
-    return tphip_summarize_rows_dev(p->device, rows, p->nloci, B, Wb, o.level, d_summary, stream);
+    return band_summarize(rows, p->nloci, B, Wb, o.level, d_summary, st);
 }
 
 int tphip_pi_parametric_bootstrap(tphip_plan* p, const double* rates, const uint8_t* states_observed, const tphip_parboot_opts* opts,
                                   double* summary, double* rows, double* rate_mean, double* rate_sd) {
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
-    ParbootOpts o;
-    int rc = parboot_read_opts(opts, &o);
+    BandOpts o;
+    int rc = band_read_opts(opts, kParbootOptsRules, &o);
     if (rc) return rc;
-    const size_t n = (size_t)p->ncols, cells = (size_t)p->ntaxa * n, Wb = (size_t)(p->T + p->n_i), L = (size_t)p->nloci,
+    const size_t n = (size_t)p->ncols, cells = (size_t)p->ntaxa * n, Wb = (size_t)parboot_width(p), L = (size_t)p->nloci,
                  B = (size_t)o.replicates;
     if (!states_observed && n) return fail(TPHIP_ERR_INVALID, "null observed alignment: its pattern of missing cells is part of the bootstrap");
     if (!summary || (n && !rates)) return fail(TPHIP_ERR_INVALID, "null host pointer");

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "band_blocks.hpp"   // align_up
 #include "gtr_model.hpp"
 #include "locus_lik_params.hpp"
 #include "locus_value_params.hpp"
@@ -95,8 +96,6 @@ struct HostArena {
         if (h) (void)hipHostFree(h);
     }
 };
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // small RAII set of device buffers for the host-pointer conveniences
 struct Scratch {

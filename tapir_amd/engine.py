@@ -264,6 +264,32 @@ def _size_out(fn, *args):
     return n.value
 
 
+def _size_pair(fn, *args):
+    """fn(*args, &min, &preferred) of a *_workspace_bytes entry point that blocks over its workspace: (min, preferred)."""
+    mn, pf = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(fn(*args, ctypes.byref(mn), ctypes.byref(pf)))
+    return mn.value, pf.value
+
+
+def _ws_nbytes(d_ws, ws_bytes):
+    """How much of the workspace d_ws a call may use: ws_bytes, by default all of it."""
+    return _nbytes(d_ws) if ws_bytes is None else int(ws_bytes)
+
+
+def _candidates(blen_vecs, cand_locus, cand_exch, cand_vec, cand_scale, cand_pidx, cand_pfac):
+    """The candidate arrays of locus_loglik / locus_gradient as the library reads them, defaults filled in: (bv, cl, ce, cv, cs, ci, cf)."""
+    bv = _np(blen_vecs, np.float64)
+    bv = bv.reshape(-1, bv.shape[-1])
+    cl = _np(cand_locus, np.int32).reshape(-1)
+    n = len(cl)
+    ce = _np(cand_exch, np.float64).reshape(n, 6)
+    cv = _np(np.arange(n) if cand_vec is None else cand_vec, np.int32).reshape(n)
+    cs = _np(np.ones(n) if cand_scale is None else cand_scale, np.float64).reshape(n)
+    ci = _np(np.full(n, -1) if cand_pidx is None else cand_pidx, np.int32).reshape(n)
+    cf = _np(np.ones(n) if cand_pfac is None else cand_pfac, np.float64).reshape(n)
+    return bv, cl, ce, cv, cs, ci, cf
+
+
 class _Pinned:
     def __init__(self, ptr):
         self.ptr = ptr
@@ -535,22 +561,10 @@ class Plan:
                                                       sc.ctypes.data, _ptr(d_post), _ptr(d_rate), _ptr(d_sd), _ptr(d_lnl),
                                                       _ptr(d_nres), stream))
 
-    def _posterior_pi_opts(self, ncat, replicates, seed, level, locus_ids):
-        ids = None
-        if locus_ids is not None:
-            ids = _np(locus_ids, np.int64).reshape(-1)
-            if ids.size != self.nloci:
-                raise TphipError("locus_ids must have one entry per locus of the plan")
-        opts = PosteriorPiOpts(struct_size=ctypes.sizeof(PosteriorPiOpts), replicates=int(replicates), level=float(level),
-                               seed=int(seed) & 0xFFFFFFFFFFFFFFFF, locus_ids=_ptr(ids), ncat=int(ncat))
-        return opts, ids
-
     def posterior_pi_workspace_bytes(self, ncat, replicates, seed=1, level=0.95):
         """(min, preferred) bytes of device workspace for posterior_pi_dev; any size >= min gives the same bits."""
-        opts, _ = self._posterior_pi_opts(ncat, replicates, seed, level, None)
-        mn, pf = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(self._lib.tphip_posterior_pi_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(mn), ctypes.byref(pf)))
-        return mn.value, pf.value
+        opts, _ = self._band_opts(PosteriorPiOpts, replicates, seed, level, None, ncat=int(ncat))
+        return _size_pair(self._lib.tphip_posterior_pi_workspace_bytes, self._h, ctypes.byref(opts))
 
     def posterior_pi(self, post, nres, scale, cat_rate, replicates=200, seed=1, level=0.95, locus_ids=None, return_rows=False,
                      return_counts=False):
@@ -572,7 +586,7 @@ class Plan:
             nres = _np(nres, np.int32)
             if nres.shape != (self.ncols,):
                 raise TphipError("nres must be [ncols]")
-        opts, ids = self._posterior_pi_opts(K, replicates, seed, level, locus_ids)
+        opts, ids = self._band_opts(PosteriorPiOpts, replicates, seed, level, locus_ids, ncat=K)
         Wb, B = self.bootstrap_width, int(replicates)
         out = dict(analytic=np.zeros((self.nloci, 2, Wb)), expected_counts=np.zeros((self.nloci, K)),
                    summary=np.zeros((self.nloci, 4, Wb)))
@@ -588,11 +602,10 @@ class Plan:
     def posterior_pi_dev(self, d_post, d_nres, d_scale, d_cat_rate, ncat, d_analytic, d_expected, d_summary, d_rows, d_counts, d_ws,
                          replicates, seed=1, level=0.95, locus_ids=None, stream=0, ws_bytes=None):
         """tphip_posterior_pi_dev on device tensors (d_nres / d_rows / d_counts may be None); ws_bytes: use only that much of d_ws."""
-        opts, ids = self._posterior_pi_opts(ncat, replicates, seed, level, locus_ids)
-        nbytes = _nbytes(d_ws) if ws_bytes is None else int(ws_bytes)
+        opts, ids = self._band_opts(PosteriorPiOpts, replicates, seed, level, locus_ids, ncat=int(ncat))
         _check(self._lib.tphip_posterior_pi_dev(self._h, _ptr(d_post), _ptr(d_nres), _ptr(d_scale), _ptr(d_cat_rate), ctypes.byref(opts),
                                                 _ptr(d_analytic), _ptr(d_expected), _ptr(d_summary), _ptr(d_rows), _ptr(d_counts),
-                                                _ptr(d_ws), nbytes, stream))
+                                                _ptr(d_ws), _ws_nbytes(d_ws, ws_bytes), stream))
 
     def corrected_rates(self, rates, nres=None):
         """parse_site_rates (+ cull when nres is given) as the PI stage applies them: round4(rate) / correction."""
@@ -611,15 +624,8 @@ class Plan:
         additionally multiplied by cand_pfac[c].  Defaults: vec = arange, scale = 1, no perturbation.
         cache: device_cache() object that keeps the alignment on the device between calls."""
         states = _np(states, np.uint8)
-        bv = _np(blen_vecs, np.float64)
-        bv = bv.reshape(-1, bv.shape[-1])
-        cl = _np(cand_locus, np.int32).reshape(-1)
+        bv, cl, ce, cv, cs, ci, cf = _candidates(blen_vecs, cand_locus, cand_exch, cand_vec, cand_scale, cand_pidx, cand_pfac)
         n = len(cl)
-        ce = _np(cand_exch, np.float64).reshape(n, 6)
-        cv = _np(np.arange(n) if cand_vec is None else cand_vec, np.int32).reshape(n)
-        cs = _np(np.ones(n) if cand_scale is None else cand_scale, np.float64).reshape(n)
-        ci = _np(np.full(n, -1) if cand_pidx is None else cand_pidx, np.int32).reshape(n)
-        cf = _np(np.ones(n) if cand_pfac is None else cand_pfac, np.float64).reshape(n)
         out = np.empty(n)
         ref = ctypes.byref(cache.ptr) if cache is not None else None
         _check(self._lib.tphip_locus_loglik(self._h, states.ctypes.data, ref, bv.shape[0], bv.ctypes.data, n, cl.ctypes.data,
@@ -649,15 +655,8 @@ class Plan:
         None, sum_dlogt[n]) and, with curvature=True, a fifth item d2logt[n, nnodes]; dexch holds branch lengths
         fixed, dlogt is d lnL / d log t_b, d2logt the matching second derivatives (Hessian diagonal)."""
         states = _np(states, np.uint8)
-        bv = _np(blen_vecs, np.float64)
-        bv = bv.reshape(-1, bv.shape[-1])
-        cl = _np(cand_locus, np.int32).reshape(-1)
+        bv, cl, ce, cv, cs, ci, cf = _candidates(blen_vecs, cand_locus, cand_exch, cand_vec, cand_scale, cand_pidx, cand_pfac)
         n = len(cl)
-        ce = _np(cand_exch, np.float64).reshape(n, 6)
-        cv = _np(np.arange(n) if cand_vec is None else cand_vec, np.int32).reshape(n)
-        cs = _np(np.ones(n) if cand_scale is None else cand_scale, np.float64).reshape(n)
-        ci = _np(np.full(n, -1) if cand_pidx is None else cand_pidx, np.int32).reshape(n)
-        cf = _np(np.ones(n) if cand_pfac is None else cand_pfac, np.float64).reshape(n)
         lnl, dex, st = np.empty(n), np.empty((n, 6)), np.empty(n)
         dlt = np.empty((n, bv.shape[1])) if per_branch else None
         d2 = np.empty((n, bv.shape[1])) if curvature else None
@@ -743,16 +742,6 @@ class Plan:
         _check(self._lib.tphip_pi_tables_dev(self._h, _ptr(d_rates), _ptr(d_nres), _ptr(d_tables), _ptr(d_ws), _nbytes(d_ws), stream))
 
     # ---- site bootstrap of the PI rows (csrc/bootstrap_driver.hip) ------------------------------
-    def _bootstrap_opts(self, replicates, seed, level, locus_ids):
-        ids = None
-        if locus_ids is not None:
-            ids = _np(locus_ids, np.int64).reshape(-1)
-            if ids.size != self.nloci:
-                raise TphipError("locus_ids must have one entry per locus of the plan")
-        opts = BootstrapOpts(struct_size=ctypes.sizeof(BootstrapOpts), replicates=int(replicates), level=float(level),
-                             seed=int(seed) & 0xFFFFFFFFFFFFFFFF, locus_ids=_ptr(ids))
-        return opts, ids
-
     @property
     def bootstrap_width(self):
         """Wb = T + n_i: net PI at t = 0..T-1, then one integral per interval."""
@@ -760,16 +749,12 @@ class Plan:
 
     def bootstrap_workspace_bytes(self, replicates, seed=1, level=0.95):
         """(min, preferred) bytes of device workspace for pi_bootstrap_dev; any size >= min gives the same bits."""
-        opts, _ = self._bootstrap_opts(replicates, seed, level, None)
-        mn, pf = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(self._lib.tphip_bootstrap_workspace_bytes(self._h, ctypes.byref(opts), ctypes.byref(mn), ctypes.byref(pf)))
-        return mn.value, pf.value
+        opts, _ = self._band_opts(BootstrapOpts, replicates, seed, level, None)
+        return _size_pair(self._lib.tphip_bootstrap_workspace_bytes, self._h, ctypes.byref(opts))
 
     def resample_workspace_bytes(self):
         """(min, preferred) bytes of device workspace for pi_resample_dev (per-site integrals only; any nrep)."""
-        mn, pf = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(self._lib.tphip_bootstrap_workspace_bytes(self._h, None, ctypes.byref(mn), ctypes.byref(pf)))
-        return mn.value, pf.value
+        return _size_pair(self._lib.tphip_bootstrap_workspace_bytes, self._h, None)
 
     def pi_bootstrap(self, rates, nres=None, replicates=200, seed=1, level=0.95, locus_ids=None, return_rows=False):
         """Site bootstrap of the PI rows (tphip_pi_bootstrap): `replicates` resamples of every locus' columns with
@@ -778,7 +763,7 @@ class Plan:
         locus_ids: the generator's stream id per locus (default: the plan's locus index); a locus gives the same rows
         whatever plan it is part of as long as its id, the seed and its rates are the same."""
         rates, nres = self._rates_nres(rates, nres)
-        opts, ids = self._bootstrap_opts(replicates, seed, level, locus_ids)
+        opts, ids = self._band_opts(BootstrapOpts, replicates, seed, level, locus_ids)
         Wb = self.bootstrap_width
         summary = np.zeros((self.nloci, 4, Wb))
         rows = np.zeros((self.nloci, int(replicates), Wb)) if return_rows else None
@@ -801,10 +786,9 @@ class Plan:
     def pi_bootstrap_dev(self, d_rates, d_nres, d_summary, d_rows, d_ws, replicates, seed=1, level=0.95, locus_ids=None,
                          stream=0, ws_bytes=None):
         """tphip_pi_bootstrap_dev on device tensors (d_nres / d_rows may be None); ws_bytes: use only that much of d_ws."""
-        opts, ids = self._bootstrap_opts(replicates, seed, level, locus_ids)
-        nbytes = _nbytes(d_ws) if ws_bytes is None else int(ws_bytes)
+        opts, ids = self._band_opts(BootstrapOpts, replicates, seed, level, locus_ids)
         _check(self._lib.tphip_pi_bootstrap_dev(self._h, _ptr(d_rates), _ptr(d_nres), ctypes.byref(opts), _ptr(d_summary),
-                                                _ptr(d_rows), _ptr(d_ws), nbytes, stream))
+                                                _ptr(d_rows), _ptr(d_ws), _ws_nbytes(d_ws, ws_bytes), stream))
 
     def pi_resample_dev(self, d_rates, d_nres, d_counts, nrep, d_rows, d_ws, stream=0):
         """tphip_pi_resample_dev on device tensors: d_counts int16/uint16 [nrep, ncols], d_rows [L, nrep, Wb]."""
@@ -975,12 +959,22 @@ class Plan:
 
     # ---- parametric bootstrap of site rates and PI rows (csrc/simulate_driver.hip) ---------------
     def _ids(self, locus_ids):
-        if locus_ids is None:
-            return None
-        ids = _np(locus_ids, np.int64).reshape(-1)
-        if ids.size != self.nloci:
+        ids = None if locus_ids is None else _np(locus_ids, np.int64).reshape(-1)
+        if ids is not None and ids.size != self.nloci:
             raise TphipError("locus_ids must have one entry per locus of the plan")
         return ids
+
+    def _band_opts(self, cls, replicates, seed, level, locus_ids, **extra):
+        """The options of a replicate-band family (BootstrapOpts, ParbootOpts, PosteriorPiOpts with ncat=) and the id array
+        they point into (keep it alive)."""
+        ids = self._ids(locus_ids)
+        return cls(struct_size=ctypes.sizeof(cls), replicates=int(replicates), level=float(level), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   locus_ids=_ptr(ids), **extra), ids
+
+    def _simulate_opts(self, replicate, seed, locus_ids):
+        ids = self._ids(locus_ids)
+        return SimulateOpts(struct_size=ctypes.sizeof(SimulateOpts), replicate=int(replicate), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            locus_ids=_ptr(ids)), ids
 
     def simulate_columns(self, rates, mask=None, replicate=0, seed=1, locus_ids=None):
         """Alignment columns simulated down the plan's tree (tphip_simulate_columns): column c under its locus' model at the
@@ -992,30 +986,20 @@ class Plan:
         if mask is not None:
             mask = _np(mask, np.uint8)
             assert mask.shape == (self.ntaxa, self.ncols), (mask.shape, self.ntaxa, self.ncols)
-        ids = self._ids(locus_ids)
-        opts = SimulateOpts(struct_size=ctypes.sizeof(SimulateOpts), replicate=int(replicate), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
-                            locus_ids=_ptr(ids))
+        opts, ids = self._simulate_opts(replicate, seed, locus_ids)
         out = np.empty((self.ntaxa, self.ncols), np.uint8)
         _check(self._lib.tphip_simulate_columns(self._h, rates.ctypes.data, _ptr(mask), ctypes.byref(opts), out.ctypes.data))
         return out
 
     def simulate_columns_dev(self, d_rates, d_mask, d_states_out, replicate=0, seed=1, locus_ids=None, stream=0):
         """tphip_simulate_columns_dev on device tensors (d_mask may be None); enqueues on `stream`."""
-        ids = self._ids(locus_ids)
-        opts = SimulateOpts(struct_size=ctypes.sizeof(SimulateOpts), replicate=int(replicate), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
-                            locus_ids=_ptr(ids))
+        opts, ids = self._simulate_opts(replicate, seed, locus_ids)
         _check(self._lib.tphip_simulate_columns_dev(self._h, _ptr(d_rates), _ptr(d_mask), ctypes.byref(opts), _ptr(d_states_out),
                                                     stream))
 
-    def _parboot_opts(self, replicates, seed, level, locus_ids):
-        ids = self._ids(locus_ids)
-        opts = ParbootOpts(struct_size=ctypes.sizeof(ParbootOpts), replicates=int(replicates), level=float(level),
-                           seed=int(seed) & 0xFFFFFFFFFFFFFFFF, locus_ids=_ptr(ids))
-        return opts, ids
-
     def parboot_workspace_bytes(self, replicates, seed=1, level=0.95):
         """bytes of device workspace for pi_parametric_bootstrap_dev."""
-        opts, _ = self._parboot_opts(replicates, seed, level, None)
+        opts, _ = self._band_opts(ParbootOpts, replicates, seed, level, None)
         return _size_out(self._lib.tphip_parboot_workspace_bytes, self._h, ctypes.byref(opts))
 
     def pi_parametric_bootstrap(self, rates, states, replicates=100, seed=1, level=0.95, locus_ids=None, return_rows=False,
@@ -1029,7 +1013,7 @@ class Plan:
         if states is not None:
             states = _np(states, np.uint8)
             assert states.shape == (self.ntaxa, self.ncols), (states.shape, self.ntaxa, self.ncols)
-        opts, ids = self._parboot_opts(replicates, seed, level, locus_ids)
+        opts, ids = self._band_opts(ParbootOpts, replicates, seed, level, locus_ids)
         Wb = self.bootstrap_width
         summary = np.zeros((self.nloci, 4, Wb))
         rows = np.zeros((self.nloci, int(replicates), Wb)) if return_rows else None
@@ -1047,10 +1031,10 @@ class Plan:
     def pi_parametric_bootstrap_dev(self, d_rates, d_states, d_summary, d_rows, d_rate_mean, d_rate_sd, d_ws, replicates, seed=1,
                                     level=0.95, locus_ids=None, stream=0, ws_bytes=None):
         """tphip_pi_parametric_bootstrap_dev on device tensors (d_rows / d_rate_mean / d_rate_sd may be None)."""
-        opts, ids = self._parboot_opts(replicates, seed, level, locus_ids)
-        nbytes = _nbytes(d_ws) if ws_bytes is None else int(ws_bytes)
+        opts, ids = self._band_opts(ParbootOpts, replicates, seed, level, locus_ids)
         _check(self._lib.tphip_pi_parametric_bootstrap_dev(self._h, _ptr(d_rates), _ptr(d_states), ctypes.byref(opts), _ptr(d_summary),
-                                                           _ptr(d_rows), _ptr(d_rate_mean), _ptr(d_rate_sd), _ptr(d_ws), nbytes, stream))
+                                                           _ptr(d_rows), _ptr(d_rate_mean), _ptr(d_rate_sd), _ptr(d_ws),
+                                                           _ws_nbytes(d_ws, ws_bytes), stream))
 
     def profile_enable(self, on=True):
         _check(self._lib.tphip_profile_enable(self._h, 1 if on else 0))
