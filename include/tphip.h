@@ -811,6 +811,50 @@ int tphip_summarize_rows_dev(int32_t device, const double *d_rows, int64_t nloci
 int tphip_summarize_rows(int32_t device, const double *rows, int64_t nloci, int32_t B, int32_t Wb, double level,
                          double *summary);
 
+/* ------------------------------------------------------------------------------------------------
+ * Site concordance factors (an extension; Minh, Hahn & Lanfear 2020): what the alignment shows at an internode, beside what
+ * the quartet sections predict for it.  Plan-less: the calls read the states, the loci's column ranges and the set tables.
+ *
+ * A set is four groups of taxon rows A, B | C, D.  counts[l][s] = (conc, disc1, disc2): summed over the columns of locus l,
+ * the number of quartets (a, b, c, d) in A x B x C x D whose four cells are each exactly one base (mask 1, 2, 4 or 8) and
+ * read xxyy (ab|cd), xyxy (ac|bd) or xyyx (ad|bc) with x != y.  A quartet with a gap, ?, N or an IUPAC union at the column is
+ * not decisive there.  Per column the three numbers come from the groups' base counts a_x, b_x, c_x, d_x in closed form,
+ * conc = (sum_x a_x b_x)(sum_y c_y d_y) - sum_x a_x b_x c_x d_x and the two other pairings likewise, in 64-bit integers (four
+ * groups of 260 taxa pass 2^32 on one column); the sums over the columns wrap at 2^64.  Integer arithmetic throughout: the
+ * counts do not depend on the launch, the loci beside a locus or the sets beside a set.
+ *
+ * Groups may be of any size >= 1 and name the taxa in any order; taxa may belong to no group of a set.  Refused
+ * (TPHIP_ERR_INVALID, before any device is touched): n_sets < 1, ntaxa < 4, an empty group, a taxon row outside 0..ntaxa-1, a
+ * taxon listed twice within one set, row_pitch < ncols_total. */
+typedef struct tphip_concordance_sets {
+    uint32_t struct_size;         /* sizeof(tphip_concordance_sets) of the caller */
+    int64_t n_sets;
+    const int64_t *group_offsets; /* HOST [4 * n_sets + 1]: CSR into group_taxa; groups A, B, C, D of set s are 4s .. 4s+3 */
+    const int32_t *group_taxa;    /* HOST taxon rows */
+} tphip_concordance_sets;
+
+/* d_states [ntaxa][row_pitch] (row_pitch >= ncols_total: the rows may be longer than the batch), d_locus_offsets [nloci + 1],
+ * d_counts [nloci][n_sets][3].  Enqueues on `stream`; the set tables are copied to a buffer of the call's own, which is freed
+ * before the call returns (that waits for the kernels). */
+int tphip_concordance_counts_dev(int32_t device, const uint8_t *d_states, int64_t ncols_total, int64_t row_pitch,
+                                 int32_t ntaxa, const int64_t *d_locus_offsets, int64_t nloci,
+                                 const tphip_concordance_sets *sets, uint64_t *d_counts, void *stream);
+/* host-pointer twin */
+int tphip_concordance_counts(int32_t device, const uint8_t *states, int64_t ncols_total, int64_t row_pitch, int32_t ntaxa,
+                             const int64_t *locus_offsets, int64_t nloci, const tphip_concordance_sets *sets,
+                             uint64_t *counts);
+/* The rows of the internodes: internode i owns the sets node_sets[i] .. node_sets[i + 1] - 1 (HOST [n_nodes + 1], at least two
+ * each): the first is its pooled set (the whole groups), the second its nearest-tip quartet, the rest its sampled quartets.
+ * d_rows [nloci][n_nodes][12] = pooled_c, pooled_1, pooled_2, near_c, near_1, near_2, sCF, sDF1, sDF2, sN, n_decisive,
+ * n_quartets.  Over the sampled quartets with dec = c + d1 + d2 > 0, in set order: sCF = (sum c / dec) / n_decisive, sDF1 and
+ * sDF2 likewise, sN = (sum dec) / n_decisive; each sum a sequential fp64 addition, one division at the end; fractions, not
+ * percentages; NaN when n_decisive is 0.  The counts are converted to fp64 exactly when they are below 2^53, which is the
+ * caller's to see to.  Handled as the counts call: node_sets is copied, `stream` waited for. */
+int tphip_concordance_rows_dev(int32_t device, const uint64_t *d_counts, int64_t nloci, int64_t n_sets,
+                               const int64_t *node_sets, int64_t n_nodes, double *d_rows, void *stream);
+int tphip_concordance_rows(int32_t device, const uint64_t *counts, int64_t nloci, int64_t n_sets, const int64_t *node_sets,
+                           int64_t n_nodes, double *rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,8 +179,37 @@ def get_args(argv=None):
     new.add_argument('--locus-sets-target', type=float, default=None, metavar='P',
                      help="the p_correct, in (0, 1), whose smallest sufficient k `locus_set_summary` reports (default 0.95).  "
                           "Needs --locus-sets")
+    new.add_argument('--site-concordance', default=False, action='store_true',
+                     help="site concordance factors (Minh, Hahn & Lanfear 2020) of every locus at every internode of the input "
+                          "tree: what the alignment shows where --tree-quartets predicts.  Per locus and internode the numbers "
+                          "of quartets its sites support as ab|cd, ac|bd and ad|bc -- over all quartets of the four groups of "
+                          "taxa around the internode (exact, from the groups' base counts), for the nearest-tip quartet of "
+                          "--tree-quartets, and sCF, sDF1, sDF2 and sN as means over sampled quartets -- go into "
+                          "phylogenetic-informativeness-concordance.sqlite, with the same for all loci together.  Cells that "
+                          "are not exactly one base are not decisive.  Not with --site-rates")
+    new.add_argument('--site-concordance-quartets', type=int, default=None, metavar='Q',
+                     help="sampled quartets per internode, 1..10000 (default 100); an internode with at most Q quartets has all "
+                          "of them listed instead.  Needs --site-concordance")
+    new.add_argument('--site-concordance-seed', type=int, default=None, metavar='S',
+                     help="seed of the sampling (default 1); needs --site-concordance")
     args = parser.parse_args(argv)
     _locus_set_flags(parser, args)
+    if args.site_concordance:
+        if args.site_rates:
+            parser.error("--site-concordance counts the sites of the alignments: it cannot be combined with --site-rates, which reads none")
+        if args.site_concordance_quartets is None:
+            args.site_concordance_quartets = 100
+        if not 1 <= args.site_concordance_quartets <= 10000:
+            parser.error("--site-concordance-quartets must be in 1..10000")
+        if args.site_concordance_seed is None:
+            args.site_concordance_seed = 1
+        if not 0 <= args.site_concordance_seed < 2 ** 64:
+            parser.error("--site-concordance-seed must be in 0..2^64-1")
+    else:
+        for flag, value in (('--site-concordance-quartets', args.site_concordance_quartets),
+                            ('--site-concordance-seed', args.site_concordance_seed)):
+            if value is not None:
+                parser.error("{0} needs --site-concordance".format(flag))
     if args.exact_quartets:
         if args.quartets is None and args.unequal_quartets is None and not args.tree_quartets:
             parser.error("--exact-quartets needs --quartets, --unequal-quartets or --tree-quartets")
@@ -600,6 +629,8 @@ def _main(args, rank, world, on_gpu, engine_mod, pool):
         _quartets_stage(cx)
     if args.unequal_quartets or args.tree_quartets:
         _unequal_quartets_stage(cx)
+    if args.site_concordance:
+        _concordance_stage(cx)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
@@ -698,6 +729,31 @@ def _gather_objects(obj, rank, world):
     box = [None] * world if rank == 0 else None
     dist.gather_object(obj, box, dst=0)
     return box
+
+
+def _concordance_stage(cx):
+    """--site-concordance: every rank counts its own loci over sets that are the same everywhere; the rows travel like the PI
+    rows, the ranks' integer totals as objects to rank 0, which adds them and forms the rows of all loci together.  The input
+    tree is read as it is, like --tree-quartets; a tree without an internode gives empty tables and no engine call."""
+    args = cx.args
+    root = newick.read_tree(args.tree, args.tree_format)
+    groups = compute.tree_concordance_groups(root)
+    sets = compute.concordance_sets(groups, cx.run.leaf_names, args.site_concordance_quartets, args.site_concordance_seed)
+    rows, totals = pipeline.concordance_tables(cx.eng, cx.mine, cx.per_locus, cx.run, sets, subsets=cx.subsets)
+    all_rows = cx.gather(rows)
+    parts = _gather_objects(totals, cx.rank, cx.world)
+    if cx.rank != 0:
+        return
+    both = np.zeros((len(groups), 12))
+    if len(groups) and len(cx.files):
+        total = [[sum(int(p[s, k]) for p in parts) for k in range(3)] for s in range(len(totals))]
+        if max(max(t) for t in total) >= 2 ** 53:
+            raise pipeline.PipelineError("the concordance counts of all loci together reach 2^53: they would not convert exactly")
+        both = cx.eng.concordance_rows(np.array(total, dtype=np.uint64).reshape(1, len(total), 3), sets["node_sets"],
+                                       device=cx.run.device)[0]
+    db.write_concordance_db(cx.path('phylogenetic-informativeness-concordance.sqlite'), cx.files, all_rows, both, groups, sets,
+                            args.site_concordance_quartets, args.site_concordance_seed,
+                            clades=[(q[0], q[1]) for q in compute.tree_quartets(root)])
 
 
 def _locus_sets(cx, name, all_rows, labels, lengths, models, unequal):

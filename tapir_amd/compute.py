@@ -155,6 +155,106 @@ def tree_quartets(root):
     return out
 
 
+def tree_concordance_groups(root):
+    """The taxon groups around the internodes tree_quartets reports, for the site concordance factors (DESIGN.md section
+    3.12): one entry (label, A, B, C, D, nearest) per row of tree_quartets(root), in its order and with its labels.  A and B
+    are the leaf names of the two lineages tree_quartets picks at the clade-side end of the edge, C and D those of the two it
+    picks at the other end, each pair ordered as tree_quartets orders its lengths: nearer tip first, ties to the children in
+    file order with the parent's direction last.  At an end with more than two other neighbours the lineages not picked take
+    no part.  nearest: the four leaves whose path lengths are (Ta, Tb, Tc, Td), ties to the first leaf in the tree's leaf
+    order."""
+    order = newick.postorder(root)
+    all_leaves = newick.leaves(root)
+    rank = {id(leaf): k for k, leaf in enumerate(all_leaves)}
+    length = lambda n: n.length or 0.0   # noqa: E731
+    down = {}                            # (distance, leaf rank, leaf) of the nearest leaf below
+    for n in order:
+        down[id(n)] = min(((length(c) + down[id(c)][0],) + down[id(c)][1:] for c in n.children), key=lambda w: w[:2],
+                          default=(0.0, rank.get(id(n)), n))
+    joined = len(root.children) == 2
+    up = {}                              # the same through the parent edge
+    for n in reversed(order):
+        if n is root:
+            continue
+        p = n.parent
+        ways = [(length(s) + down[id(s)][0],) + down[id(s)][1:] for s in p.children if s is not n]
+        if p is not root:
+            ways.append(up[id(p)])
+        best = min(ways, key=lambda w: w[:2]) if ways else (float("inf"), None, None)
+        up[id(n)] = (length(n) + best[0],) + best[1:]
+
+    def below(c):
+        return (length(c) + down[id(c)][0], [leaf.name for leaf in newick.leaves(c)], down[id(c)][2])
+
+    def above(p):
+        inside = {id(leaf) for leaf in newick.leaves(p)}
+        return (up[id(p)][0], [leaf.name for leaf in all_leaves if id(leaf) not in inside], up[id(p)][2])
+
+    out = []
+    for n in order:
+        if n is root or n.is_leaf():
+            continue
+        p = n.parent
+        near = [below(c) for c in n.children]
+        if p is root and joined:
+            other = p.children[1]
+            if n is not p.children[0] or other.is_leaf():
+                continue
+            t_o = length(n) + length(other)
+            far = [below(c) for c in other.children]
+        else:
+            t_o = length(n)
+            far = [below(s) for s in p.children if s is not n]
+            if p is not root:
+                far.append(above(p))
+        if t_o == 0.0 or len(near) < 2 or len(far) < 2:
+            continue
+        near.sort(key=lambda w: w[0])    # (stable: ties keep the order they were listed in)
+        far.sort(key=lambda w: w[0])
+        four = near[:2] + far[:2]
+        out.append(("node%d" % (len(out) + 1),) + tuple(w[1] for w in four) + ([w[2].name for w in four],))
+    return out
+
+
+def concordance_sets(groups, leaf_names, quartets=100, seed=1):
+    """The sets of four taxon groups the site concordance counts are taken over, from tree_concordance_groups' entries:
+    dict(group_offsets int64 [4 * n_sets + 1], group_taxa int32 (rows of leaf_names), node_sets int64 [n_nodes + 1],
+    sizes [n_nodes, 4], enumerated bool [n_nodes]).  Per internode, in this order: the pooled set (the whole groups), the
+    nearest-tip quartet, then the sampled quartets -- every quartet of A x B x C x D in lexicographic order, A outermost, when
+    there are at most `quartets` of them (nothing is sampled then), else `quartets` draws with replacement from the
+    internode's own generator np.random.default_rng([seed, i]), i its index from 0: integers(0, |G|, size=quartets) for
+    G = A, B, C, D in that order.  Nothing depends on the loci, the rank or the blocking."""
+    import itertools
+    row = {name: k for k, name in enumerate(leaf_names)}
+    quartets = int(quartets)
+    taxa, sizes_of_groups, node_sets, sizes, enumerated = [], [], [0], [], []
+
+    def add(a, b, c, d):
+        for g in (a, b, c, d):
+            taxa.extend(g)
+            sizes_of_groups.append(len(g))
+
+    for i, (label, A, B, C, D, nearest) in enumerate(groups):
+        G = [[row[name] for name in g] for g in (A, B, C, D)]
+        add(*G)
+        add(*[[row[name]] for name in nearest])
+        total = len(A) * len(B) * len(C) * len(D)
+        if total <= quartets:
+            for a, b, c, d in itertools.product(*G):
+                add([a], [b], [c], [d])
+        else:
+            rng = np.random.default_rng([int(seed), i])
+            picks = [rng.integers(0, len(g), size=quartets) for g in G]
+            for k in range(quartets):
+                add(*[[g[int(pick[k])]] for g, pick in zip(G, picks)])
+        node_sets.append(len(sizes_of_groups) // 4)
+        sizes.append([len(g) for g in G])
+        enumerated.append(total <= quartets)
+    return dict(group_offsets=np.concatenate([[0], np.cumsum(sizes_of_groups)]).astype(np.int64),
+                group_taxa=np.asarray(taxa, dtype=np.int32), node_sets=np.asarray(node_sets, dtype=np.int64),
+                sizes=np.asarray(sizes, dtype=np.int64).reshape(-1, 4), enumerated=np.asarray(enumerated, dtype=bool))
+
+
 def get_net_pi_for_periods(pi, times):
     """Sum across sites of the PI matrix at the requested times (tapir/compute.py:76-79).
     A time >= T raises IndexError exactly as numpy indexing does in the reference."""

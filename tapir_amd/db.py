@@ -303,6 +303,71 @@ def write_unequal_quartet_db(db_name, names, rows, labels, quartets, model, clad
     conn.close()
 
 
+CONCORDANCE_RULE_VERSION = 1
+_CONCORDANCE_COLUMNS = ("pooled_c INTEGER, pooled_1 INTEGER, pooled_2 INTEGER, pooled_cf FLOAT, pooled_df1 FLOAT, pooled_df2 FLOAT, "
+                        "near_c INTEGER, near_1 INTEGER, near_2 INTEGER, sCF FLOAT, sDF1 FLOAT, sDF2 FLOAT, sN FLOAT, "
+                        "n_decisive INTEGER, n_quartets INTEGER")
+CONCORDANCE_DDL = [
+    "CREATE TABLE loci (id INTEGER PRIMARY KEY AUTOINCREMENT, locus TEXT)",
+    "CREATE TABLE internode (label TEXT PRIMARY KEY, size_a INT, size_b INT, size_c INT, size_d INT, n_all_quartets INTEGER, "
+    "n_quartets INT, enumerated INT)",
+    "CREATE TABLE clade (quartet TEXT, ntaxa INT, taxa TEXT, taxa_a TEXT, taxa_b TEXT, taxa_c TEXT, taxa_d TEXT, nearest TEXT)",
+    "CREATE TABLE concordance (id INT, internode TEXT, " + _CONCORDANCE_COLUMNS + ", FOREIGN KEY(id) REFERENCES loci(id))",
+    "CREATE TABLE concordance_all (internode TEXT, " + _CONCORDANCE_COLUMNS + ")",
+    "CREATE TABLE meta (key TEXT PRIMARY KEY, value TEXT)",
+]
+
+
+def _concordance_values(row):
+    """The 15 stored values of one row of 12: counts as integers, the pooled fractions (NULL when no quartet is decisive), NaN as
+    NULL."""
+    import math
+    pooled = [int(v) for v in row[:3]]
+    total = sum(pooled)
+    means = [None if math.isnan(v) else float(v) for v in row[6:10]]
+    return (pooled + [p / total if total else None for p in pooled] + [int(v) for v in row[3:6]] + means
+            + [int(row[10]), int(row[11])])
+
+
+def write_concordance_db(db_name, names, rows, all_rows, groups, sets, quartets, seed, clades):
+    """phylogenetic-informativeness-concordance.sqlite, a file of its own (every other output stays byte for byte what it is
+    without --site-concordance).  rows [L, n_nodes, 12] from pipeline.concordance_tables; all_rows [n_nodes, 12]: the same for
+    all loci analysed as one alignment; groups: compute.tree_concordance_groups' entries; sets: compute.concordance_sets'
+    tables; clades: (label, leaf names) per internode as the unequal-quartets file has them (at a polytomy the clade holds
+    more than groups A and B).  `clade` carries them with the four groups' taxa and the nearest-tip quartet, comma-joined.
+    Loci get the ids 1..L in file order."""
+    import numpy as np
+    if os.path.exists(db_name):
+        os.remove(db_name)
+    conn = sqlite3.connect(db_name)
+    c = conn.cursor()
+    for stmt in CONCORDANCE_DDL:
+        c.execute(stmt)
+    L, n_nodes = len(names), len(groups)
+    rows = np.asarray(rows, dtype=np.float64).reshape(L, n_nodes, 12)
+    all_rows = np.asarray(all_rows, dtype=np.float64).reshape(n_nodes, 12)
+    c.executemany("INSERT INTO loci(locus) VALUES (?)", [(locus_name(n),) for n in names])
+    keys = [r[0] for r in c.execute("SELECT id FROM loci ORDER BY id").fetchall()]
+    node_sets = [int(v) for v in sets["node_sets"]]
+    for i, (label, A, B, C, D, nearest) in enumerate(groups):
+        total = len(A) * len(B) * len(C) * len(D)
+        c.execute("INSERT INTO internode VALUES (?,?,?,?,?,?,?,?)",
+                  (label, len(A), len(B), len(C), len(D), total, node_sets[i + 1] - node_sets[i] - 2, int(bool(sets["enumerated"][i]))))
+        clade = clades[i][1]
+        c.execute("INSERT INTO clade VALUES (?,?,?,?,?,?,?,?)",
+                  (label, len(clade), ",".join(clade), ",".join(A), ",".join(B), ",".join(C), ",".join(D), ",".join(nearest)))
+    c.executemany("INSERT INTO concordance VALUES (" + ",".join("?" * 17) + ")",
+                  [[keys[l], groups[i][0]] + _concordance_values(rows[l, i]) for l in range(L) for i in range(n_nodes)])
+    c.executemany("INSERT INTO concordance_all VALUES (" + ",".join("?" * 16) + ")",
+                  [[groups[i][0]] + _concordance_values(all_rows[i]) for i in range(n_nodes)])
+    c.executemany("INSERT INTO meta VALUES (?,?)", [("seed", str(seed)), ("quartets_per_internode", str(quartets)),
+                                                    ("rule_version", str(CONCORDANCE_RULE_VERSION)),
+                                                    ("rule", "cells of exactly one base; xxyy, xyxy, xyyx with x != y")])
+    conn.commit()
+    c.close()
+    conn.close()
+
+
 LOCUS_SET_SUMS = {False: ("Y", "X", "Yy", "Xx", "XY"), True: ("Y", "X1", "X2", "Yy", "X1x1", "X2x2", "YX1", "YX2", "X1X2")}
 
 

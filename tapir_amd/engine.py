@@ -86,6 +86,10 @@ class ParbootOpts(ctypes.Structure):
                 ("locus_ids", _vp)]
 
 
+class ConcordanceSets(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_sets", _i64), ("group_offsets", _vp), ("group_taxa", _vp)]
+
+
 # every symbol include/tphip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("tphip_version", ctypes.c_int, []),
@@ -180,6 +184,10 @@ SYMBOLS = [
     ("tphip_pi_parametric_bootstrap", ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ParbootOpts), _vp, _vp, _vp, _vp]),
     ("tphip_summarize_rows_dev", ctypes.c_int, [_i32, _vp, _i64, _i32, _i32, _f64, _vp, _vp]),
     ("tphip_summarize_rows", ctypes.c_int, [_i32, _vp, _i64, _i32, _i32, _f64, _vp]),
+    ("tphip_concordance_counts_dev", ctypes.c_int, [_i32, _vp, _i64, _i64, _i32, _vp, _i64, ctypes.POINTER(ConcordanceSets), _vp, _vp]),
+    ("tphip_concordance_counts", ctypes.c_int, [_i32, _vp, _i64, _i64, _i32, _vp, _i64, ctypes.POINTER(ConcordanceSets), _vp]),
+    ("tphip_concordance_rows_dev", ctypes.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    ("tphip_concordance_rows", ctypes.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp]),
 ]
 
 _lib = None
@@ -1139,6 +1147,66 @@ def state_histogram(states, locus_offsets, device=0):
     _check(load().tphip_state_histogram(device, states.ctypes.data, ncols, ntaxa, off.ctypes.data, len(off) - 1,
                                         hist.ctypes.data))
     return hist
+
+
+def _concordance_sets(group_offsets, group_taxa):
+    """The set tables of the concordance calls: the struct and the arrays it points into (keep them alive)."""
+    goff, taxa = _np(group_offsets, np.int64).reshape(-1), _np(group_taxa, np.int32).reshape(-1)
+    if len(goff) % 4 != 1:
+        raise TphipError("group_offsets must have 4 * n_sets + 1 entries")
+    if len(goff) and len(taxa) < goff.max():   # (what the offsets say is the library's to judge; what they reach must exist)
+        raise TphipError("group_offsets reach beyond group_taxa")
+    sets = ConcordanceSets(struct_size=ctypes.sizeof(ConcordanceSets), n_sets=len(goff) // 4, group_offsets=goff.ctypes.data,
+                           group_taxa=taxa.ctypes.data if len(taxa) else None)
+    return sets, goff, taxa
+
+
+def concordance_counts(states, locus_offsets, group_offsets, group_taxa, ncols_total=None, device=0):
+    """Site concordance counts (tphip_concordance_counts): uint64 [L, n_sets, 3] = per locus and set of four taxon groups
+    A, B | C, D the quartets of A x B x C x D its columns support as ab|cd, ac|bd and ad|bc, over cells of exactly one base.
+    states uint8 [ntaxa, pitch]; ncols_total: the columns of the batch when the rows are longer than it (default: all of them).
+    group_offsets int64 [4 * n_sets + 1] into group_taxa (taxon rows): groups A, B, C, D of set s are 4s .. 4s + 3."""
+    states = _np(states, np.uint8)
+    off = _np(locus_offsets, np.int64)
+    ntaxa, pitch = states.shape
+    ncols = pitch if ncols_total is None else int(ncols_total)
+    sets, goff, taxa = _concordance_sets(group_offsets, group_taxa)
+    counts = np.zeros((len(off) - 1, sets.n_sets, 3), np.uint64)
+    _check(load().tphip_concordance_counts(int(device), states.ctypes.data, ncols, pitch, ntaxa, off.ctypes.data, len(off) - 1,
+                                           ctypes.byref(sets), counts.ctypes.data))
+    return counts
+
+
+def concordance_counts_dev(d_states, ncols_total, row_pitch, ntaxa, d_locus_offsets, nloci, group_offsets, group_taxa, d_counts,
+                           device=0, stream=0):
+    """tphip_concordance_counts_dev on device tensors: d_states uint8 [ntaxa, row_pitch], d_locus_offsets int64 [nloci + 1],
+    d_counts [nloci, n_sets, 3] of 64-bit integers; the set tables are host arrays.  Waits for its kernels."""
+    sets, goff, taxa = _concordance_sets(group_offsets, group_taxa)
+    _check(load().tphip_concordance_counts_dev(int(device), _ptr(d_states), int(ncols_total), int(row_pitch), int(ntaxa),
+                                               _ptr(d_locus_offsets), int(nloci), ctypes.byref(sets), _ptr(d_counts), stream))
+
+
+def concordance_rows(counts, node_sets, device=0):
+    """The per-internode rows of the concordance counts (tphip_concordance_rows): counts uint64 [L, n_sets, 3], node_sets int64
+    [n_nodes + 1] (internode i owns the sets node_sets[i] .. node_sets[i + 1] - 1: pooled, nearest-tip quartet, sampled
+    quartets).  Returns [L, n_nodes, 12] = pooled_c, pooled_1, pooled_2, near_c, near_1, near_2, sCF, sDF1, sDF2, sN,
+    n_decisive, n_quartets."""
+    counts = _np(counts, np.uint64)
+    if counts.ndim != 3 or counts.shape[2] != 3:
+        raise TphipError("counts must be [L, n_sets, 3]")
+    nodes = _np(node_sets, np.int64).reshape(-1)
+    rows = np.zeros((counts.shape[0], len(nodes) - 1, 12))
+    _check(load().tphip_concordance_rows(int(device), counts.ctypes.data, counts.shape[0], counts.shape[1], nodes.ctypes.data,
+                                         len(nodes) - 1, rows.ctypes.data))
+    return rows
+
+
+def concordance_rows_dev(d_counts, nloci, n_sets, node_sets, d_rows, device=0, stream=0):
+    """tphip_concordance_rows_dev on device tensors: d_counts [nloci, n_sets, 3], d_rows [nloci, n_nodes, 12]; node_sets is a
+    host array.  Waits for its kernel."""
+    nodes = _np(node_sets, np.int64).reshape(-1)
+    _check(load().tphip_concordance_rows_dev(int(device), _ptr(d_counts), int(nloci), int(n_sets), nodes.ctypes.data, len(nodes) - 1,
+                                             _ptr(d_rows), stream))
 
 
 def compress_columns(states, locus_offsets, device=0, want_map=True):

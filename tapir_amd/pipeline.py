@@ -1185,6 +1185,48 @@ def exact_locus_set_tables(eng, per_locus, pi, exch, run, quartets, order, model
         return out
 
 
+# concordance_tables works through the loci in blocks of at most this many columns whose counts ([loci][sets][3] 64-bit integers)
+# stay within this many bytes
+CONCORDANCE_BLOCK_COLS = 1 << 24
+CONCORDANCE_COUNT_BYTES = 256 << 20
+
+
+def concordance_tables(eng, alignments, per_locus, run, sets, subsets=None):
+    """Site concordance factors of the loci at the tree's internodes: what the alignments show where
+    the quartet stages predict.  Returns (rows [L, n_nodes, 12], totals uint64 [n_sets, 3]): per locus and internode pooled_c,
+    pooled_1, pooled_2, near_c, near_1, near_2, sCF, sDF1, sDF2, sN, n_decisive, n_quartets (engine.concordance_rows), and
+    the integer sum of the counts over these loci, from which the rows of all loci analysed as one alignment follow.
+
+    alignments: the loci's NEXUS files, re-read here and sliced for `subsets` as parametric_bootstrap_tables does; every
+    column of a locus counts, culled or not.  per_locus: the run's final rates (their lengths are checked).  sets:
+    compute.concordance_sets' tables, the same for every locus.  The loci go through in blocks of at most
+    CONCORDANCE_BLOCK_COLS columns whose counts fit CONCORDANCE_COUNT_BYTES; a locus' counts depend on nothing beside it, so
+    the blocking changes no bit.  A locus and internode with ncols * |A||B||C||D| >= 2^53 is refused: its counts might not
+    convert to fp64 exactly."""
+    L = len(alignments)
+    node_sets = np.asarray(sets["node_sets"], dtype=np.int64)
+    n_nodes, n_sets = len(node_sets) - 1, int(node_sets[-1])
+    rows = np.zeros((L, n_nodes, 12))
+    totals = np.zeros((n_sets, 3), dtype=np.uint64)
+    if L == 0 or n_nodes == 0:
+        return rows, totals
+    most = max(int(np.prod([int(v) for v in s])) for s in sets["sizes"])
+    for a, r in zip(alignments, per_locus):
+        if len(r) * most >= 2 ** 53:
+            raise PipelineError("{0}: {1} columns times {2} quartets around an internode reach 2^53: the concordance counts "
+                                "would not convert exactly".format(os.path.basename(a), len(r), most))
+    step = max(1, CONCORDANCE_COUNT_BYTES // (24 * n_sets))
+    for l0, l1, states, offsets in _observed_blocks(run, alignments, per_locus, subsets or {}, CONCORDANCE_BLOCK_COLS):
+        for k0 in range(0, l1 - l0, step):
+            k1 = min(l1 - l0, k0 + step)
+            part = states if (k0, k1) == (0, l1 - l0) else np.ascontiguousarray(states[:, offsets[k0]:offsets[k1]])
+            counts = eng.concordance_counts(part, offsets[k0:k1 + 1] - offsets[k0], sets["group_offsets"], sets["group_taxa"],
+                                            device=run.device)
+            rows[l0 + k0:l0 + k1] = eng.concordance_rows(counts, node_sets, device=run.device)
+            totals += counts.sum(axis=0, dtype=np.uint64)
+    return rows, totals
+
+
 def dot_progress():
     sys.stdout.write(".")
     sys.stdout.flush()
