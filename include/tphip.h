@@ -154,7 +154,14 @@ int tphip_plan_destroy(tphip_plan *plan);
 /* width W of a PI table row, and total columns */
 int32_t tphip_plan_table_width(const tphip_plan *plan);
 int64_t tphip_plan_ncols(const tphip_plan *plan);
-/* bytes of device scratch the *_dev entry points need (compacted column list, per-chunk PI partials) */
+/* bytes of device scratch the *_dev entry points need (compacted column list, per-chunk PI partials).
+ * Alignment: tphip_site_rates_dev, tphip_pi_tables_dev and tphip_run_dev need d_workspace 16-byte aligned (the widest access
+ * into it is a 16-byte store of packed tip words; its other regions hold 64-bit prefixes and the 64-bit keys of the
+ * de-duplication table, which atomics reach) and return TPHIP_ERR_INVALID, "workspace must be 16-byte aligned", before anything
+ * is enqueued otherwise.  Its content on entry is irrelevant and nothing beyond the stated size is touched.
+ * Data arrays of every *_dev entry point need the natural alignment of their element type only (1 for states and flags, 2 for
+ * 16-bit counts, 4 for int32, 8 for double and the 64-bit integers): a caller may slice one big buffer.  Nothing before or
+ * beyond an array's extent is written. */
 size_t tphip_plan_workspace_bytes(const tphip_plan *plan);
 /* chronogram length = sum of branch lengths (bf:1006-1013) and LDS stack depth of the program */
 double tphip_plan_chrono_length(const tphip_plan *plan);
@@ -525,7 +532,11 @@ int32_t tphip_bootstrap_width(const tphip_plan *plan);
 /* Device workspace of tphip_pi_bootstrap_dev: any size >= *min_bytes works and gives the same bits (the library blocks over
  * loci and, for a locus too long for the workspace, over replicate ranges); *preferred_bytes (<= about 1 GiB, or the
  * minimum) lets it take more loci per block.  opts = NULL sizes the workspace of tphip_pi_resample_dev instead, which holds
- * per-site integrals only and does not depend on nrep (a bootstrap workspace is always large enough for it too). */
+ * per-site integrals only and does not depend on nrep (a bootstrap workspace is always large enough for it too).
+ * Alignment: none.  The replicate-band calls (tphip_pi_resample_dev, tphip_pi_bootstrap_dev, tphip_posterior_pi_dev,
+ * tphip_pi_parametric_bootstrap_dev) start at the first multiple of 256 in d_workspace; *min_bytes, *preferred_bytes and
+ * tphip_parboot_workspace_bytes() already contain the 256 bytes that can cost, so a workspace of exactly *min_bytes at an odd
+ * address is enough. */
 int tphip_bootstrap_workspace_bytes(const tphip_plan *plan, const tphip_bootstrap_opts *opts, size_t *min_bytes,
                                     size_t *preferred_bytes);
 /* The weighted-sum core on caller-supplied counts (jackknife, delete-half, site weighting): d_counts is uint16

@@ -344,8 +344,12 @@ __global__ __launch_bounds__(kPiBlock) void classify_kernel(ClassifyParams P) {
     const int64_t c0 = lo + (int64_t)P.chunk_index[blockIdx.x] * kPiChunk + 4 * (int64_t)threadIdx.x;
     if (c0 >= hi) return;
     const bool full = (c0 + 4 <= hi);
-    const bool aligned = full && ((reinterpret_cast<uintptr_t>(P.states) & 3u) == 0) && ((P.ncols_total & 3) == 0) &&
-                         ((c0 & 3) == 0);
+    // (the three output pointers are the caller's or a workspace region: legal at their element type's alignment, while the
+    //  fast path stores 16 bytes through nres and packed and 4 through flag; with ncols_total and c0 multiples of 4 the bases
+    //  decide for every row and column.  Kernel arguments: the test is a few scalar ANDs)
+    const bool wide_ok = ((reinterpret_cast<uintptr_t>(P.states) & 3u) | (reinterpret_cast<uintptr_t>(P.flag) & 3u) |
+                          (reinterpret_cast<uintptr_t>(P.nres) & 15u) | (reinterpret_cast<uintptr_t>(P.packed) & 15u)) == 0;
+    const bool aligned = full && wide_ok && ((P.ncols_total & 3) == 0) && ((c0 & 3) == 0);
     const int n = full ? 4 : (int)(hi - c0);
     const bool fast = __all(aligned);   // wave-uniform: only the last wave of a locus can have a ragged thread
     ColumnScan4 c;

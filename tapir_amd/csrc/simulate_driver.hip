@@ -193,6 +193,7 @@ int tphip_pi_parametric_bootstrap_dev(tphip_plan* p, const double* d_rates, cons
     for (int32_t b = 0; b < B; ++b) {
         rc = sim_launch(p, d_rates, d_states_observed, d_ids, (uint32_t)b, o.seed, states, st);
         if (rc) return rc;
+        // (the plan's own workspace: `base` and L.plan_ws are multiples of 256, which meets tphip_run_dev's 16-byte rule)
         rc = tphip_run_dev(p, states, rate, subst, lnl, flag, nres, tables, base + L.plan_ws, p->ws.total, stream);
         if (rc) return rc;
         if (Wb > 0) parboot_rows_kernel<<<dim3((unsigned)p->nloci), dim3(256), 0, st>>>(tables, W, p->T, p->n_t, p->n_i, b, B, rows);

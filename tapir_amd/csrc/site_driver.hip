@@ -276,6 +276,14 @@ int launch_pi_tables(tphip_plan* p, const double* d_rates, const int32_t* d_nres
     return TPHIP_OK;
 }
 
+// The plan workspace's base (tphip_plan_workspace_bytes).  Its regions lie at multiples of 256 from it (layout_workspace) and are
+// reached through their own types: int64_t prefixes, int2 chunk counts, the 64-bit keys of the de-duplication table (atomics)
+// and, widest, classify_kernel's 16-byte stores into `packed`.  The three entry points below refuse any other base before
+// anything is enqueued.
+constexpr uintptr_t kPlanWsAlign = 16;
+static const char* const kPlanWsAlignMessage = "workspace must be 16-byte aligned";
+static bool plan_ws_aligned(const void* ws) { return ((uintptr_t)ws & (kPlanWsAlign - 1)) == 0; }
+
 static int take_slot(tphip_plan* p) {
     if (!p->profile) return -1;
     if (p->ev_used >= kProfileRing) {
@@ -290,6 +298,7 @@ int tphip_run_dev(tphip_plan* p, const uint8_t* d_states, double* d_rate, double
     if (!d_states || !d_rate || !d_subst || !d_lnl || !d_flag || !d_nres || !d_tables || !ws)
         return fail(TPHIP_ERR_INVALID, "null device pointer");
     if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
+    if (!plan_ws_aligned(ws)) return fail(TPHIP_ERR_INVALID, kPlanWsAlignMessage);
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     int slot = take_slot(p);
@@ -304,6 +313,7 @@ int tphip_site_rates_dev(tphip_plan* p, const uint8_t* d_states, double* d_rate,
     if (!d_states || !d_rate || !d_subst || !d_lnl || !d_flag || !d_nres || !ws)
         return fail(TPHIP_ERR_INVALID, "null device pointer");
     if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
+    if (!plan_ws_aligned(ws)) return fail(TPHIP_ERR_INVALID, kPlanWsAlignMessage);
     HIP_TRY(hipSetDevice(p->device));
     int slot = take_slot(p);
     int rc = launch_site_rates(p, d_states, d_rate, d_subst, d_lnl, d_flag, d_nres, ws, (hipStream_t)stream, slot);
@@ -319,6 +329,7 @@ int tphip_pi_tables_dev(tphip_plan* p, const double* d_rates, const int32_t* d_n
     if (!p) return fail(TPHIP_ERR_INVALID, "null plan");
     if (!d_rates || !d_tables || !ws) return fail(TPHIP_ERR_INVALID, "null device pointer");
     if (ws_bytes < p->ws.total) return fail(TPHIP_ERR_WORKSPACE, "workspace smaller than tphip_plan_workspace_bytes()");
+    if (!plan_ws_aligned(ws)) return fail(TPHIP_ERR_INVALID, kPlanWsAlignMessage);
     HIP_TRY(hipSetDevice(p->device));
     int slot = take_slot(p);
     if (slot >= 0) {

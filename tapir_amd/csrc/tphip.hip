@@ -504,6 +504,8 @@ static int host_enqueue(tphip_plan* p, const uint8_t* states, size_t spitch, hip
     hipStream_t cs = B.copy_stream, rs = B.run_stream;
     if (do_site) {
         if (!states || !rate || !subst || !lnl || !flag || !nres) return fail(TPHIP_ERR_INVALID, "null host pointer");
+        // (+ 1, and + 8 for the tables below: redundant guards against an empty allocation, which DevGrow::reserve handles
+        //  itself; no kernel writes past the states matrix or the tables: tests/test_gpu_abi_contract.py)
         rc = B.states.reserve(n * (size_t)p->ntaxa + 1);
         if (rc) return rc;
         uint8_t* d_states = (uint8_t*)B.states.p;
